@@ -15,13 +15,25 @@ resident in HBM when the timed region starts.  Default workload: BASELINE.json c
 d = 8, sqexp, n* = 4^8 = 65536 -- the configuration the metric's target is quoted on; it fits one GPU and
 is the same at every N (strong scaling).  `--workload c2|c3` select the other single-GPU configs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (dominant kernel, HIP
-events recorded inside the native library on the launching stream), `parity_timed_config_normwise_err` (the
-outputs of the LAST TIMED step against an independent small-batch predict, the K alpha = y - noise alpha
-identity and -- mean AND variance -- a vendor-LAPACK fp64 reference that shares nothing with the library; the run
-FAILS above 1e-10) and, at N = 1, `cpu_baseline` (three CPU lines on a bounded sample) and `abi_host_path` (the
-drop-in boundary as R's `.Call` would use it: gprc_gpr_fit_retry + gprc_gpr_predict with HOST pointers on the
-timed workload, one cold call -- first-call device allocations included -- and one warm call).
+Prints ONE JSON line on rank 0: `metric`, `value` (TFLOP/s of the timed steps), `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, the configuration and the per-phase split of the timed steps.  A plain run does only
+that: set up, warm up, time the --steps steps, write the outputs (--dump-outputs) and print the line.
+
+--full adds the checks and side measurements, each of which costs runs of its own: a parity gate against the
+oracle before timing, `kernels` / `roofline` (dominant kernel, HIP events recorded inside the native library on
+the launching stream during the timed steps), `parity_timed_config_normwise_err` (the outputs of the LAST TIMED
+step against an independent small-batch predict, the K alpha = y - noise alpha identity and -- mean AND variance --
+a vendor-LAPACK fp64 reference that shares nothing with the library; the run FAILS above 1e-10) and, at N = 1,
+`cpu_baseline` (three CPU lines on a bounded sample) and `abi_host_path` (the drop-in boundary as R's `.Call` would
+use it: gprc_gpr_fit_retry + gprc_gpr_predict with HOST pointers on the timed workload, one cold call -- first-call
+device allocations included -- and one warm call).  The --no-* switches leave out single legs of --full.
+
+--dump-outputs DIR writes what the LAST TIMED step computed, as a caller of GPR$new + GPR$predict receives it, to
+DIR/<name>.npy in float64: mean, var (all n* test points, every rank's slice), alpha, logp, L_diag (the diagonal
+of the factor) and L_sample (entries L[i, j], i >= j, of the factor: the whole lower triangle when it is small,
+else pairs drawn from a fixed seed).  An array longer than DUMP_MAX is replaced by a fixed, seeded sample of its
+entries, which holds the dump under 64 MB.  The inputs depend only on the arguments, so two builds run with the
+same arguments can be compared output for output.
 
 GPRC_BENCH_BACKEND=gloo: ranks exchange through gloo and share cuda:(LOCAL_RANK mod device count) -- how
 `pytest -m gpu` rehearses `--gpus 2` on a one-GPU box.  Default backend: nccl (= RCCL over xGMI).
@@ -54,6 +66,7 @@ WORKLOADS = {
 }
 KERNEL_IDS = {"constant": 0, "linear": 1, "polynomial": 2, "sqrexp": 3, "gammaexp": 4, "rationalquadratic": 5}
 SEED = 20261004
+DUMP_MAX = 1 << 20             # doubles per dumped array (8 MB): five arrays + logp stay under 64 MB
 
 
 def synth(n, d, n_star):
@@ -278,6 +291,40 @@ def abi_host_path(device, kname, params, X, y, Xs, resident_ms):
     return rec, mean, var
 
 
+# ---- --dump-outputs --------------------------------------------------------------------------------------------------
+def factor_offsets(geom, n):
+    """Offsets in the packed buffer of L_diag (L[j, j], j < n) and of L_sample (L[i, j], i >= j: the whole lower triangle
+    in row-major order when it has at most DUMP_MAX entries, else DUMP_MAX pairs drawn from a fixed seed).  Panel p holds
+    rows [p NB, n_pad) x columns [p NB, (p+1) NB), column-major with leading dimension n_pad - p NB (include/gprc_native.h),
+    so every offset lies inside panel j // NB for i < n <= n_pad."""
+    base = np.asarray(geom.offsets, dtype=np.int64)
+
+    def offsets(i, j):
+        p = j // geom.NB
+        return base[p] + (j - p * geom.NB) * (geom.n_pad - p * geom.NB) + (i - p * geom.NB)
+
+    diag = np.arange(n, dtype=np.int64)
+    if n * (n + 1) // 2 <= DUMP_MAX:
+        i, j = np.tril_indices(n)
+    else:
+        rng = np.random.Generator(np.random.Philox(SEED + 1))
+        a, b = rng.integers(0, n, DUMP_MAX), rng.integers(0, n, DUMP_MAX)
+        i, j = np.maximum(a, b), np.minimum(a, b)
+    return offsets(diag, diag), offsets(i.astype(np.int64), j.astype(np.int64))
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy in float64; an array longer than DUMP_MAX is cut to DUMP_MAX entries at ascending indices drawn
+    from a fixed seed (the same for every build)."""
+    os.makedirs(path, exist_ok=True)
+    for k, (name, a) in enumerate(arrays.items()):
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_MAX:
+            rng = np.random.Generator(np.random.Philox(SEED + 2 + k))
+            a = a[np.sort(rng.choice(a.size, DUMP_MAX, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ---- launching -------------------------------------------------------------------------------------------------------
 def free_port():
     s = socket.socket()
@@ -315,10 +362,13 @@ def main():
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--ntrain", type=int, default=0, help="override n (not --n: ambiguous for torch.distributed.run)")
     ap.add_argument("--nstar", type=int, default=0, help="override n* (random test points instead of the grid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-gate", action="store_true")
-    ap.add_argument("--no-abi-host-path", action="store_true", help="skip the host-pointer (.Call-shaped) cold/warm timing at N = 1")
-    ap.add_argument("--no-vendor-parity", action="store_true", help="skip the vendor-LAPACK leg of the timed-output parity check")
+    ap.add_argument("--full", action="store_true", help="also the parity checks, per-kernel / roofline figures, the host-pointer "
+                    "timing and the CPU baseline (off: set up, warm up, time the steps, dump, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity-gate", action="store_true", help="--full without the parity gate before timing")
+    ap.add_argument("--no-abi-host-path", action="store_true", help="--full without the host-pointer (.Call-shaped) cold/warm timing at N = 1")
+    ap.add_argument("--no-vendor-parity", action="store_true", help="--full without the vendor-LAPACK leg of the timed-output parity check")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         raise SystemExit("bench.py: --gpus >= 1, --steps >= 1, --warmup >= 0")
@@ -381,7 +431,7 @@ def main():
         return eng, ops, bufs
 
     gate_err = None
-    if not args.no_parity_gate:
+    if args.full and not args.no_parity_gate:
         gate_err = parity_gate(make_engine, comm)
 
     X, y, Xs = synth(n, d, n_star)
@@ -426,10 +476,18 @@ def main():
         torch.distributed.all_gather(outs, t)
         return [[float(v) for v in o.cpu()] for o in outs]
 
+    def all_gather_concat(a):
+        """this rank's slice of the test points -> all n* of them, in order (every rank takes part)"""
+        if not use_dist:
+            return a
+        t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda" if backend == "nccl" else "cpu")
+        return comm.gather_concat(t, [h - l for l, h in eng.slice_bounds(ns, world)]).cpu().numpy()
+
     for _ in range(args.warmup):
         step()
-    nat.lib().gprc_prof_reset()
-    nat.lib().gprc_prof_enable(1 if rank == 0 else 0)
+    if args.full:
+        nat.lib().gprc_prof_reset()
+        nat.lib().gprc_prof_enable(1 if rank == 0 else 0)
     fence()
     marks.clear()
     t0 = time.perf_counter()
@@ -437,26 +495,62 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    nat.lib().gprc_prof_enable(0)
+    if args.full:
+        nat.lib().gprc_prof_enable(0)
     elapsed = all_max([elapsed])[0]
 
-    mean = ops.to_host(bufs["mean"])[: hi - lo]
-    var = ops.to_host(bufs["var"])[: hi - lo]
-    sane = bool(np.isfinite(mean).all() and np.isfinite(var).all() and (var > -1e-8).all())
-    tp = timed_config_parity(eng, ops, bufs, X, y, Xs, lo, hi, mean, var)
-    vp = None
-    if rank == 0 and not args.no_vendor_parity:   # rank 0's slice against vendor LAPACK: independent of the library, mean AND variance
-        vp = vendor_parity(kname, X, y, Xs, lo, hi, mean, var, ops.to_host(eng.alpha)[:n], device)
-    vend_err = max(vp["alpha_err"], vp["mean_err"], vp["var_err"]) if vp else 0.0
-    par_err, id_err, bad, vend_err = all_max([tp["normwise_err"], tp["identity_err"],
-                                              0.0 if (sane and tp["var_bounds_ok"] and tp["bitwise_equal"]) else 1.0, vend_err])
-    parity_ok = bool(par_err <= PARITY_FAIL and id_err <= PARITY_FAIL and vend_err <= PARITY_FAIL and bad == 0.0)
+    if args.full or args.dump_outputs:
+        mean = ops.to_host(bufs["mean"])[: hi - lo]
+        var = ops.to_host(bufs["var"])[: hi - lo]
+    if args.dump_outputs:   # the last timed step's outputs, before any check runs on the engine
+        outputs = {"mean": all_gather_concat(mean), "var": all_gather_concat(var)}
+        if rank == 0:
+            d_off, s_off = factor_offsets(eng.geom, n)
+            idx = ops.from_host(np.concatenate([d_off, s_off]))
+            with ops.on(False):
+                picked = eng.packed.index_select(0, idx)
+            picked = ops.to_host(picked)
+            outputs.update(alpha=ops.to_host(eng.alpha)[:n], logp=ops.to_host(eng.scal)[:1], L_diag=picked[:n], L_sample=picked[n:])
+            write_outputs(args.dump_outputs, outputs)
+
+    parity_ok = True
+    if args.full:
+        sane = bool(np.isfinite(mean).all() and np.isfinite(var).all() and (var > -1e-8).all())
+        tp = timed_config_parity(eng, ops, bufs, X, y, Xs, lo, hi, mean, var)
+        vp = None
+        if rank == 0 and not args.no_vendor_parity:   # rank 0's slice against vendor LAPACK: independent of the library, mean AND variance
+            vp = vendor_parity(kname, X, y, Xs, lo, hi, mean, var, ops.to_host(eng.alpha)[:n], device)
+        vend_err = max(vp["alpha_err"], vp["mean_err"], vp["var_err"]) if vp else 0.0
+        par_err, id_err, bad, vend_err = all_max([tp["normwise_err"], tp["identity_err"],
+                                                  0.0 if (sane and tp["var_bounds_ok"] and tp["bitwise_equal"]) else 1.0, vend_err])
+        parity_ok = bool(par_err <= PARITY_FAIL and id_err <= PARITY_FAIL and vend_err <= PARITY_FAIL and bad == 0.0)
 
     phases = all_gather_rows([sum(a.elapsed_time(b) for a, b, _ in marks) / len(marks), sum(b.elapsed_time(c) for _, b, c in marks) / len(marks)])
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         flops = step_flops(n, ns)
+        out = {
+            "metric": "GPR predict-step achieved fp64 TFLOP/s (kernel fill + Cholesky + solves + mean/variance), n x n sqexp",
+            "value": round(flops / (elapsed / args.steps) * 1e-12, 4),
+            "unit": "TFLOP/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms, 3),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": f"{args.workload}: n={n} d={d} {kname} GPR fit+predict, n*={ns} (reference test-grid rule), noise=0.1",
+                       "n": n, "d": d, "n_star": ns, "kernel": kname, "kernel_params": params, "backend": backend if use_dist else None,
+                       "parallelism": f"1-D block-cyclic 512-column panels over {world} GPU(s), test points sliced"},
+            "phases_ms": {"fit_F1_F3": round(max(p[0] for p in phases), 3), "predict_P1_P3": round(max(p[1] for p in phases), 3),
+                          "per_rank": [{"rank": r, "fit_F1_F3": round(p[0], 3), "predict_P1_P3": round(p[1], 3)} for r, p in enumerate(phases)]},
+            "panel_broadcast": getattr(comm, "calibration", None) or {"choice": getattr(comm, "choice", None)},
+        }
+    if rank == 0 and args.full:
         prof = nat.prof_summary()
         kernels = {}
         for name, r in prof.items():
@@ -482,38 +576,20 @@ def main():
                     break
             except (OSError, KeyError, ValueError):
                 pass
-        out = {
-            "metric": "GPR predict-step achieved fp64 TFLOP/s (kernel fill + Cholesky + solves + mean/variance), n x n sqexp",
-            "value": round(flops / (elapsed / args.steps) * 1e-12, 4),
-            "unit": "TFLOP/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"{args.workload}: n={n} d={d} {kname} GPR fit+predict, n*={ns} (reference test-grid rule), noise=0.1",
-                       "n": n, "d": d, "n_star": ns, "kernel": kname, "kernel_params": params, "backend": backend if use_dist else None,
-                       "parallelism": f"1-D block-cyclic 512-column panels over {world} GPU(s), test points sliced"},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": symbol, "achieved": round(achieved, 3), "peak": FP64_MFMA_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(achieved / FP64_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
                          "traffic_unit": "bytes per launch (PMC, separate pass)", "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": round(dom["bytes"] / max(dom["count"], 1)),
                          "launches": dom["count"], "avg_launch_ms": round(dom["ms"] / max(dom["count"], 1), 4)},
-            "phases_ms": {"fit_F1_F3": round(max(p[0] for p in phases), 3), "predict_P1_P3": round(max(p[1] for p in phases), 3),
-                          "per_rank": [{"rank": r, "fit_F1_F3": round(p[0], 3), "predict_P1_P3": round(p[1], 3)} for r, p in enumerate(phases)]},
             "kernels": kernels,
             "frac_of_fp64_peak_end_to_end": round(flops / (elapsed / args.steps) * 1e-12 / (FP64_MFMA_PEAK_TFLOPS * world), 4),
-            "panel_broadcast": getattr(comm, "calibration", None) or {"choice": getattr(comm, "choice", None)},
             "parity_gate_normwise_err": gate_err,
             "parity_timed_config_normwise_err": par_err,
             "parity_timed_config": {"rows_rank0": tp["rows"], "bitwise_equal_to_small_batch": bad == 0.0 or tp["bitwise_equal"],
                                     "identity_K_alpha_normwise_err": id_err, "vendor_lapack": vp, "fail_above": PARITY_FAIL, "ok": parity_ok},
             "outputs_sane": sane,
-        }
+        })
         if world == 1 and not args.no_abi_host_path and parity_ok:
             # the resident engine's buffers go first: the cold call must find the device as R's first call would
             ops.close()
@@ -524,6 +600,7 @@ def main():
             out["abi_host_path"] = rec
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(kname, params, d)
+    if rank == 0:
         if parity_ok:
             print(json.dumps(out), flush=True)
         else:   # a fast step with wrong outputs is not a measurement: no JSON line on stdout

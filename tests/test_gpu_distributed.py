@@ -87,7 +87,7 @@ def test_two_ranks_one_gpu_gloo(tmp_path, world, n):
         assert np.array_equal(o["packed"], outs[0]["packed"])   # the factor is replicated on every rank
 
 
-def test_bench_gpus2_spawns_its_own_ranks():
+def test_bench_gpus2_spawns_its_own_ranks(tmp_path, orc):
     """`python bench.py --gpus 2` with no launcher: the parent (which never touches the GPU) starts two rank processes
     and relays rank 0's JSON line.  GPRC_BENCH_BACKEND=gloo lets both ranks share cuda:0 on a one-GPU box (RCCL wants a
     device per rank; the 2/4/8-device RCCL runs are the driver's).  The line must be an N = 2 line, carry the panel
@@ -98,7 +98,8 @@ def test_bench_gpus2_spawns_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "c2",
-                        "--ntrain", "2300", "--nstar", "1100", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--ntrain", "2300", "--nstar", "1100", "--no-cpu-baseline", "--full", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -108,6 +109,13 @@ def test_bench_gpus2_spawns_its_own_ranks():
     assert [p["rank"] for p in out["phases_ms"]["per_rank"]] == [0, 1]
     assert out["parity_timed_config"]["ok"] and out["parity_timed_config_normwise_err"] <= TOL
     assert out["parity_gate_normwise_err"] <= TOL and out["value"] > 0
+    import bench                                                  # --dump-outputs: both ranks' slices of the test points, in order
+    X, y, Xs = bench.synth(2300, 8, 1100)
+    ref = orc.gpr_fit(orc.SQREXP, [1.0], X.T, y, 0.1)
+    mref, vref = orc.gpr_predict(orc.SQREXP, [1.0], X.T, ref["L"], ref["alpha"], Xs.T)
+    mean, var = np.load(tmp_path / "mean.npy"), np.load(tmp_path / "var.npy")
+    assert mean.shape == (1100,) and nerr(mean, mref) <= TOL and nerr(var, vref) <= TOL
+    assert nerr(np.load(tmp_path / "alpha.npy"), ref["alpha"]) <= TOL
 
 
 def test_bench_c1_workload_has_a_line():
@@ -118,12 +126,38 @@ def test_bench_c1_workload_has_a_line():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-abi-host-path"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["config"]["n"] == 256 and out["config"]["d"] == 1 and out["config"]["n_star"] == 10000
     assert out["parity_timed_config"]["ok"] and out["parity_timed_config_normwise_err"] <= TOL and out["parity_gate_normwise_err"] <= TOL
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path, orc):
+    """A plain `bench.py` run (no --full) prints the headline line without the checks of --full, and --dump-outputs writes
+    what its last timed step computed -- mean, var, alpha, logp and the factor (diagonal + the whole lower triangle at
+    n = 256) -- in float64; every array agrees with the CPU oracle on the same synthetic inputs."""
+    import json
+    import subprocess
+    import bench
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f64" and out["unit"] == "TFLOP/s"
+    assert not {"roofline", "kernels", "parity_timed_config", "cpu_baseline", "abi_host_path"} & set(out)
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("mean", "var", "alpha", "logp", "L_diag", "L_sample")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    X, y, Xs = bench.synth(256, 1, None)
+    ref = orc.gpr_fit(orc.SQREXP, [1.0], X.T, y, 0.1)
+    mref, vref = orc.gpr_predict(orc.SQREXP, [1.0], X.T, ref["L"], ref["alpha"], Xs.T)
+    assert got["mean"].shape == (10000,) and nerr(got["mean"], mref) <= TOL and nerr(got["var"], vref) <= TOL
+    assert nerr(got["alpha"], ref["alpha"]) <= TOL and nerr(got["logp"], [ref["logp"]]) <= TOL
+    assert nerr(got["L_diag"], np.diag(ref["L"])) <= TOL and nerr(got["L_sample"], ref["L"][np.tril_indices(256)]) <= TOL
 
 
 def test_bench_gpus4_gloo_rehearsal_n16384():
@@ -137,7 +171,7 @@ def test_bench_gpus4_gloo_rehearsal_n16384():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1", "--workload", "c2",
-                        "--ntrain", "16384", "--nstar", "8192", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--ntrain", "16384", "--nstar", "8192", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 4 and out["config"]["n"] == 16384 and [p["rank"] for p in out["phases_ms"]["per_rank"]] == [0, 1, 2, 3]

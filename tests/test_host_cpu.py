@@ -231,3 +231,35 @@ def test_bench_refuses_a_world_size_it_was_not_asked_for():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "refusing" in r.stderr and not r.stdout.strip()
+
+
+@pytest.mark.parametrize("n", [256, 2300])
+def test_bench_dump_reads_the_factor_from_the_packed_layout(n, tmp_path):
+    """bench.py --dump-outputs picks L_diag and L_sample out of the packed block-column buffer: every offset must land on
+    L[i, j] with i >= j (n = 256: the whole lower triangle, row-major; n = 2300: seeded pairs, the same on every call), and
+    write_outputs caps an array at DUMP_MAX entries by a seeded sample, in float64."""
+    import bench
+    from gprc_amd.distributed import Geometry
+    g = Geometry(n)
+    rng = np.random.default_rng(3)
+    L = np.tril(rng.uniform(1, 2, (g.n_pad, g.n_pad)))
+    packed = np.full(g.packed_size, np.nan)
+    for p in range(g.P):                      # panel p: rows [p NB, n_pad) x columns [p NB, (p+1) NB), column-major
+        c0 = p * g.NB
+        packed[g.panel_slice(p)] = L[c0:, c0:c0 + g.NB].ravel(order="F")
+    d_off, s_off = bench.factor_offsets(g, n)
+    assert d_off.min() >= 0 and max(d_off.max(), s_off.max()) < g.packed_size and s_off.min() >= 0
+    assert np.array_equal(packed[d_off], np.diag(L)[:n])
+    if n * (n + 1) // 2 <= bench.DUMP_MAX:
+        assert np.array_equal(packed[s_off], L[np.tril_indices(n)])
+    else:
+        assert s_off.size == bench.DUMP_MAX
+        assert np.array_equal(s_off, bench.factor_offsets(g, n)[1])
+    vals = packed[s_off]
+    assert np.isfinite(vals).all() and (vals >= 1).all()        # lower triangle of L only, never the padding or above it
+    big = np.arange(bench.DUMP_MAX + 7, dtype=np.float64)
+    bench.write_outputs(str(tmp_path / "a"), {"x": big, "y": np.float32([1.5])})
+    bench.write_outputs(str(tmp_path / "b"), {"x": big, "y": np.float32([1.5])})
+    xa, xb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert xa.dtype == np.float64 and xa.size == bench.DUMP_MAX and np.array_equal(xa, xb) and (np.diff(xa) > 0).all()
+    assert np.load(tmp_path / "a" / "y.npy").tolist() == [1.5]

@@ -13,7 +13,7 @@ for sp in 0 1; do echo "== GPRC_CHAIN_SPLIT=$sp"; GPRC_CHAIN_SPLIT=$sp GPRC_SERV
 tail -1 $out/trace.txt
 GPRC_LIB_SUFFIX=_cprof timeout -k 10 200 python tools/chain_prof.py 8192 2>&1 | grep -v amdgpu.ids > $out/prof.txt
 for sp in 0 1; do
-  GPRC_CHAIN_SPLIT=$sp timeout -k 10 300 python bench.py --workload c2 --no-cpu-baseline 2>&1 | grep "^{" > $out/c2_split$sp.json
+  GPRC_CHAIN_SPLIT=$sp timeout -k 10 300 python bench.py --full --workload c2 --no-cpu-baseline 2>&1 | grep "^{" > $out/c2_split$sp.json
   python -c "import json;d=json.load(open('$out/c2_split$sp.json'));print('C2 split=$sp step ms',d['ms_per_step'],'fit',d['phases_ms']['fit_F1_F3'],'TFLOP/s',d['value'])" | tee -a $out/configs.txt
   GPRC_CHAIN_SPLIT=$sp timeout -k 10 300 python tools/bench_gpc.py 2>&1 | grep "^{" > $out/c5_split$sp.json
   python -c "import json;d=json.load(open('$out/c5_split$sp.json'));print('C5 split=$sp ms per IRLS iteration',d['ms_per_irls_iteration'],'fit',d['fit_ms'],'potrf TFLOP/s',d['potrf_tflops_per_iteration'])" | tee -a $out/configs.txt

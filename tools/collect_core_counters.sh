@@ -7,7 +7,7 @@ set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/core; mkdir -p $out
 export GPRC_SERVICE=0
-W="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity-gate --no-abi-host-path --no-vendor-parity ${CORE_ARGS:-}"
+W="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity-gate --no-abi-host-path --no-vendor-parity ${CORE_ARGS:-}"
 rocprofv3 -L > $out/avail.txt 2>&1 || true
 pass() {  # name counters...
   local name=$1; shift

@@ -4,7 +4,7 @@
 set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/mfma; mkdir -p $out
-W="python3 bench.py --workload c3 --steps 1 --warmup 0 --no-cpu-baseline --no-parity-gate"
+W="python3 bench.py --full --workload c3 --steps 1 --warmup 0 --no-cpu-baseline --no-parity-gate"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $out/pmc -- $W > $out/pmc.log 2>&1; echo "pmc rc=$?"
 python3 - <<'PY' > $out/mfma_util_summary.txt
 import csv, glob, collections

@@ -4,8 +4,8 @@
 set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/final2; mkdir -p $out
-timeout -k 10 200 python3 bench.py --workload c2 --no-cpu-baseline > $out/c2.json 2> $out/c2.err; echo "c2 rc=$?"
-timeout -k 10 300 python3 bench.py --workload c3 --no-cpu-baseline > $out/c3.json 2> $out/c3.err; echo "c3 rc=$?"
+timeout -k 10 200 python3 bench.py --full --workload c2 --no-cpu-baseline > $out/c2.json 2> $out/c2.err; echo "c2 rc=$?"
+timeout -k 10 300 python3 bench.py --full --workload c3 --no-cpu-baseline > $out/c3.json 2> $out/c3.err; echo "c3 rc=$?"
 timeout -k 10 200 python3 tools/bench_gpc.py > $out/c5.json 2> $out/c5.err; echo "c5 rc=$?"
 timeout -k 10 200 python3 tools/bench_fit.py > $out/fit.json 2> $out/fit.err; echo "fit rc=$?"
 timeout -k 10 300 python3 tools/trsv_bench.py 8192 16384 32768 65536 > $out/trsv.txt 2>&1; echo "trsv rc=$?"

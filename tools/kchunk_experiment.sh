@@ -6,10 +6,10 @@
 set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/kchunk; mkdir -p $out
-W="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity-gate"
+W="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity-gate"
 for kc in 0 16 8 4; do
   export GPRC_KCHUNK=$kc
-  timeout -k 10 300 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_k$kc.json 2> $out/bench_k$kc.err || { echo "bench k=$kc failed"; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_k$kc.json 2> $out/bench_k$kc.err || { echo "bench k=$kc failed"; exit 1; }
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch_k$kc -- $W > $out/fetch_k$kc.log 2>&1 || { echo "pmc fetch k=$kc failed"; exit 1; }
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $out/gui_k$kc -- $W > $out/gui_k$kc.log 2>&1 || { echo "pmc gui k=$kc failed"; exit 1; }
 done
