@@ -61,6 +61,7 @@ PROTOTYPES = {
     "gprc_gpr_log_marginal": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.POINTER(C.c_double)]),
     "gprc_fit_gradient": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, _dp]),
     "gprc_gpr_predict": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp]),
+    "gprc_gpr_extend": (C.c_int, [_vp, _vp, _i64, _vp]),
     "gprc_model_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_model_get_L": (C.c_int, [_vp, _vp, _i64]),
     "gprc_gpr_get_alpha": (C.c_int, [_vp, _vp]),

@@ -509,10 +509,11 @@ int factor_all(gprc_ctx* ctx, double* packed, int64_t n_pad, double* winv, int* 
 // left of its last column and (b) a row tile's left-looking pass starts at the tile's first column: n^3 / 3 flops for the whole
 // inverse instead of n^3.  Everything skipped is a product with an exact zero: the same bits as the dense solve
 // (test_fit_gradient_triangular_solve_is_bit_identical); sspart must have been zeroed (rows never reached keep their zeros).
+// p_end >= 0: only panels [0, p_end) are solved (columns [0, p_end NB) of the result; later columns never feed back into them).
 int solve_rows(gprc_ctx* ctx, const double* packed, const double* winv, int64_t n_pad, double* vt, int64_t ldv, int64_t m_pad,
-               double* sspart = nullptr, int64_t tri_row0 = -1) {
+               double* sspart = nullptr, int64_t tri_row0 = -1, int64_t p_end = -1) {
   hipStream_t s = ctx->stream;
-  const int64_t P = n_pad / NB;
+  const int64_t P = p_end >= 0 ? std::min(p_end, n_pad / NB) : n_pad / NB;
   const char* mode = std::getenv("GPRC_SOLVE");
   int64_t G = (4096 + (m_pad / 128) * (NB / NBI) - 1) / ((m_pad / 128) * (NB / NBI));
   if (mode && std::strcmp(mode, "left") == 0) G = 1;
@@ -783,6 +784,72 @@ int chunk_workspace(gprc_ctx* ctx, int64_t n_pad, int64_t ns, bool want_tmp, int
     rows = std::max<int64_t>(256, rows / 2 / 256 * 256);
   }
   *rows_out = rows;
+  return 0;
+}
+
+// ---- extend: append observations to a fitted GPR model (DESIGN.md section "Extend") -----------------------------------------
+// Refactor from the last panel boundary n0 = floor(n / NB) NB: columns [0, n0) of L stay valid in L' = chol(K' + noise I).  The
+// TAIL -- old points [n0, n) and the m new ones, t = n' - n0 rows -- gets
+//   L21 = K(X_tail, X[, 1:n0]) L11^-T          solve_rows with the OLD factor, panels [0, p0) only (later columns never feed back)
+//   panels [0, p0) of L'                       extend_merge: old rows [p NB, n0) + the tail rows of L21, in the new layout
+//   L22 = chol(K22 + noise I - L21 L21^T)      fill + one update pass with panels [0, p0) + factor_all on the SUB-VIEW
+// The sub-view: panels p0.. of a packed matrix of n_pad' are a packed matrix of n_pad' - n0 of their own, at packed' +
+// panel_offset(n_pad', p0) (offset(n_pad, p0 + k) - offset(n_pad, p0) = offset(n_pad - p0 NB, k)), its winv at winv' + n0 NBI and its
+// inv at inv' + p0 NB NB -- so the factor schedules run on it unchanged.  Everything is built in NEW buffers (peak memory: the old
+// model plus the new one); the model changes only on success.  *info_out > 0: the global 1-based column of the first non-PD minor.
+int gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const double* y_new, int* info_out) {
+  gprc_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n, d = m->d, n_pad = m->n_pad;
+  const int64_t n1 = n + mnew, n_pad1 = pad_up(n1, NB), P1 = n_pad1 / NB;
+  const int64_t n0 = n / NB * NB, p0 = n0 / NB, t = n1 - n0, t_pad = pad_up(t, 128);
+  *info_out = 0;
+  In xin, yin;
+  GPRC_TRY(xin.set(s, X_new, d * mnew));
+  GPRC_TRY(yin.set(s, y_new, mnew));
+  gprc_model* nm = nullptr;   // the new buffers; whatever it holds at the end goes back to the pool
+  GPRC_TRY(alloc_model(ctx, MODEL_GPR, m->ks, n1, d, &nm));
+  struct Guard { gprc_model* p; ~Guard() { free_model(p); } } guard{nm};
+  DevMem inv;
+  GPRC_TRY(inv.alloc(gprc_solve_inv_size(n_pad1)));
+  GPRC_HIP(hipMemcpyAsync(nm->X, m->X, sizeof(double) * d * n, hipMemcpyDeviceToDevice, s));                  // cbind(X, X_new)
+  GPRC_HIP(hipMemcpyAsync(nm->X + d * n, xin.dev, sizeof(double) * d * mnew, hipMemcpyDeviceToDevice, s));
+  GPRC_HIP(hipMemsetAsync(nm->y, 0, sizeof(double) * n_pad1, s));                                              // c(y, y_new), zero padded
+  GPRC_HIP(hipMemcpyAsync(nm->y, m->y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  GPRC_HIP(hipMemcpyAsync(nm->y + n, yin.dev, sizeof(double) * mnew, hipMemcpyDeviceToDevice, s));
+  if (p0 > 0) {
+    const int64_t ldv = t_pad + ctx->vt_pad;
+    double* vt = nullptr;
+    GPRC_TRY(ws_get(ctx, 0, ldv * n0, &vt));
+    GPRC_TRY(launch_fill(s, m->ks, nm->X + d * n0, t, m->X, n, d, vt, ldv, 0, t_pad, 0, n0, PAD_ZERO, 0.0));   // K(X_tail, X[, 1:n0])
+    GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, ldv, t_pad, nullptr, -1, p0));                      // L21 = . L11^-T
+    GPRC_TRY(launch_extend_merge(s, m->packed, n_pad, vt, ldv, t_pad, t, n0, n_pad1, nm->packed));
+    GPRC_HIP(hipMemcpyAsync(nm->winv, m->winv, sizeof(double) * n0 * NBI, hipMemcpyDeviceToDevice, s));         // kept diagonal blocks
+  }
+  auto fill_tail = [&]() -> int {   // K22 + noise I (identity padding), then - L21 L21^T in one pass (K = n0)
+    for (int64_t p = p0; p < P1; ++p)
+      GPRC_TRY(launch_fill(s, m->ks, nm->X, n1, nm->X, n1, d, nm->packed + panel_offset(n_pad1, p), panel_ld(n_pad1, p), p * NB,
+                           n_pad1 - p * NB, p * NB, NB, PAD_IDENTITY, m->noise));
+    if (p0 == 1) GPRC_TRY(launch_trailing_update(s, nm->packed, n_pad1, 0, p0, P1, 1));
+    else if (p0 > 1) GPRC_TRY(launch_trailing_range(s, nm->packed, n_pad1, 0, p0, p0, P1, 1));
+    return 0;
+  };
+  GPRC_TRY(fill_tail());
+  int info = 0;
+  GPRC_TRY(factor_all_or_refill(ctx, nm->packed + panel_offset(n_pad1, p0), n_pad1 - n0, nm->winv + n0 * NBI, &info, inv.p + p0 * NB * NB,
+                                fill_tail));
+  if (info != 0) { *info_out = info + (int)n0; return 0; }
+  GPRC_TRY(launch_inv512(s, nm->packed, n_pad1, nm->winv, inv.p, 0, p0));
+  GPRC_HIP(hipMemcpyAsync(nm->alpha, nm->y, sizeof(double) * n_pad1, hipMemcpyDeviceToDevice, s));
+  GPRC_TRY(launch_trsv(s, nm->packed, inv.p, n_pad1, nm->alpha, 0, nm->work));
+  GPRC_TRY(launch_trsv(s, nm->packed, inv.p, n_pad1, nm->alpha, 1, nm->work));
+  GPRC_TRY(launch_logp(s, nm->packed, n_pad1, n1, nm->y, nm->alpha, ctx->scal_dev));
+  GPRC_HIP(hipMemcpyAsync(&nm->logp, ctx->scal_dev, sizeof(double), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  // success: the new buffers become the model's, the old ones leave with `nm` (free_model sizes them by the swapped n, n_pad)
+  std::swap(m->n, nm->n); std::swap(m->n_pad, nm->n_pad); std::swap(m->X, nm->X); std::swap(m->y, nm->y);
+  std::swap(m->packed, nm->packed); std::swap(m->winv, nm->winv); std::swap(m->alpha, nm->alpha); std::swap(m->work, nm->work);
+  std::swap(m->logp, nm->logp);
   return 0;
 }
 
@@ -1083,6 +1150,25 @@ int gprc_gpr_predict(gprc_model* m, const double* X_star, int64_t ns, int pointw
   GPRC_TRY(mean.finish(s));
   GPRC_TRY(var.finish(s));
   GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gprc_gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const double* y_new) {
+  if (!m) { set_error("extend: null model"); return GPRC_ERR_ARG; }
+  if (m->type != MODEL_GPR) { set_error("extend: not a GPR model (a GPC fit must iterate again: refit)"); return GPRC_ERR_ARG; }
+  if (m->borrowed) {
+    set_error("extend: the model borrows its buffers (gprc_gpr_model_from_device / gprc_mgpu_model_rank); refit on the concatenated data");
+    return GPRC_ERR_ARG;
+  }
+  if (mnew < 1 || !X_new || !y_new) { set_error("extend: bad arguments (m >= 1 observations, non-null X_new and y_new)"); return GPRC_ERR_ARG; }
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("extend: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(use_device(m->ctx));
+  int info = 0;
+  GPRC_TRY(gpr_extend(m, X_new, mnew, y_new, &info));
+  if (info != 0) {
+    set_error("extend: the leading minor of order " + std::to_string(info) + " is not positive definite (model unchanged)");
+    return info;
+  }
   return 0;
 }
 

@@ -132,6 +132,10 @@ int launch_row_reduce(hipStream_t s, const double* vt, int64_t ld, int64_t rows,
                       double* work);
 // out[0] = -0.5*y.alpha - sum(log(diag L)) - n/2 log(2 pi)   (R/GPRclass.R:153); n valid entries
 int launch_logp(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, const double* y, const double* alpha, double* out);
+// extend (gpr_extend): panels [0, n0 / NB) of the factor in layout n_pad_new from the old factor (layout n_pad_old: its rows < n0) and
+// the solved tail rows vt (t_pad x n0, ld ldv; t valid rows = global rows n0 .. n0 + t - 1), zero below; bandwidth-bound
+int launch_extend_merge(hipStream_t s, const double* old_packed, int64_t n_pad_old, const double* vt, int64_t ldv, int64_t t_pad, int64_t t,
+                        int64_t n0, int64_t n_pad_new, double* packed);
 // unpack the factor into a dense n x n lower matrix (upper = 0)
 int launch_unpack_L(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, double* out, int64_t ld_out);
 // out[i] = (minuend ? minuend[i] : 0) -/+ sum_{t < nparts} part[t * stride + i], summed in t order: the tail of the fused

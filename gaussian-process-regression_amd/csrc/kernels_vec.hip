@@ -6,6 +6,7 @@
 //   gpc_*           the elementwise IRLS stages                  R/GPCclass.R:78-86
 // All reductions use a fixed summation order (no floating-point atomics): results are bitwise
 // reproducible run to run.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -389,6 +390,45 @@ __global__ __launch_bounds__(256) void unpack_kernel(const double* packed, int64
   for (int64_t j = blockIdx.y; j < n; j += gridDim.y) out[i + j * ld_out] = (i >= j) ? *packed_at(packed, n_pad, i, j) : 0.0;
 }
 
+// ---- extend: relayout of the kept columns ---------------------------------------------------------
+// Panels [0, p0) of the extended factor (layout n_pad_new): in panel p, column c, local row r (global row p NB + r)
+//   r <  split = n0 - p NB   : the old factor (layout n_pad_old, same panel, same column, same local row)
+//   r >= split               : row r - split of the solved tail rows vt (column p NB + c), zero from global row n_new on.
+// One column = two contiguous runs; 16-byte accesses (every run start is even: n0, NB, the leading dimensions and ldv are).
+// Grid-strided over the p0 NB columns; a thread moves four double2 per pass (loads first, then stores).
+constexpr int MERGE_THREADS = 256, MERGE_UNROLL = 4;
+__global__ __launch_bounds__(MERGE_THREADS) void extend_merge_kernel(const double* __restrict__ old_packed, int64_t n_pad_old,
+                                                                     const double* __restrict__ vt, int64_t ldv, int64_t t, int64_t n0,
+                                                                     int64_t p0, int64_t n_pad_new, double* __restrict__ packed) {
+  const int64_t cols = p0 * NB;
+  for (int64_t col = blockIdx.x; col < cols; col += gridDim.x) {
+    const int64_t p = col / NB, c = col - p * NB;
+    const int64_t ld_new = n_pad_new - p * NB, split = n0 - p * NB;
+    const double* src_old = old_packed + panel_offset(n_pad_old, p) + c * (n_pad_old - p * NB);
+    const double* src_vt = vt + col * ldv;
+    double* dst = packed + panel_offset(n_pad_new, p) + c * ld_new;
+    for (int64_t r0 = 2 * (int64_t)threadIdx.x; r0 < ld_new; r0 += 2 * MERGE_THREADS * MERGE_UNROLL) {
+      double2 v[MERGE_UNROLL];
+#pragma unroll
+      for (int k = 0; k < MERGE_UNROLL; ++k) {
+        const int64_t r = r0 + 2 * MERGE_THREADS * k;
+        v[k] = make_double2(0.0, 0.0);
+        if (r < split) {
+          v[k] = *reinterpret_cast<const double2*>(src_old + r);
+        } else if (r < ld_new && r - split < t) {   // t odd: row t of vt exists (t_pad > t), the pair stays inside
+          v[k] = *reinterpret_cast<const double2*>(src_vt + (r - split));
+          if (r - split + 1 >= t) v[k].y = 0.0;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < MERGE_UNROLL; ++k) {
+        const int64_t r = r0 + 2 * MERGE_THREADS * k;
+        if (r < ld_new) *reinterpret_cast<double2*>(dst + r) = v[k];
+      }
+    }
+  }
+}
+
 // ---- GPC (Laplace / IRLS) stages ----------------------------------------------------------------
 __device__ __forceinline__ double sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }  // R/GPCclass.R:63
 
@@ -592,6 +632,21 @@ int launch_sum_partials(hipStream_t s, const double* part, int64_t nparts, int64
   if (rows <= 0) return 0;
   ProfScope ps(s, PK_ROWREDUCE, (double)rows * nparts, 8.0 * rows * nparts);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(blocks(rows, 256)), dim3(256), 0, s, part, nparts, stride, rows, minuend, out);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_extend_merge(hipStream_t s, const double* old_packed, int64_t n_pad_old, const double* vt, int64_t ldv, int64_t t_pad, int64_t t,
+                        int64_t n0, int64_t n_pad_new, double* packed) {
+  const int64_t p0 = n0 / NB;
+  if (p0 <= 0) return 0;
+  if (n0 % NB || n0 > n_pad_old || n_pad_new < n0 + t || t < 1 || t_pad % 128 || t_pad < t || ldv < t_pad || ldv % 2) {
+    set_error("extend_merge: bad layout arguments");
+    return GPRC_ERR_ARG;
+  }
+  const int64_t grid = std::min<int64_t>(p0 * NB, 2048);
+  hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)grid), dim3(MERGE_THREADS), 0, s, old_packed, n_pad_old, vt, ldv, t, n0, p0, n_pad_new,
+                     packed);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

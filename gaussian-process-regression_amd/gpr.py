@@ -128,6 +128,36 @@ class GPR:
         nat.check(nat.lib().gprc_gpr_predict(self._model, Xs.ctypes.data, ns, 0, mean.ctypes.data, cov.ctypes.data))
         return [mean.reshape(-1, 1), cov]                                                    # :168
 
+    def add_data(self, X_new, y_new):
+        """Append observations: the model becomes GPR$new(cbind(X, X_new), c(y, y_new), noise = $noise, k) -- same kernel,
+        parameters and stored noise (a jitter the fit added is kept, never re-tried) -- without refactoring the whole matrix
+        (gprc_gpr_extend).  Returns self.  An extended matrix that is not positive definite raises NotPositiveDefinite and
+        leaves the model unchanged."""
+        d = self._X.shape[0]
+        Xa = np.asarray(X_new)
+        if Xa.dtype.kind not in "fiub" or not _is_numeric_vector(y_new):
+            raise TypeError("is.numeric(X_new), is.vector(y_new), is.numeric(y_new) are not all TRUE")     # as :129
+        if Xa.size % d:
+            raise ValueError("is.numeric(X_new), length(X_new) %% nrow(self$X) == 0 are not all TRUE")     # as :156
+        Xn = as_points(Xa, d=d, what="X_new") if Xa.ndim <= 1 else as_points(Xa, what="X_new")
+        if Xn.shape[0] != d:
+            raise ValueError("X_new must have nrow(X) rows")
+        y_new = np.ascontiguousarray(np.asarray(y_new, dtype=np.float64))
+        if y_new.size != Xn.shape[1]:
+            raise ValueError("length(y_new) == ncol(X_new) is not TRUE")                                  # as :133
+        if self._mmodel is not None:
+            raise ValueError("add_data: a model fitted over several devices cannot be extended; refit GPR on the concatenated data")
+        nat.check(nat.lib().gprc_gpr_extend(self._model, Xn.ctypes.data, Xn.shape[1], y_new.ctypes.data))
+        self._X = np.asfortranarray(np.concatenate([self._X, Xn], axis=1))
+        self._y = np.concatenate([self._y, y_new])
+        alpha = np.empty(self._X.shape[1])
+        lp = C.c_double()
+        nat.check(nat.lib().gprc_gpr_get_alpha(self._model, alpha.ctypes.data))
+        nat.check(nat.lib().gprc_gpr_get_logp(self._model, C.byref(lp)))
+        self._alpha, self._logp = alpha, lp.value
+        self._L = None
+        return self
+
     def posterior_draws(self, n=5, limits=None, length_out=200, *, z=None, rng=None):
         """The data behind GPR$plot_posterior_draws(n = 5, limits = expand_range(X), length.out = 200)  --
         R/GPRclass.R:190-199 (one-dimensional inputs only, :192-195): test points, cbind(mean, diag(cov)) and n draws

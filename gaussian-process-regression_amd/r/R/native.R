@@ -81,6 +81,19 @@ covariance_matrix <- function(A, B, covariance_function) {
   .Call(gprc_R_gpr_predict, private$.handle, X_star, isTRUE(pointwise_var))
 }
 
+# body of GPR$add_data after its input checks, native branch: the model becomes GPR$new(cbind(X, X_new), c(y, y_new),
+# noise = $noise, k) without a refit (gprc_gpr_extend); a multi-GPU model is refitted by the caller
+.gpr_add_data_native <- function(private, X_new, y_new) {
+  if (isTRUE(private$.multi)) stop("gprc: a model fitted over several GPUs cannot be extended; refit on the concatenated data")
+  storage.mode(X_new) <- "double"
+  res <- .Call(gprc_R_gpr_extend, private$.handle, X_new, as.double(y_new))
+  private$.X <- cbind(private$.X, X_new)
+  private$.y <- c(private$.y, y_new)
+  private$.alpha <- res[[1]]
+  private$.logp <- matrix(res[[2]], 1, 1)
+  private$.L <- NULL
+}
+
 # body of GPC$initialize (R/GPCclass.R:73-103), native branch
 .gpc_initialize_native <- function(private, X, y, k, epsilon) {
   tag <- attr(k, "gprc_kernel")

@@ -112,6 +112,28 @@ SEXP gprc_R_gpr_predict(SEXP handle, SEXP X_star, SEXP pointwise) {
   return res;
 }
 
+/* GPR$add_data: the model becomes GPR$new(cbind(X, X_new), c(y, y_new), noise = $noise, k) without a refit.  Returns
+ * list(alpha, logp) of the extended model; on a non-PD extension the model is unchanged and R gets chol()'s error. */
+SEXP gprc_R_gpr_extend(SEXP handle, SEXP X_new, SEXP y_new) {
+  gprc_model* m = model_of(handle);
+  int64_t n = 0, d = 0;
+  gprc_model_dims(m, &n, &d);
+  const int64_t mnew = Rf_ncols(X_new);
+  if (Rf_nrows(X_new) != d || LENGTH(y_new) != mnew) Rf_error("gprc: X_new must have nrow(X) rows and length(y_new) == ncol(X_new)");
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+  SEXP alpha = Rf_allocVector(REALSXP, (R_xlen_t)(n + mnew));
+  SET_VECTOR_ELT(res, 0, alpha);
+  SEXP s_logp = Rf_allocVector(REALSXP, 1);
+  SET_VECTOR_ELT(res, 1, s_logp);
+  int rc = gprc_gpr_extend(m, REAL(X_new), mnew, REAL(y_new));
+  if (rc == 0) rc = gprc_gpr_get_alpha(m, REAL(alpha));
+  if (rc == 0) rc = gprc_gpr_get_logp(m, REAL(s_logp));
+  UNPROTECT(1);
+  if (rc > 0) Rf_error("the leading minor of order %d is not positive definite", rc);
+  if (rc != 0) Rf_error("gprc: %s", gprc_last_error());
+  return res;
+}
+
 /* ---- multi-GPU from R's one process: options(gprc.devices = c(0, 1, ..., 7)) selects it (native.R) ------------------
  * One gprc_mgpu per distinct (devices, flags) request, ALL kept until the package is unloaded: creating the streams / RCCL
  * communicators is not free, and GPR objects fitted earlier hold gprc_mgpu_model handles into theirs -- destroying a
@@ -318,6 +340,7 @@ static const R_CallMethodDef call_methods[] = {
     {"gprc_R_kernel_matrix", (DL_FUNC)&gprc_R_kernel_matrix, 4},
     {"gprc_R_gpr_fit", (DL_FUNC)&gprc_R_gpr_fit, 5},
     {"gprc_R_gpr_predict", (DL_FUNC)&gprc_R_gpr_predict, 3},
+    {"gprc_R_gpr_extend", (DL_FUNC)&gprc_R_gpr_extend, 3},
     {"gprc_R_model_L", (DL_FUNC)&gprc_R_model_L, 1},
     {"gprc_R_gpc_fit", (DL_FUNC)&gprc_R_gpc_fit, 5},
     {"gprc_R_gpc_predict_latent", (DL_FUNC)&gprc_R_gpc_predict_latent, 2},

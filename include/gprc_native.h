@@ -141,6 +141,15 @@ GPRC_API int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, 
  * pointwise == 0: mean_out[n_star], var_out = n_star x n_star K(X*,X*) - t(v) %*% v (:167-168) */
 GPRC_API int gprc_gpr_predict(gprc_model* model, const double* X_star, int64_t n_star, int pointwise, double* mean_out,
                      double* var_out);
+/* Append m observations (X_new: d x m, y_new: m) to a fitted GPR model in place of GPR$new on
+ * cbind(X, X_new), c(y, y_new) with the model's kernel, parameters and stored $noise (jitter kept, never re-tried).
+ * Only the factor's columns behind the last panel boundary n0 = floor(n / 512) 512 are recomputed: the new rows of the
+ * kept columns by a triangular solve with the old factor (m n0^2 flop), the trailing block by the ordinary factorisation.
+ * The result is built in new buffers: peak device memory is the old model plus the extended one.  X_new, y_new may be
+ * host or device pointers.
+ * Returns 0; info > 0 (global 1-based column, model unchanged) when the extended matrix is not PD;
+ * GPRC_ERR_ARG for m < 1, null pointers, a GPC model, or a borrowed model (gprc_gpr_model_from_device, gprc_mgpu_model_rank). */
+GPRC_API int gprc_gpr_extend(gprc_model* model, const double* X_new, int64_t m, const double* y_new);
 /* active bindings (R/GPRclass.R:230-280).  get_L materialises the n x n lower factor (upper = 0,
  * as t(chol(.)) has it) -- lazily, only when asked: it is 32 GiB at n = 65536. */
 GPRC_API int gprc_model_dims(const gprc_model* model, int64_t* n_out, int64_t* d_out);
