@@ -8,15 +8,15 @@ CPU fallback: without the built library / an MI355X the compute calls raise.
 from . import _native
 from ._native import GprcError, NotPositiveDefinite, Context, default_context, device_count
 from .covfunc import (cov_func, covariance_matrix, constant, linear, polynomial, sqrexp, gammaexp,
-                      rationalquadratic, CovFunc)
+                      rationalquadratic, sqrexp_ard, CovFunc)
 from .gpr import (GPR, GPR_constant, GPR_linear, GPR_polynomial, GPR_sqrexp, GPR_gammaexp,
-                  GPR_rationalquadratic)
+                  GPR_rationalquadratic, GPR_sqrexp_ard)
 from .gpc import GPC
-from .fit import fit, dens, dens_deriv
+from .fit import fit, dens, dens_deriv, logp_grad, optimize
 from .sampling import multivariate_normal, expand_range, mvn_factor, sym_eigen
 from .simulation import combine_all, iid_noise, simulate_regression, simulate_regression_gp, simulate_classification
 
-__all__ = ["fit", "dens", "dens_deriv", "multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "combine_all", "iid_noise",
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "sqrexp_ard", "GPR_sqrexp_ard", "multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "combine_all", "iid_noise",
            "simulate_regression", "simulate_regression_gp", "simulate_classification", "GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp",
            "GPR_rationalquadratic", "GPC", "cov_func", "covariance_matrix", "constant", "linear", "polynomial",
            "sqrexp", "gammaexp", "rationalquadratic", "CovFunc", "GprcError", "NotPositiveDefinite", "Context",

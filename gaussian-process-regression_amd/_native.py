@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgprc_native" + os.environ.get("GPRC_LIB_SUFFIX", "") + ".so")
 
 # kernel ids (include/gprc_native.h gprc_kernel_id)
-CONSTANT, LINEAR, POLYNOMIAL, SQREXP, GAMMAEXP, RATQUAD = range(6)
+CONSTANT, LINEAR, POLYNOMIAL, SQREXP, GAMMAEXP, RATQUAD, SQREXP_ARD = range(7)
 
 OK = 0
 GPC_REFERENCE_STOP = 1
@@ -60,6 +60,7 @@ PROTOTYPES = {
                                      C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "gprc_gpr_log_marginal": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.POINTER(C.c_double)]),
     "gprc_fit_gradient": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, _dp]),
+    "gprc_gpr_logp_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.POINTER(C.c_double), _dp]),
     "gprc_gpr_predict": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp]),
     "gprc_gpr_extend": (C.c_int, [_vp, _vp, _i64, _vp]),
     "gprc_model_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -198,7 +199,8 @@ def device_count() -> int:
 
 INFO_WAIT_TIMEOUT = -99   # include/gprc_native.h: a device-side dependency wait ran out
 PROF_KINDS = ["fill", "potf2_inv", "trsm_panel", "gemm_inner_k128", "trailing_update", "solve_update_k512", "trsv",
-              "row_reduce", "cov_syrk", "deriv_rowsum", "jacobi_sweep", "solve_left", "trailing_left", "panel_fused", "solve_panel"]
+              "row_reduce", "cov_syrk", "deriv_rowsum", "jacobi_sweep", "solve_left", "trailing_left", "panel_fused", "solve_panel",
+              "inverse_gemm", "grad_contract"]
 
 
 def prof_summary():

@@ -1,6 +1,7 @@
 """Covariance-function layer: the reference's operator API (R/GPRclass.R:353-357, 378-403, 424-427).
 
-`cov_func(func, ...)` fixes the parameters of one of the six kernel generics and returns a callable
+`cov_func(func, ...)` fixes the parameters of one of the six kernel generics (or of `sqrexp_ard`, the squared
+exponential with one length scale per input dimension, which the reference does not have) and returns a callable
 `k(x, y)` obeying the reference's closure contract (two d x m matrices -> the m kernel values of their
 columns).  The returned closure carries `gprc_kernel = (id, params)`, which is what routes
 `covariance_matrix`, `GPR` and `GPC` to the fused HIP fill kernel.  Arbitrary user closures are part of
@@ -14,7 +15,7 @@ import numpy as np
 from . import _native as nat
 
 __all__ = ["cov_func", "covariance_matrix", "constant", "linear", "polynomial", "sqrexp", "gammaexp",
-           "rationalquadratic", "CovFunc", "KernelGeneric", "as_points"]
+           "rationalquadratic", "sqrexp_ard", "CovFunc", "KernelGeneric", "as_points"]
 
 
 def as_points(X, d=None, what="X"):
@@ -80,6 +81,8 @@ polynomial = KernelGeneric("polynomial", nat.POLYNOMIAL, ("sigma", "p"))
 sqrexp = KernelGeneric("sqrexp", nat.SQREXP, ("l",))
 gammaexp = KernelGeneric("gammaexp", nat.GAMMAEXP, ("l", "gamma"))
 rationalquadratic = KernelGeneric("rationalquadratic", nat.RATQUAD, ("l", "alpha"))
+# automatic relevance determination: exp(-1/2 sum_k ((x_k - y_k) / l_k)^2), l of length nrow(X) (no reference counterpart)
+sqrexp_ard = KernelGeneric("sqrexp_ard", nat.SQREXP_ARD, ("l",))
 
 
 class CovFunc:
@@ -89,12 +92,16 @@ class CovFunc:
         self.func = func
         self.values = dict(values)
         self.params = func.param_vector(values)
+        if func.kernel_id == nat.SQREXP_ARD and not (self.params.size >= 1 and np.all(np.isfinite(self.params)) and np.all(self.params > 0)):
+            raise ValueError("all(is.finite(l)), all(l > 0) are not all TRUE")
         self.gprc_kernel = (func.kernel_id, self.params)
 
     def native_params(self, d):
-        """Parameter vector checked against the input dimension (linear: sigma of length 1 or d)."""
+        """Parameter vector checked against the input dimension (linear: sigma of length 1 or d; sqrexp_ard: l of length d)."""
         if self.func.kernel_id == nat.LINEAR and self.params.size not in (1, d):
             raise ValueError("length(sigma) == nrow(X) is not TRUE")
+        if self.func.kernel_id == nat.SQREXP_ARD and self.params.size != d:
+            raise ValueError("length(l) == nrow(X) is not TRUE")
         return self.params
 
     def __call__(self, x, y, ctx=None):
@@ -124,7 +131,7 @@ def cov_func(func, *args, **kwargs):
     """cov_func(func, ...) (R/GPRclass.R:424-427): a covariance function with fixed parameters."""
     if not isinstance(func, KernelGeneric):
         raise TypeError("cov_func: `func` must be one of constant, linear, polynomial, sqrexp, gammaexp, "
-                        "rationalquadratic on the MI355X path (arbitrary R closures stay on the reference's R path)")
+                        "rationalquadratic, sqrexp_ard on the MI355X path (arbitrary R closures stay on the reference's R path)")
     return CovFunc(func, func.bind(args, kwargs))
 
 

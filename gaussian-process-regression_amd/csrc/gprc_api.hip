@@ -272,6 +272,12 @@ int make_spec(int kernel, const double* params, int n_params, int64_t d, KernelS
     case GPRC_LINEAR: ok = n_params == 1 || n_params == d; break;
     case GPRC_POLYNOMIAL: case GPRC_GAMMAEXP: case GPRC_RATQUAD: ok = n_params == 2; break;
     case GPRC_SQREXP: ok = n_params == 1; break;
+    case GPRC_SQREXP_ARD:
+      if (n_params != d) { set_error("sqrexp_ard: one length scale per input dimension (n_params == d <= 256)"); return GPRC_ERR_ARG; }
+      for (int i = 0; i < n_params; ++i)
+        if (!(params[i] > 0.0) || !std::isfinite(params[i])) { set_error("sqrexp_ard: every length scale must be finite and > 0"); return GPRC_ERR_ARG; }
+      ok = true;
+      break;
     default: set_error("unknown kernel id"); return GPRC_ERR_ARG;
   }
   if (!ok) { set_error("wrong number of kernel parameters for this kernel"); return GPRC_ERR_ARG; }
@@ -1078,6 +1084,68 @@ int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, int n_par
     for (int64_t r = 0; r < n; ++r) acc += (long double)(ha[r] * ha[r] - hk[r]) * (long double)hs[(int64_t)i * n + r];
     grad_out[i] = (double)(0.5L * acc);
   }
+  return 0;
+}
+
+// logp and its exact gradient ("Exact gradient and ARD"):
+//   fit                    L, alpha, logp                                     as gprc_gpr_log_marginal          n^3 / 3
+//   V^T = I L^-T           the identity through the predict's solve, triangular form (as gprc_fit_gradient)     n^3 / 3
+//   W = -V^T V = -K_y^-1   lower triangle; row tile r of V^T is zero left of column 128 r: its products start there     n^3 / 3
+//   contraction            one pass over W with K, dK / dtheta recomputed from X (kernels_grad.hip); host: sum of the partials
+int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                       const double* y, double noise, double* logp_out, double* grad_out) {
+  if (!logp_out || !grad_out) { set_error("logp_grad: null output"); return GPRC_ERR_ARG; }
+  if (kernel != GPRC_SQREXP && kernel != GPRC_GAMMAEXP && kernel != GPRC_RATQUAD && kernel != GPRC_SQREXP_ARD) {
+    set_error("logp_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard");
+    return GPRC_ERR_ARG;
+  }
+  gprc_model* m = nullptr;
+  GPRC_TRY(gpr_prepare(ctx, kernel, params, n_params, X, d, n, y, noise, &m));
+  struct Guard { gprc_model* m; ~Guard() { free_model(m); } } guard{m};
+  int info = 0;
+  GPRC_TRY(gpr_attempt(m, noise, &info));
+  if (info != 0) { set_error("the leading minor of order " + std::to_string(info) + " is not positive definite"); return info; }
+  hipStream_t s = ctx->stream;
+  const int64_t n_pad = m->n_pad;
+  double *vt = nullptr, *W = nullptr;
+  int rc = ws_get(ctx, 0, n_pad * n_pad, &vt);
+  if (rc == 0) rc = ws_get(ctx, 3, n_pad * n_pad, &W);
+  if (rc == GPRC_ERR_NOMEM) {
+    set_error("logp_grad: L^-1 and (K + noise I)^-1 are held whole, 2 x " + std::to_string(n_pad) + "^2 doubles (" +
+              std::to_string((2 * n_pad * n_pad * (int64_t)sizeof(double)) >> 20) + " MiB) of device memory, which could not be allocated");
+    return GPRC_ERR_NOMEM;
+  }
+  GPRC_TRY(rc);
+  GPRC_TRY(launch_set_identity_rows(s, vt, n_pad, n_pad, n_pad, 0));
+  GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, n_pad, n_pad, nullptr, 0));   // vt = L^-T (upper triangular)
+  GPRC_HIP(hipMemsetAsync(W, 0, sizeof(double) * (size_t)(n_pad * n_pad), s));
+  GPRC_TRY(launch_gemm_nt(s, W, n_pad, vt, n_pad, vt, n_pad, n_pad, n_pad, n_pad, 1, PK_INV_GEMM));
+  const int64_t rows = grad_partial_rows(), np1 = n_params + 1;
+  DevMem part;
+  GPRC_TRY(part.alloc(rows * np1));
+  GPRC_TRY(launch_grad_contract(s, m->ks, m->X, d, n, m->alpha, W, n_pad, part.p));
+  std::vector<double> hp((size_t)(rows * np1));
+  GPRC_HIP(hipMemcpyAsync(hp.data(), part.p, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  std::vector<long double> acc((size_t)np1, 0.0L);
+  for (int64_t g = 0; g < rows; ++g)
+    for (int64_t k = 0; k < np1; ++k) acc[(size_t)k] += (long double)hp[(size_t)(g * np1 + k)];
+  const double p0 = params[0], p1 = n_params > 1 ? params[1] : 0.0;
+  switch (kernel) {   // the factors that do not depend on (i, j): kernels_grad.hip
+    case GPRC_SQREXP: grad_out[0] = (double)(0.5L * acc[0] / ((long double)p0 * p0 * p0)); break;
+    case GPRC_GAMMAEXP:
+      grad_out[0] = (double)(0.5L * acc[0] * (long double)p1 / (long double)p0);
+      grad_out[1] = (double)(-0.25L * acc[1]);
+      break;
+    case GPRC_RATQUAD:
+      grad_out[0] = (double)(0.5L * acc[0] / ((long double)p0 * p0 * p0));
+      grad_out[1] = (double)(0.5L * acc[1]);
+      break;
+    default:
+      for (int k = 0; k < n_params; ++k) grad_out[k] = (double)(0.5L * acc[(size_t)k] / (long double)params[k]);
+  }
+  grad_out[n_params] = (double)(0.5L * acc[(size_t)n_params]);
+  *logp_out = m->logp;
   return 0;
 }
 

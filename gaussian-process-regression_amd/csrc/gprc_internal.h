@@ -45,7 +45,7 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 // ---- in-library event profiler (bench.py's live roofline numbers) ---------------------------------
 enum ProfKind { PK_FILL = 0, PK_POTF2 = 1, PK_TRSM_PANEL = 2, PK_GEMM_INNER = 3, PK_TRAILING = 4, PK_SOLVE_UPDATE = 5,
-                PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_COUNT = 15 };
+                PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_INV_GEMM = 15, PK_GRAD_CONTRACT = 16, PK_COUNT = 17 };
 bool prof_enabled();
 void prof_begin(hipStream_t s, int kind);
 void prof_end(hipStream_t s, int kind, double flops, double bytes);
@@ -83,6 +83,15 @@ int launch_fill_cross_fused(hipStream_t s, const KernelSpec& ks, const double* X
 int launch_deriv_rowsum(hipStream_t s, int kernel, double v0, double v1, const double* X, int64_t d, int64_t n, double* S);
 int launch_set_identity_rows(hipStream_t s, double* vt, int64_t ld, int64_t rows, int64_t cols, int64_t row0);  // vt[i,j] = (row0+i == j)
 
+// ---- launchers (kernels_grad.hip) --------------------------------------------------------------
+// the exact gradient's contraction: one pass over the stored lower triangle of W = -(K + noise I)^-1 (n_pad x n_pad, ld), K and dK/dtheta
+// recomputed from X.  part: grad_partial_rows() x (ks.n_params + 1) doubles, row g = what workgroup g summed over its tiles of
+//   sum_ij (alpha_i alpha_j + W_ij) dK_ij / dtheta_k   (ARD: times l_k, the host divides)   and, last, of sum_i (alpha_i^2 + W_ii);
+// the caller sums the rows in order and halves.  Kernels: sqrexp, gammaexp, rationalquadratic, sqrexp_ard.
+int64_t grad_partial_rows();
+int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* alpha, const double* W,
+                         int64_t ld, double* part);
+
 // ---- launchers (kernels_chol.hip) --------------------------------------------------------------
 // factor the 128x128 diagonal block at A (ld) in LDS, write L in place and its inverse to winv
 int launch_potf2_inv(hipStream_t s, double* A, int64_t lda, double* winv, int* info_dev, int col0);
@@ -95,6 +104,7 @@ int launch_solve_panel_fused(hipStream_t s, double* vt, int64_t ldv, int64_t m_p
 // X[M x 128] := X * W^T for lower-triangular 128x128 W (= inverse of a diagonal block of L)
 int launch_trsm_panel(hipStream_t s, double* X, int64_t ldx, int64_t M, const double* winv, double* ssq = nullptr);
 // C[M x N] -= A[M x K] * B[N x K]^T; lower_diag >= 0: row tile r / col tile c with r + lower_diag < c is skipped
+// kind PK_INV_GEMM (square, lower, A and B upper triangular): the tile of row tile r starts its products at column r 128
 int launch_gemm_nt(hipStream_t s, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
                    int64_t M, int64_t N, int64_t K, int lower, int kind);
 // trailing update of packed panels q_begin, q_begin+q_stride, ... < q_end with factored panel p

@@ -864,14 +864,18 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(double* C, int64_t ldc,
   const unsigned ntiles = (unsigned)tiles_m * (unsigned)tiles_n;
   const int width = group * tiles_n;
   for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const unsigned id = xcd_remap(t, ntiles);
+    // (PK_INV_GEMM: a tile's length falls with its row, so the ids stay round-robin over the XCDs -- every XCD the same mix, as solve_left_kernel)
+    const unsigned id = ROLE == PK_INV_GEMM ? t : xcd_remap(t, ntiles);
     const int g = id / width, first_m = g * group;
     const int gsize = (tiles_m - first_m < group) ? (tiles_m - first_m) : group;
     const int tr = first_m + (int)(id % width) % gsize;
     const int tc = (int)(id % width) / gsize;
     if (lower && tc > tr) continue;
-    gemm_tile_128<false>(C + (int64_t)tr * 128 + (int64_t)tc * 128 * ldc, ldc, A + (int64_t)tr * 128, lda,
-                         B + (int64_t)tc * 128, ldb, K, smem);
+    // PK_INV_GEMM (K_y^-1 = L^-T L^-1, A = B = L^-T, lower tiles): rows tr 128.. of an UPPER-triangular matrix are zero left of
+    // column tr 128 >= tc 128, so the products start there -- n^3 / 3 instead of n^3; what is skipped is exact zeros
+    const int64_t k0 = ROLE == PK_INV_GEMM ? (int64_t)tr * 128 : 0;
+    gemm_tile_128<false>(C + (int64_t)tr * 128 + (int64_t)tc * 128 * ldc, ldc, A + (int64_t)tr * 128 + k0 * lda, lda,
+                         B + (int64_t)tc * 128 + k0 * ldb, ldb, K - (int)k0, smem);
     __syncthreads();  // every wave has left the tile (LDS reads done) before the next tile's first DMA lands
   }
 }
@@ -2452,6 +2456,7 @@ static int ensure_gemm_attrs() {
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_GEMM_INNER>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_SOLVE_UPDATE>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_COV_SYRK>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_INV_GEMM>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trsm_panel_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trsm_panel_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_panel_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
@@ -2548,8 +2553,9 @@ int launch_gemm_nt(hipStream_t s, double* C, int64_t ldc, const double* A, int64
   GPRC_TRY(ensure_gemm_attrs());
   const int64_t tiles = (M / 128) * (N / 128);
   if (tiles > 0x7fffffff) { set_error("gemm_nt: too many tiles"); return GPRC_ERR_ARG; }
-  const double useful = lower ? 0.5 : 1.0;  // algorithmic: the lower triangle only
-  ProfScope ps(s, kind, 2.0 * M * N * K * useful, 8.0 * (2.0 * M * N * useful + (M + N) * (double)K));
+  if (kind == PK_INV_GEMM && !(lower && M == N && K == M)) { set_error("gemm_nt: the triangular inverse product is square and lower"); return GPRC_ERR_ARG; }
+  const double useful = kind == PK_INV_GEMM ? 1.0 / 6.0 : lower ? 0.5 : 1.0;  // algorithmic: the lower triangle only (inverse product: from the diagonal on)
+  ProfScope ps(s, kind, 2.0 * M * N * K * useful, 8.0 * (2.0 * M * N * (lower ? 0.5 : 1.0) + (M + N) * (double)K));
   constexpr int pg = 0;   // (a persistent grid of N workgroups striding over the tile list measured 4 % slower: DESIGN.md 3)
   const dim3 grid((unsigned)((pg > 0 && tiles > pg) ? pg : tiles)), block(256);
   const size_t smem = G_SMEM_DOUBLES * sizeof(double);
@@ -2557,6 +2563,7 @@ int launch_gemm_nt(hipStream_t s, double* C, int64_t ldc, const double* A, int64
   constexpr int group = 8;  // 8 x 8 concurrent tiles per XCD share 16 strips; 4..32 measured within 0.5 %
   if (kind == PK_SOLVE_UPDATE) hipLaunchKernelGGL((gemm_nt_kernel<PK_SOLVE_UPDATE>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
   else if (kind == PK_COV_SYRK) hipLaunchKernelGGL((gemm_nt_kernel<PK_COV_SYRK>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
+  else if (kind == PK_INV_GEMM) hipLaunchKernelGGL((gemm_nt_kernel<PK_INV_GEMM>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
   else hipLaunchKernelGGL((gemm_nt_kernel<PK_GEMM_INNER>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
   GPRC_LAUNCH_CHECK();
   return 0;

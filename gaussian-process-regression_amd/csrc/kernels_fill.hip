@@ -49,6 +49,10 @@ __device__ __forceinline__ double accum(double s, double a, double b, double sig
   if constexpr (KID == GPRC_LINEAR) return fma(sig * a, b, s);  // colSums(sigma * x * y)
   else if constexpr (KID == GPRC_POLYNOMIAL) return fma(a, b, s);  // colSums(x * y)
   else if constexpr (KID == GPRC_CONSTANT) return s;
+  else if constexpr (KID == GPRC_SQREXP_ARD) {
+    double t = (a - b) * sig;  // colSums(((x - y) / l)^2): sig = 1 / l_k (make_fill_spec)
+    return fma(t, t, s);
+  }
   else {
     double t = a - b;  // colSums((x - y)^2)
     return fma(t, t, s);
@@ -86,6 +90,7 @@ __device__ __forceinline__ double finish(double s, const KernelSpec& ks) {
     q = fma(fma(-q, c, s), rc, q);
     return exp(-q);
   }
+  else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);  // s is already the scaled distance: sqrexp with l = 1
   else if constexpr (KID == GPRC_GAMMAEXP) {
     // exp(-(sqrt(s) / l)^gamma).  gamma == 2 is R's x^2 = x * x (R_pow); any other gamma > 0 went through libm pow -- a special-case ladder and
     // an extended-precision log / exp, ~3x the work of a plain log and exp: the gamma-exponential fill ran at 0.8 TB/s against 3.5 for sqexp.
@@ -178,7 +183,7 @@ __global__ __launch_bounds__(256) void fill_kernel(FillArgs a) {
       int64_t gj = tj + j;
       Bs[j][r] = (gj < a.nB) ? a.B[gj * a.d + r0 + r] : 0.0;
     }
-    if (t < dc) Sg[t] = (KID == GPRC_LINEAR) ? (a.ks.n_params == 1 ? a.ks.p[0] : a.ks.p[r0 + t]) : 1.0;
+    if (t < dc) Sg[t] = (KID == GPRC_LINEAR) ? (a.ks.n_params == 1 ? a.ks.p[0] : a.ks.p[r0 + t]) : (KID == GPRC_SQREXP_ARD) ? a.ks.p[r0 + t] : 1.0;
     __syncthreads();
     for (int r = 0; r < dc; ++r) {
       const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
@@ -257,15 +262,17 @@ __global__ __launch_bounds__(256) void colwise_kernel(KernelSpec ks, const doubl
   if (c >= m) return;
   double s = 0.0;
   for (int64_t r = 0; r < d; ++r) {
-    double sg = (KID == GPRC_LINEAR) ? (ks.n_params == 1 ? ks.p[0] : ks.p[r]) : 1.0;
+    double sg = (KID == GPRC_LINEAR) ? (ks.n_params == 1 ? ks.p[0] : ks.p[r]) : (KID == GPRC_SQREXP_ARD) ? ks.p[r] : 1.0;
     s = accum<KID>(s, x[c * d + r], y[c * d + r], sg);
   }
   out[c] = finish<KID>(s, ks);
 }
 
-// device-side copy of the spec with derived constants (sqexp: p[1] = 2 l^2, p[2] = 1 / (2 l^2))
+// device-side copy of the spec with derived constants (sqexp: p[1] = 2 l^2, p[2] = 1 / (2 l^2); ARD: p[k] = 1 / l_k)
 KernelSpec make_fill_spec(const KernelSpec& ks) {
   KernelSpec d = ks;
+  if (ks.id == GPRC_SQREXP_ARD)
+    for (int k = 0; k < ks.n_params; ++k) d.p[k] = 1.0 / ks.p[k];
   if (ks.id == GPRC_SQREXP) {
     d.p[1] = 2.0 * (ks.p[0] * ks.p[0]);
     d.p[2] = 1.0 / d.p[1];
@@ -387,6 +394,7 @@ static int fill_dispatch(hipStream_t s, const FillArgs& a) {
     case GPRC_SQREXP: return do_fill<GPRC_SQREXP>(s, a);
     case GPRC_GAMMAEXP: return do_fill<GPRC_GAMMAEXP>(s, a);
     case GPRC_RATQUAD: return do_fill<GPRC_RATQUAD>(s, a);
+    case GPRC_SQREXP_ARD: return do_fill<GPRC_SQREXP_ARD>(s, a);
     default: set_error("unknown kernel id"); return GPRC_ERR_ARG;
   }
 }
@@ -427,6 +435,7 @@ int launch_colwise(hipStream_t s, const KernelSpec& ks, const double* x, const d
     case GPRC_SQREXP: hipLaunchKernelGGL((colwise_kernel<GPRC_SQREXP>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
     case GPRC_GAMMAEXP: hipLaunchKernelGGL((colwise_kernel<GPRC_GAMMAEXP>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
     case GPRC_RATQUAD: hipLaunchKernelGGL((colwise_kernel<GPRC_RATQUAD>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
+    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((colwise_kernel<GPRC_SQREXP_ARD>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
     default: set_error("unknown kernel id"); return GPRC_ERR_ARG;
   }
   GPRC_LAUNCH_CHECK();

@@ -1,0 +1,238 @@
+// kernels_grad.hip -- the contraction of the exact marginal-likelihood gradient for gfx950 (gprc_gpr_logp_grad).
+//
+//   d logp / d theta = 1/2 sum_ij M_ij dK_ij / d theta,     M = alpha alpha^T - K_y^-1,  K_y = K + noise I
+//
+// K_y^-1 arrives as W = -K_y^-1 (the inverse GEMM subtracts from a zeroed matrix), lower triangle stored.  One pass reads that
+// triangle -- 8 B per element, 16 B per lane, 1 KiB contiguous per wave and column, the only HBM traffic -- in the fill's tile
+// shape (128 x 64, two rows x 16 columns per lane); K_ij and dK_ij / d theta are recomputed from X through LDS exactly as the fill
+// forms them, so no derivative array and no second kernel matrix exists.  Off-diagonal entries count twice (symmetry), entries
+// above the diagonal or in the padding not at all; the diagonal also carries d / d noise = 1/2 sum_i M_ii.
+//
+// What the device leaves per parameter is the sum WITHOUT the factors that do not depend on (i, j); the host applies them:
+//   sqrexp        sum M K s                     (x 1 / l^3)                  s = |x - y|^2
+//   gammaexp      sum M K u, sum M K u L        (x gamma / l, x -1/2)        u = (s / l^2)^(gamma / 2), L = log(s / l^2); 0 at s = 0
+//   ratquad       sum M K s / q, sum M K (x / q - log q)   (x 1 / l^3, x 1)  x = s / (2 alpha l^2), q = 1 + x
+//   sqrexp_ard    sum M K t_k^2  per k          (x 1 / l_k)                  t_k = (x_k - y_k) / l_k
+// For ARD a lane keeps M K of its 32 elements in registers and passes over the coordinates a second time, 16 at a time: the d sums
+// never live in registers at once (d <= 256), and nothing of size n x d is formed.
+//
+// Order of summation is fixed: a lane's elements in column order, the 64 lanes by a shuffle tree, the four waves in wave order, a
+// workgroup's tiles in tile order (a fixed grid strides over the tile list), the workgroups by the host in long double.  No atomics:
+// two calls on the same input give the same bits.
+#include "gprc_internal.h"
+
+#include <algorithm>
+
+namespace gprc {
+
+namespace {
+
+constexpr int GT_R = 128;      // tile rows: 2 consecutive rows per lane x 64 lanes
+constexpr int GT_C = 64;       // tile cols: 16 per wave x 4 waves
+constexpr int GD = 16;         // coordinates staged per pass
+constexpr int GRAD_WGS = 1024; // workgroups of the launch = rows of the partial buffer (a constant: the order of summation does not depend on the device)
+
+struct GradArgs {
+  const double* X;
+  const double* alpha;
+  const double* W;
+  double* part;
+  int64_t n, d, ld;
+  int64_t ntiles;
+  KernelSpec ks;   // derived constants, see make_grad_spec
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;  // lane 0 holds the sum
+}
+
+template <int KID>
+__global__ __launch_bounds__(256) void grad_contract_kernel(GradArgs a) {
+  __shared__ __attribute__((aligned(16))) double As[GD][GT_R];
+  __shared__ double Bs[GT_C][GD + 1];
+  __shared__ double Al[GT_C];
+  __shared__ double red[4][GD + 1];
+  __shared__ double gacc[MAX_PARAMS + 1];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int np = KID == GPRC_SQREXP_ARD ? (int)a.d : (KID == GPRC_SQREXP ? 1 : 2);
+  for (int k = t; k <= np; k += 256) gacc[k] = 0.0;
+  double a0 = 0.0, a1 = 0.0, nz = 0.0;  // isotropic kernels: this lane's sums over all its tiles; nz: the diagonal's M_ii
+
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    // row tile bi holds the column tiles 0 .. 2 bi + 1 (everything that touches the lower triangle): tiles before it = bi (bi + 1)
+    int64_t bi = (int64_t)((sqrt(4.0 * (double)tile + 1.0) - 1.0) * 0.5);
+    while ((bi + 1) * (bi + 2) <= tile) ++bi;
+    while (bi * (bi + 1) > tile) --bi;
+    const int64_t bj = tile - bi * (bi + 1);
+    const int64_t ti = bi * GT_R, tj = bj * GT_C;
+
+    auto stage = [&](int64_t r0, int dc) {  // coordinates r0 .. r0 + dc - 1 of the tile's points (ARD: divided by their length scale)
+      __syncthreads();
+      for (int e = t; e < GT_R * dc; e += 256) {
+        const int i = e / dc, r = e - i * dc;
+        const int64_t gi = ti + i;
+        double v = (gi < a.n) ? a.X[gi * a.d + r0 + r] : 0.0;
+        if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
+        As[r][i] = v;
+      }
+      for (int e = t; e < GT_C * dc; e += 256) {
+        const int j = e / dc, r = e - j * dc;
+        const int64_t gj = tj + j;
+        double v = (gj < a.n) ? a.X[gj * a.d + r0 + r] : 0.0;
+        if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
+        Bs[j][r] = v;
+      }
+      if (r0 == 0 && t < GT_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
+      __syncthreads();
+    };
+
+    double s0[16], s1[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) { s0[c] = 0.0; s1[c] = 0.0; }
+    for (int64_t r0 = 0; r0 < a.d; r0 += GD) {
+      const int dc = (int)((a.d - r0 < GD) ? (a.d - r0) : GD);
+      stage(r0, dc);
+      for (int r = 0; r < dc; ++r) {
+        const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+          const double b = Bs[wave * 16 + c][r];
+          const double t0 = av.x - b, t1 = av.y - b;
+          s0[c] = fma(t0, t0, s0[c]);
+          s1[c] = fma(t1, t1, s1[c]);
+        }
+      }
+    }
+
+    const int64_t gi0 = ti + 2 * lane;
+    const double al0 = (gi0 < a.n) ? a.alpha[gi0] : 0.0, al1 = (gi0 + 1 < a.n) ? a.alpha[gi0 + 1] : 0.0;
+    // rows < 128 ceil(n / 128) <= n_pad and columns <= 64 (2 bi + 1) + 63 < 128 (bi + 1): every load is inside the n_pad x n_pad matrix
+    const double* wp = a.W + gi0 + (tj + wave * 16) * a.ld;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const int64_t gj = tj + wave * 16 + c;
+      const double2 w = *reinterpret_cast<const double2*>(wp + c * a.ld);
+      const double alj = Al[wave * 16 + c];
+      double m0 = fma(al0, alj, w.x), m1 = fma(al1, alj, w.y);
+      const bool jin = gj < a.n;
+      if (jin && gi0 == gj) nz += m0;
+      if (jin && gi0 + 1 == gj) nz += m1;
+      m0 = (jin && gi0 < a.n && gi0 > gj) ? 2.0 * m0 : 0.0;          // the diagonal's dK / d theta is zero for all four kernels
+      m1 = (jin && gi0 + 1 < a.n && gi0 + 1 > gj) ? 2.0 * m1 : 0.0;
+      if constexpr (KID == GPRC_SQREXP) {
+        const double h = a.ks.p[1];  // 1 / (2 l^2)
+        a0 = fma(m0 * exp(-s0[c] * h), s0[c], a0);
+        a0 = fma(m1 * exp(-s1[c] * h), s1[c], a0);
+      } else if constexpr (KID == GPRC_SQREXP_ARD) {
+        s0[c] = m0 * exp(-0.5 * s0[c]);  // M K, kept for the second pass
+        s1[c] = m1 * exp(-0.5 * s1[c]);
+      } else if constexpr (KID == GPRC_GAMMAEXP) {
+        const double rl2 = a.ks.p[2], hg = a.ks.p[3];  // 1 / l^2, gamma / 2
+        if (s0[c] > 0.0) {
+          const double lg = log(s0[c] * rl2), u = exp(hg * lg), ku = m0 * exp(-u) * u;
+          a0 += ku;
+          a1 = fma(ku, lg, a1);
+        }
+        if (s1[c] > 0.0) {
+          const double lg = log(s1[c] * rl2), u = exp(hg * lg), ku = m1 * exp(-u) * u;
+          a0 += ku;
+          a1 = fma(ku, lg, a1);
+        }
+      } else {  // rationalquadratic
+        const double al = a.ks.p[1], rc = a.ks.p[2];  // alpha, 1 / (2 alpha l^2)
+        {
+          const double x = s0[c] * rc, q = 1.0 + x, lq = log1p(x), k = m0 * exp(-al * lq);
+          a0 = fma(k, s0[c] / q, a0);
+          a1 = fma(k, x / q - lq, a1);
+        }
+        {
+          const double x = s1[c] * rc, q = 1.0 + x, lq = log1p(x), k = m1 * exp(-al * lq);
+          a0 = fma(k, s1[c] / q, a0);
+          a1 = fma(k, x / q - lq, a1);
+        }
+      }
+    }
+
+    if constexpr (KID == GPRC_SQREXP_ARD) {
+      for (int64_t r0 = 0; r0 < a.d; r0 += GD) {
+        const int dc = (int)((a.d - r0 < GD) ? (a.d - r0) : GD);
+        if (a.d > GD) stage(r0, dc);  // (d <= 16: the only chunk is still in LDS)
+        for (int r = 0; r < dc; ++r) {
+          const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
+          double acc = 0.0;
+#pragma unroll
+          for (int c = 0; c < 16; ++c) {
+            const double b = Bs[wave * 16 + c][r];
+            const double t0 = av.x - b, t1 = av.y - b;
+            acc = fma(s0[c], t0 * t0, acc);
+            acc = fma(s1[c], t1 * t1, acc);
+          }
+          acc = wave_sum(acc);
+          if (lane == 0) red[wave][r] = acc;
+        }
+        __syncthreads();
+        if (t < dc) gacc[r0 + t] += (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+        if (a.d <= GD) __syncthreads();  // (otherwise the next stage() separates these reads from the next chunk's writes)
+      }
+    }
+  }
+
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  nz = wave_sum(nz);
+  __syncthreads();
+  if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; red[wave][2] = nz; }
+  __syncthreads();
+  if (t == 0) {
+    if constexpr (KID != GPRC_SQREXP_ARD) {
+      gacc[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+      if (np == 2) gacc[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    }
+    gacc[np] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+  }
+  __syncthreads();
+  for (int k = t; k <= np; k += 256) a.part[(int64_t)blockIdx.x * (np + 1) + k] = gacc[k];
+}
+
+// the spec with the constants the kernel wants (ARD: p[k] = 1 / l_k)
+KernelSpec make_grad_spec(const KernelSpec& ks) {
+  KernelSpec g = ks;
+  if (ks.id == GPRC_SQREXP) g.p[1] = 1.0 / (2.0 * (ks.p[0] * ks.p[0]));
+  if (ks.id == GPRC_GAMMAEXP) { g.p[2] = 1.0 / (ks.p[0] * ks.p[0]); g.p[3] = 0.5 * ks.p[1]; }
+  if (ks.id == GPRC_RATQUAD) g.p[2] = 1.0 / (2.0 * ks.p[1] * (ks.p[0] * ks.p[0]));
+  if (ks.id == GPRC_SQREXP_ARD)
+    for (int k = 0; k < ks.n_params; ++k) g.p[k] = 1.0 / ks.p[k];
+  return g;
+}
+
+}  // namespace
+
+int64_t grad_partial_rows() { return GRAD_WGS; }
+
+int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* alpha, const double* W,
+                         int64_t ld, double* part) {
+  if (n <= 0) return 0;
+  if ((ld & 1) || (reinterpret_cast<uintptr_t>(W) & 15)) { set_error("grad_contract: the inverse must be 16-byte aligned with an even leading dimension"); return GPRC_ERR_ARG; }
+  const int64_t R = (n + GT_R - 1) / GT_R;
+  if (ld < R * GT_R) { set_error("grad_contract: leading dimension smaller than the padded size"); return GPRC_ERR_ARG; }
+  const int np = ks.n_params;
+  GradArgs a{X, alpha, W, part, n, d, ld, R * (R + 1), make_grad_spec(ks)};
+  GPRC_HIP(hipMemsetAsync(part, 0, sizeof(double) * (size_t)(GRAD_WGS * (np + 1)), s));   // rows of workgroups that are not launched
+  const dim3 grid((unsigned)std::min<int64_t>(a.ntiles, GRAD_WGS)), block(256);
+  // bytes: the stored triangle once + X and alpha; flops: the distance (3 d), the kernel and its derivatives (~60), ARD's second pass (4 d)
+  const double elems = 0.5 * (double)n * (double)(n + 1);
+  ProfScope ps(s, PK_GRAD_CONTRACT, elems * (3.0 * d + 60.0 + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)), 8.0 * (elems + (double)n * d + n));
+  switch (ks.id) {
+    case GPRC_SQREXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP>), grid, block, 0, s, a); break;
+    case GPRC_GAMMAEXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_GAMMAEXP>), grid, block, 0, s, a); break;
+    case GPRC_RATQUAD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_RATQUAD>), grid, block, 0, s, a); break;
+    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP_ARD>), grid, block, 0, s, a); break;
+    default: set_error("logp_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
+  }
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace gprc

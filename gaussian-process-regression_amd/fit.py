@@ -17,6 +17,10 @@ What runs where
     kept: gammaexp's gradient has a NaN component (0 * log 0 on the diagonal), vmmin then takes its "uphill" exit at
     once and fit() returns the start values (1, 1); a failing gradient (K not invertible) aborts optim and
     optim_until_error falls back to the best objective value seen so far.
+Beside the reference-faithful fit() stands an EXACT path (no reference counterpart): `logp_grad` is the log marginal
+likelihood and its true gradient in one native call (gprc_gpr_logp_grad: the noisy K_y = K + noise I, a trace, every
+parameter and the noise), and `optimize` maximises it over log(theta) (and log(noise)) with the same vmmin.  It is what
+makes gammaexp / rationalquadratic searches move and what the d length scales of `sqrexp_ard` need.
 Parity status: unpinned (the reference holds no numeric expectations for fit(); tests/testthat/test-fit.R:12-17 only
 checks which kernel NAME wins); cross-checked against scipy's bounded Brent on the same native objective, and the
 BFGS branch against the same driver running on the CPU oracle's objective and gradient.
@@ -30,9 +34,9 @@ import sys
 import numpy as np
 
 from . import _native as nat
-from .covfunc import CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic
+from .covfunc import CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard
 
-__all__ = ["fit", "dens", "dens_deriv", "cov_dict", "brent_fmin", "vmmin"]
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
 cov_dict = {
@@ -48,8 +52,9 @@ SENTINEL = -10000.0  # R/fit.R:50
 
 def dens(X, y, noise, name, v, ctx=None):
     """dens(v) of R/fit.R:117-124 for kernel `name` with parameter vector v (in the generic's argument order).
-    Raises nat.NotPositiveDefinite when K + noise*I is not positive definite (the reference's stopifnot / chol error)."""
-    func = cov_dict[name][0]
+    Raises nat.NotPositiveDefinite when K + noise*I is not positive definite (the reference's stopifnot / chol error).
+    `name` may also be "sqrexp_ard" (v = one length scale per row of X), which is not in cov_dict."""
+    func = cov_dict[name][0] if name in cov_dict else grad_dict[name]
     Xm = as_points(X)
     y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
     d, n = Xm.shape
@@ -74,6 +79,76 @@ def dens_deriv(X, y, name, v, ctx=None):
     nat.check(nat.lib().gprc_fit_gradient(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data,
                                           g.ctypes.data_as(C.POINTER(C.c_double))))
     return g
+
+
+# kernels of the exact gradient: name -> generic (parameter vectors in the ABI's order: {l}, {l, gamma}, {l, alpha}, {l_1..l_d})
+grad_dict = {"sqrexp": sqrexp, "gammaexp": gammaexp, "rationalquadratic": rationalquadratic, "sqrexp_ard": sqrexp_ard}
+
+
+def logp_grad(X, y, noise, name, v, ctx=None):
+    """(logp, grad) of GPR(X, y, noise, name(v)): the log marginal likelihood and its exact gradient, one native call
+    (gprc_gpr_logp_grad).  `v` in the order `dens` takes it; grad has len(v) + 1 entries, d logp / d noise last
+    (noise enters as K + noise * I).  Raises nat.NotPositiveDefinite when K + noise * I is not positive definite."""
+    func = grad_dict[name]
+    Xm = as_points(X)
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    d, n = Xm.shape
+    ctx = ctx or nat.default_context()
+    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    g = np.empty(p.size + 1)
+    out = C.c_double()
+    nat.check(nat.lib().gprc_gpr_logp_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
+                                           C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.value, g
+
+
+def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, value_and_grad=None, ctx=None):
+    """Maximise the log marginal likelihood of kernel `name` ("sqrexp", "gammaexp", "rationalquadratic", "sqrexp_ard")
+    over its parameters, and over the noise when `optimize_noise` and noise > 0, with vmmin on z = log(theta): every
+    parameter stays positive, and d / dz = theta * d / dtheta.  start: parameter vector (default: cov_dict's start values;
+    ones(d) for sqrexp_ard).  value_and_grad(theta, noise) -> (logp, grad) replaces the native objective (grad: len(theta) + 1,
+    noise last).  An evaluation that fails (not positive definite, a parameter over- or underflowing) counts as the sentinel
+    -10000, as in optim_until_error.  Returns dict(par, noise, value, counts, convergence, func): GPR(X, y, r["noise"],
+    r["func"]) is the fitted model; convergence 0: converged, 1: maxit reached (optim's codes)."""
+    func = grad_dict[name]
+    Xm = as_points(X)
+    d = Xm.shape[0]
+    if start is None:
+        start = np.ones(d) if name == "sqrexp_ard" else cov_dict[name][2]
+    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
+    npar = theta0.size
+    with_noise = bool(optimize_noise) and noise > 0
+    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
+        raise ValueError("optimize: start values must be finite and > 0")
+    if value_and_grad is None:
+        ctx = ctx or nat.default_context()
+        value_and_grad = lambda theta, nz: logp_grad(Xm, y, nz, name, theta, ctx)   # noqa: E731
+    z0 = np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0)
+    last = {}   # vmmin asks for the gradient at the point whose value it has just accepted: one evaluation serves both
+
+    def evaluate(z):
+        key = z.tobytes()
+        if last.get("key") != key:
+            with np.errstate(over="ignore"):
+                t = np.exp(z)
+            if not (np.all(np.isfinite(t)) and np.all(t > 0)):
+                raise ArithmeticError("parameter out of range")
+            val, g = value_and_grad(t[:npar].copy(), float(t[npar]) if with_noise else float(noise))
+            g = np.asarray(g, dtype=np.float64)
+            last.update(key=key, val=float(val), grad=(g if with_noise else g[:npar]) * t)
+        return last["val"], last["grad"]
+
+    def fn(z):
+        try:
+            return -evaluate(z)[0]
+        except (nat.NotPositiveDefinite, ArithmeticError):
+            return -SENTINEL
+
+    z, fmin, fncount, grcount, fail = vmmin(z0, fn, lambda z: -evaluate(z)[1], maxit=maxit)
+    t = np.exp(z)
+    par = tuple(float(v) for v in t[:npar])
+    return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
+            "convergence": fail, "func": CovFunc(func, {"l": np.array(par)} if name == "sqrexp_ard" else func.bind(par, {}))}
 
 
 def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):

@@ -13,9 +13,10 @@ import numpy as np
 
 from . import _native as nat
 from .covfunc import (as_points, cov_func, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic,
-                      require_tagged)
+                      sqrexp_ard, require_tagged)
 
-__all__ = ["GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp", "GPR_rationalquadratic"]
+__all__ = ["GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp", "GPR_rationalquadratic",
+           "GPR_sqrexp_ard"]
 
 
 def _r_num(x) -> str:
@@ -337,6 +338,19 @@ class GPR_rationalquadratic(GPR):
         super().__init__(X, y, noise, cov_func(rationalquadratic, l=l, alpha=alpha), **kw)
 
 
+class GPR_sqrexp_ard(GPR):
+    """GPR with the ARD squared exponential exp(-1/2 sum_k ((x_k - y_k) / l_k)^2); l = None: every length scale 1
+    (fit.optimize(X, y, noise, "sqrexp_ard") learns them).  No reference counterpart."""
+
+    def __init__(self, X, y, noise, l=None, **kw):
+        d = as_points(np.asarray(X)).shape[0]
+        if l is None:
+            l = np.ones(d)
+        if _len(l) != d:
+            raise ValueError("length(l) == nrow(X) is not TRUE")
+        super().__init__(X, y, noise, cov_func(sqrexp_ard, l=l), **kw)
+
+
 # `GPR.sqrexp$new(...)` reads `GPR.sqrexp.new(...)` here
 GPR.constant = GPR_constant
 GPR.linear = GPR_linear
@@ -344,3 +358,4 @@ GPR.polynomial = GPR_polynomial
 GPR.sqrexp = GPR_sqrexp
 GPR.gammaexp = GPR_gammaexp
 GPR.rationalquadratic = GPR_rationalquadratic
+GPR.sqrexp_ard = GPR_sqrexp_ard

@@ -126,6 +126,13 @@ covariance_matrix <- function(A, B, covariance_function) {
   y <- as.double(y)
   function(v) .Call(gprc_R_fit_gradient, id, as.double(v), X, y)
 }
+# the exact gradient (no reference counterpart): function(v, noise) -> c(logp, d logp / d v, d logp / d noise);
+# id 6L is the ARD squared exponential (v = one length scale per row of X)
+.logp_grad_native <- function(id, X, y) {
+  storage.mode(X) <- "double"
+  y <- as.double(y)
+  function(v, noise) .Call(gprc_R_logp_grad, id, as.double(v), X, y, as.double(noise))
+}
 
 # multivariate_normal (R/GPRclass.R:360-370), native branch: rnorm() stays in R, the factorisation and L %*% Z move
 multivariate_normal <- function(n, mean, covariance, tol = 1e-6) {

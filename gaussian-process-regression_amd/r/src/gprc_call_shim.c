@@ -304,6 +304,18 @@ SEXP gprc_R_fit_gradient(SEXP kernel, SEXP params, SEXP X, SEXP y) {
   return g;
 }
 
+/* log marginal likelihood and its exact gradient (gprc_gpr_logp_grad; no reference counterpart): c(logp, d/dparams..., d/dnoise);
+ * not positive definite -> R error, as gprc_R_log_marginal */
+SEXP gprc_R_logp_grad(SEXP kernel, SEXP params, SEXP X, SEXP y, SEXP noise) {
+  const int64_t d = Rf_nrows(X), n = Rf_ncols(X);
+  SEXP g = PROTECT(Rf_allocVector(REALSXP, LENGTH(params) + 2));
+  int rc = gprc_gpr_logp_grad(ctx(), Rf_asInteger(kernel), REAL(params), LENGTH(params), REAL(X), d, n, REAL(y), Rf_asReal(noise), REAL(g), REAL(g) + 1);
+  UNPROTECT(1);
+  if (rc > 0) Rf_error("the leading minor of order %d is not positive definite", rc);
+  if (rc != 0) Rf_error("gprc: %s", gprc_last_error());
+  return g;
+}
+
 /* multivariate_normal(n, mean, covariance, tol)  --  R/GPRclass.R:360-370.  Z = matrix(rnorm(n * length(mean)), nrow =
  * length(mean)) is drawn by the R caller, so set.seed() keeps governing the draws. */
 SEXP gprc_R_mvn_sample(SEXP mean, SEXP covariance, SEXP tol, SEXP Z) {
@@ -347,6 +359,7 @@ static const R_CallMethodDef call_methods[] = {
     {"gprc_R_gpc_predict_class", (DL_FUNC)&gprc_R_gpc_predict_class, 2},
     {"gprc_R_log_marginal", (DL_FUNC)&gprc_R_log_marginal, 5},
     {"gprc_R_fit_gradient", (DL_FUNC)&gprc_R_fit_gradient, 4},
+    {"gprc_R_logp_grad", (DL_FUNC)&gprc_R_logp_grad, 5},
     {"gprc_R_mvn_sample", (DL_FUNC)&gprc_R_mvn_sample, 4},
     {"gprc_R_combine_all", (DL_FUNC)&gprc_R_combine_all, 2},
     {"gprc_R_device_count", (DL_FUNC)&gprc_R_device_count, 0},

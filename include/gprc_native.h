@@ -53,14 +53,16 @@ extern "C" {
  *   GPRC_POLYNOMIAL   params = {sigma, p}        R/GPRclass.R:390
  *   GPRC_SQREXP       params = {l}               R/GPRclass.R:394
  *   GPRC_GAMMAEXP     params = {l, gamma}        R/GPRclass.R:398
- *   GPRC_RATQUAD      params = {l, alpha}        R/GPRclass.R:402 */
+ *   GPRC_RATQUAD      params = {l, alpha}        R/GPRclass.R:402
+ *   GPRC_SQREXP_ARD   params = l[d], every l_k > 0: exp(-1/2 sum_k ((x_k - y_k) / l_k)^2)   (no reference counterpart; d <= 256) */
 typedef enum {
   GPRC_CONSTANT = 0,
   GPRC_LINEAR = 1,
   GPRC_POLYNOMIAL = 2,
   GPRC_SQREXP = 3,
   GPRC_GAMMAEXP = 4,
-  GPRC_RATQUAD = 5
+  GPRC_RATQUAD = 5,
+  GPRC_SQREXP_ARD = 6
 } gprc_kernel_id;
 
 typedef enum {
@@ -136,6 +138,19 @@ GPRC_API int gprc_gpr_log_marginal(gprc_ctx* ctx, int kernel, const double* para
  * K is not (numerically) positive definite -- the reference's solve(K) fails there with "computationally singular". */
 GPRC_API int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,
                       int64_t n, const double* y, double* grad_out);
+/* log marginal likelihood of GPR(X, y, noise, kernel(params)) and its exact gradient
+ *   d logp / d theta = 1/2 sum_ij (alpha_i alpha_j - (K_y^-1)_ij) dK_y,ij / d theta,   K_y = K + noise * I,  alpha = K_y^-1 y
+ * (no reference counterpart: R/fit.R:126-139 and gprc_fit_gradient above keep the reference's form).
+ * grad_out: n_params + 1 doubles in HOST memory: d logp / d params[i] in the ABI's parameter order
+ * (GPRC_SQREXP {l}; GPRC_GAMMAEXP {l, gamma}; GPRC_RATQUAD {l, alpha}; GPRC_SQREXP_ARD {l_1..l_d}),
+ * then d logp / d noise (noise enters as K + noise * I, un-squared, R/GPRclass.R:139).
+ * gammaexp's d/d gamma takes u log(r / l) = 0 at r = 0 (the limit, not the reference's NaN).
+ * The whole of L^-1 and of K_y^-1 is held on the device: 2 * gprc_pad(n)^2 doubles of the context's workspace
+ * (GPRC_ERR_NOMEM when that does not fit; gprc_ctx_trim releases it).
+ * No jitter retry: returns info > 0 (leading minor) when K + noise * I is not positive definite.
+ * Other kernel ids: GPRC_ERR_ARG. */
+GPRC_API int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,
+                                int64_t n, const double* y, double noise, double* logp_out, double* grad_out);
 /* GPR$predict (R/GPRclass.R:155-170).  X_star is d x n_star.
  * pointwise != 0: mean_out[n_star], var_out[n_star] = k(x*,x*) - colSums(v*v)      (:164-165)
  * pointwise == 0: mean_out[n_star], var_out = n_star x n_star K(X*,X*) - t(v) %*% v (:167-168) */
