@@ -12,11 +12,11 @@ from .covfunc import (cov_func, covariance_matrix, constant, linear, polynomial,
 from .gpr import (GPR, GPR_constant, GPR_linear, GPR_polynomial, GPR_sqrexp, GPR_gammaexp,
                   GPR_rationalquadratic, GPR_sqrexp_ard)
 from .gpc import GPC
-from .fit import fit, dens, dens_deriv, logp_grad, optimize
+from .fit import fit, dens, dens_deriv, logp_grad, optimize, logq_grad, optimize_gpc
 from .sampling import multivariate_normal, expand_range, mvn_factor, sym_eigen
 from .simulation import combine_all, iid_noise, simulate_regression, simulate_regression_gp, simulate_classification
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "sqrexp_ard", "GPR_sqrexp_ard", "multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "combine_all", "iid_noise",
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "logq_grad", "optimize_gpc", "sqrexp_ard", "GPR_sqrexp_ard", "multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "combine_all", "iid_noise",
            "simulate_regression", "simulate_regression_gp", "simulate_classification", "GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp",
            "GPR_rationalquadratic", "GPC", "cov_func", "covariance_matrix", "constant", "linear", "polynomial",
            "sqrexp", "gammaexp", "rationalquadratic", "CovFunc", "GprcError", "NotPositiveDefinite", "Context",

@@ -76,6 +76,8 @@ PROTOTYPES = {
     "gprc_class_probability": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "gprc_gpc_get_f_hat": (C.c_int, [_vp, _vp]),
     "gprc_gpc_get_logq": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "gprc_gpc_logq_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.c_int, C.POINTER(C.c_double), _dp,
+                                     C.POINTER(C.c_int)]),
     "gprc_panel_width": (_i64, []),
     "gprc_pad": (_i64, [_i64]),
     "gprc_panel_count": (_i64, [_i64]),
@@ -200,7 +202,7 @@ def device_count() -> int:
 INFO_WAIT_TIMEOUT = -99   # include/gprc_native.h: a device-side dependency wait ran out
 PROF_KINDS = ["fill", "potf2_inv", "trsm_panel", "gemm_inner_k128", "trailing_update", "solve_update_k512", "trsv",
               "row_reduce", "cov_syrk", "deriv_rowsum", "jacobi_sweep", "solve_left", "trailing_left", "panel_fused", "solve_panel",
-              "inverse_gemm", "grad_contract"]
+              "inverse_gemm", "grad_contract", "gpc_grad_contract"]
 
 
 def prof_summary():

@@ -859,6 +859,82 @@ int gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const double* y
   return 0;
 }
 
+// The Laplace mode search of GPC$initialize (R/GPCclass.R:73-102), shared by gprc_gpc_fit and gprc_gpc_logq_grad: Newton / IRLS from
+// f = 0 until |delta objective| < epsilon, then the final B = L L^T at the mode.  The model receives X, y, f_hat, sw and the factor; the
+// state keeps what the evidence gradient goes on with: the dense K, a = K^-1 f_hat (vec + 2 n_pad), the objective at the mode and,
+// with final_inv, the explicit diagonal-block inverses of the FINAL factor (the fit does not need them and does not compute them).
+// st->it is set whatever the outcome (0: the loop was never reached).
+struct GpcMode {
+  DevMem Kf, vec, red, inv;
+  int it = 0;
+  double objective = 0.0;
+};
+int gpc_mode_search(gprc_model* m, const double* X, const double* y, double epsilon, int max_iter, int flags, bool final_inv, GpcMode* st) {
+  gprc_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n, d = m->d, n_pad = m->n_pad;
+  const KernelSpec& ks = m->ks;
+  if (max_iter <= 0) max_iter = 1000;
+  DevMem &Kf = st->Kf, &vec = st->vec, &red = st->red, &inv = st->inv;
+  GPRC_TRY(Kf.alloc(n_pad * n_pad));
+  GPRC_TRY(vec.alloc(4 * n_pad));
+  GPRC_TRY(red.alloc(n_pad * rowreduce_splits(n_pad)));
+  double *b = vec.p, *t = vec.p + n_pad, *a = vec.p + 2 * n_pad, *f = m->f_hat;
+  GPRC_HIP(hipMemcpyAsync(m->X, X, sizeof(double) * d * n, hipMemcpyDefault, s));
+  GPRC_HIP(hipMemsetAsync(m->y, 0, sizeof(double) * n_pad, s));
+  GPRC_HIP(hipMemcpyAsync(m->y, y, sizeof(double) * n, hipMemcpyDefault, s));
+  GPRC_HIP(hipMemsetAsync(f, 0, sizeof(double) * n_pad, s));  // f <- rep(0, n)  R/GPCclass.R:74
+  GPRC_HIP(hipMemsetAsync(vec.p, 0, sizeof(double) * 4 * n_pad, s));
+  for (int64_t c0 = 0; c0 < n_pad; c0 += 32768) {  // K <- covariance_matrix(X, X, k)  :73 (dense, zero padded)
+    const int64_t nc = (n_pad - c0 < 32768) ? n_pad - c0 : 32768;
+    GPRC_TRY(launch_fill(s, ks, m->X, n, m->X, n, d, Kf.p + c0 * n_pad, n_pad, 0, n_pad, c0, nc, PAD_ZERO, 0.0));
+  }
+  // explicit inverses of B's diagonal blocks, for the two vector solves of an iteration
+  GPRC_TRY(inv.alloc(gprc_solve_inv_size(n_pad)));
+  int it = 0;
+  double objective = 0.0, last_objective = 0.0, least_objective = 0.0;
+  int status = 0;
+  for (;;) {
+    st->it = ++it;
+    GPRC_TRY(launch_gpc_pre(s, f, m->y, n, m->sw, b));                       // :78-81
+    auto build_B = [&]() -> int { return launch_gpc_build_B(s, Kf.p, n_pad, m->sw, m->packed); };
+    GPRC_TRY(build_B());                                                      // :80
+    int info = 0;
+    GPRC_TRY(factor_all_or_refill(ctx, m->packed, n_pad, m->winv, &info, inv.p, build_B));
+    if (info != 0) { set_error("GPC: I + sqrt(W) K sqrt(W) not positive definite"); return info; }
+    GPRC_TRY(launch_row_reduce(s, Kf.p, n_pad, n_pad, n_pad, b, t, red.p));  // K %*% b
+    GPRC_TRY(launch_gpc_scale(s, m->sw, t, t, n_pad));                        // sqrt(W) * .
+    GPRC_TRY(launch_trsv(s, m->packed, inv.p, n_pad, t, 0, m->work));         // :82
+    GPRC_TRY(launch_trsv(s, m->packed, inv.p, n_pad, t, 1, m->work));         // :83
+    GPRC_TRY(launch_gpc_a(s, b, m->sw, t, a, n_pad));                         // :84
+    GPRC_TRY(launch_row_reduce(s, Kf.p, n_pad, n_pad, n_pad, a, f, red.p));  // f <- K %*% a  :85
+    GPRC_TRY(launch_gpc_objective(s, a, f, m->y, n, ctx->scal_dev));          // :86
+    GPRC_HIP(hipMemcpyAsync(&objective, ctx->scal_dev, sizeof(double), hipMemcpyDeviceToHost, s));
+    GPRC_HIP(hipStreamSynchronize(s));
+    if (it > 1) {
+      if (std::fabs(objective - last_objective) < epsilon) break;                          // :88
+      else if ((flags & GPRC_GPC_REFERENCE_STOP) && least_objective + 10.0 < objective) { status = GPRC_ERR_DIVERGED; break; }  // :90
+    } else {
+      least_objective = objective;
+    }
+    last_objective = objective;
+    if (it >= max_iter) { status = GPRC_ERR_MAXITER; break; }
+  }
+  st->objective = objective;
+  if (status != 0) {
+    set_error(status == GPRC_ERR_DIVERGED ? "Apparently does not converge." : "GPC: iteration cap reached");
+    return status;
+  }
+  // final L from the converged f (:99-102)
+  GPRC_TRY(launch_gpc_pre(s, f, m->y, n, m->sw, b));
+  auto build_B = [&]() -> int { return launch_gpc_build_B(s, Kf.p, n_pad, m->sw, m->packed); };
+  GPRC_TRY(build_B());
+  int info = 0;
+  GPRC_TRY(factor_all_or_refill(ctx, m->packed, n_pad, m->winv, &info, final_inv ? inv.p : nullptr, build_B));
+  if (info != 0) { set_error("GPC: final factorisation failed"); return info; }
+  return 0;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1306,84 +1382,113 @@ int gprc_gpc_fit(gprc_ctx* ctx, int kernel, const double* params, int n_params, 
                  int* iters_out) {
   GPRC_TRY(check_fit_args(ctx, X, d, n, y, model_out));
   if (!(epsilon > 0.0)) { set_error("epsilon must be > 0"); return GPRC_ERR_ARG; }  // R/GPCclass.R:68
-  if (max_iter <= 0) max_iter = 1000;
   GPRC_TRY(use_device(ctx));
   KernelSpec ks;
   GPRC_TRY(make_spec(kernel, params, n_params, d, &ks));
   gprc_model* m = nullptr;
   GPRC_TRY(alloc_model(ctx, MODEL_GPC, ks, n, d, &m));
   hipStream_t s = ctx->stream;
-  const int64_t n_pad = m->n_pad;
-  DevMem Kf, vec, red;
-  int rc = 0;
+  GpcMode st;
+  int rc = gpc_mode_search(m, X, y, epsilon, max_iter, flags, false, &st);
+  if (iters_out && st.it > 0) *iters_out = st.it;
+  if (rc != 0) { free_model(m); return rc; }
 #define GPC_TRY(call) do { rc = (call); if (rc != 0) { free_model(m); return rc; } } while (0)
 #define GPC_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { free_model(m); return hip_fail(e__, #call, __FILE__, __LINE__); } } while (0)
-  GPC_TRY(Kf.alloc(n_pad * n_pad));
-  GPC_TRY(vec.alloc(4 * n_pad));
-  GPC_TRY(red.alloc(n_pad * rowreduce_splits(n_pad)));
-  double *b = vec.p, *t = vec.p + n_pad, *a = vec.p + 2 * n_pad, *f = m->f_hat;
-  GPC_HIP(hipMemcpyAsync(m->X, X, sizeof(double) * d * n, hipMemcpyDefault, s));
-  GPC_HIP(hipMemsetAsync(m->y, 0, sizeof(double) * n_pad, s));
-  GPC_HIP(hipMemcpyAsync(m->y, y, sizeof(double) * n, hipMemcpyDefault, s));
-  GPC_HIP(hipMemsetAsync(f, 0, sizeof(double) * n_pad, s));  // f <- rep(0, n)  R/GPCclass.R:74
-  GPC_HIP(hipMemsetAsync(vec.p, 0, sizeof(double) * 4 * n_pad, s));
-  for (int64_t c0 = 0; c0 < n_pad; c0 += 32768) {  // K <- covariance_matrix(X, X, k)  :73 (dense, zero padded)
-    const int64_t nc = (n_pad - c0 < 32768) ? n_pad - c0 : 32768;
-    GPC_TRY(launch_fill(s, ks, m->X, n, m->X, n, d, Kf.p + c0 * n_pad, n_pad, 0, n_pad, c0, nc, PAD_ZERO, 0.0));
-  }
-  DevMem inv;   // explicit inverses of B's diagonal blocks, for the two vector solves of an iteration
-  GPC_TRY(inv.alloc(gprc_solve_inv_size(n_pad)));
-  int it = 0;
-  double objective = 0.0, last_objective = 0.0, least_objective = 0.0;
-  int status = 0;
-  for (;;) {
-    ++it;
-    GPC_TRY(launch_gpc_pre(s, f, m->y, n, m->sw, b));                       // :78-81
-    auto build_B = [&]() -> int { return launch_gpc_build_B(s, Kf.p, n_pad, m->sw, m->packed); };
-    GPC_TRY(build_B());                                                      // :80
-    int info = 0;
-    GPC_TRY(factor_all_or_refill(ctx, m->packed, n_pad, m->winv, &info, inv.p, build_B));
-    if (info != 0) { free_model(m); set_error("GPC: I + sqrt(W) K sqrt(W) not positive definite"); return info; }
-    GPC_TRY(launch_row_reduce(s, Kf.p, n_pad, n_pad, n_pad, b, t, red.p));  // K %*% b
-    GPC_TRY(launch_gpc_scale(s, m->sw, t, t, n_pad));                        // sqrt(W) * .
-    GPC_TRY(launch_trsv(s, m->packed, inv.p, n_pad, t, 0, m->work));         // :82
-    GPC_TRY(launch_trsv(s, m->packed, inv.p, n_pad, t, 1, m->work));         // :83
-    GPC_TRY(launch_gpc_a(s, b, m->sw, t, a, n_pad));                         // :84
-    GPC_TRY(launch_row_reduce(s, Kf.p, n_pad, n_pad, n_pad, a, f, red.p));  // f <- K %*% a  :85
-    GPC_TRY(launch_gpc_objective(s, a, f, m->y, n, ctx->scal_dev));          // :86
-    GPC_HIP(hipMemcpyAsync(&objective, ctx->scal_dev, sizeof(double), hipMemcpyDeviceToHost, s));
-    GPC_HIP(hipStreamSynchronize(s));
-    if (it > 1) {
-      if (std::fabs(objective - last_objective) < epsilon) break;                          // :88
-      else if ((flags & GPRC_GPC_REFERENCE_STOP) && least_objective + 10.0 < objective) { status = GPRC_ERR_DIVERGED; break; }  // :90
-    } else {
-      least_objective = objective;
-    }
-    last_objective = objective;
-    if (it >= max_iter) { status = GPRC_ERR_MAXITER; break; }
-  }
-  if (iters_out) *iters_out = it;
-  if (status != 0) {
-    free_model(m);
-    set_error(status == GPRC_ERR_DIVERGED ? "Apparently does not converge." : "GPC: iteration cap reached");
-    return status;
-  }
-  // final L from the converged f (:99-102), logq = objective - sum(diag(L)) (:103, sic)
-  GPC_TRY(launch_gpc_pre(s, f, m->y, n, m->sw, b));
-  auto build_B = [&]() -> int { return launch_gpc_build_B(s, Kf.p, n_pad, m->sw, m->packed); };
-  GPC_TRY(build_B());
-  int info = 0;
-  GPC_TRY(factor_all_or_refill(ctx, m->packed, n_pad, m->winv, &info, nullptr, build_B));
-  if (info != 0) { free_model(m); set_error("GPC: final factorisation failed"); return info; }
+  // logq = objective - sum(diag(L)) (:103, sic)
   double dsum = 0.0;
-  GPC_TRY(launch_diag_sum(s, m->packed, n_pad, n, ctx->scal_dev));
+  GPC_TRY(launch_diag_sum(s, m->packed, m->n_pad, n, ctx->scal_dev));
   GPC_HIP(hipMemcpyAsync(&dsum, ctx->scal_dev, sizeof(double), hipMemcpyDeviceToHost, s));
-  GPC_TRY(launch_gpc_grad(s, f, m->y, n, m->alpha, m->sw));  // g = (y+1)/2 - P, sw = sqrt(P(1-P)) for predict
+  GPC_TRY(launch_gpc_grad(s, m->f_hat, m->y, n, m->alpha, m->sw));  // g = (y+1)/2 - P, sw = sqrt(P(1-P)) for predict
   GPC_HIP(hipStreamSynchronize(s));
-  m->logq = objective - dsum;
+  m->logq = st.objective - dsum;
 #undef GPC_TRY
 #undef GPC_HIP
   *model_out = m;
+  return 0;
+}
+
+// log q(y | X, theta) of the Laplace approximation and its exact gradient ("GPC evidence gradient"):
+//   mode search            the loop of gprc_gpc_fit (flags 0); K stays; final B = L L^T at the mode with the solve inverses
+//   V^T = I L^-T           the identity through the predict's solve, triangular form                                   n^3 / 3
+//   W = -V^T V = -B^-1     lower triangle (PK_INV_GEMM)                                                               n^3 / 3
+//   vectors                s2 from diag(W); u = s2 - sw B^-1 sw (K s2): one K-matvec, two vector solves
+//   contraction            one pass over W, M = a a^T + sw sw^T o W + u g^T + g u^T, K and dK / dtheta recomputed from X (kernels_grad.hip)
+int gprc_gpc_logq_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                       const double* y, double epsilon, int max_iter, double* logq_out, double* grad_out, int* iters_out) {
+  if (!logq_out || !grad_out) { set_error("logq_grad: null output"); return GPRC_ERR_ARG; }
+  if (kernel != GPRC_SQREXP && kernel != GPRC_GAMMAEXP && kernel != GPRC_RATQUAD && kernel != GPRC_SQREXP_ARD) {
+    set_error("logq_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard");
+    return GPRC_ERR_ARG;
+  }
+  if (!ctx || !X || !y || d < 1 || n < 1) { set_error("logq_grad: bad arguments"); return GPRC_ERR_ARG; }
+  if (!(epsilon > 0.0)) { set_error("epsilon must be > 0"); return GPRC_ERR_ARG; }
+  GPRC_TRY(use_device(ctx));
+  KernelSpec ks;
+  GPRC_TRY(make_spec(kernel, params, n_params, d, &ks));
+  const int64_t n_pad = pad_up(n, NB);
+  const auto nomem = [&]() {
+    set_error("logq_grad: K, the factor, L^-1 and B^-1 are held whole, about 3.5 x " + std::to_string(n_pad) + "^2 doubles (" +
+              std::to_string((7 * n_pad * n_pad * (int64_t)sizeof(double) / 2) >> 20) + " MiB) of device memory, which could not be allocated");
+    return GPRC_ERR_NOMEM;
+  };
+  gprc_model* m = nullptr;
+  int rc = alloc_model(ctx, MODEL_GPC, ks, n, d, &m);
+  if (rc == GPRC_ERR_NOMEM) return nomem();
+  GPRC_TRY(rc);
+  struct Guard { gprc_model* m; ~Guard() { free_model(m); } } guard{m};
+  hipStream_t s = ctx->stream;
+  double *vt = nullptr, *W = nullptr;   // claimed before the mode search: a size that does not fit fails before any work
+  rc = ws_get(ctx, 0, n_pad * n_pad, &vt);
+  if (rc == 0) rc = ws_get(ctx, 3, n_pad * n_pad, &W);
+  if (rc == GPRC_ERR_NOMEM) return nomem();
+  GPRC_TRY(rc);
+  GpcMode st;
+  rc = gpc_mode_search(m, X, y, epsilon, max_iter, 0, true, &st);
+  if (iters_out && st.it > 0) *iters_out = st.it;
+  if (rc == GPRC_ERR_NOMEM) return nomem();
+  GPRC_TRY(rc);
+  double* a = st.vec.p + 2 * n_pad;                                          // K^-1 f_hat (the loop's a)
+  double *s2 = st.vec.p, *t = st.vec.p + n_pad, *u = st.vec.p + 3 * n_pad;   // b and t of the loop are free now
+  double* g = m->alpha;
+  GPRC_TRY(launch_diag_log_sum(s, m->packed, n_pad, n, ctx->scal_dev + 1));
+  GPRC_TRY(launch_gpc_grad(s, m->f_hat, m->y, n, g, m->sw));                 // g = (y+1)/2 - P; sw as the final factorisation used it
+  GPRC_TRY(launch_set_identity_rows(s, vt, n_pad, n_pad, n_pad, 0));
+  GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, n_pad, n_pad, nullptr, 0));   // vt = L^-T (upper triangular)
+  GPRC_HIP(hipMemsetAsync(W, 0, sizeof(double) * (size_t)(n_pad * n_pad), s));
+  GPRC_TRY(launch_gemm_nt(s, W, n_pad, vt, n_pad, vt, n_pad, n_pad, n_pad, n_pad, 1, PK_INV_GEMM));
+  GPRC_TRY(launch_gpc_s2(s, m->f_hat, W, n_pad, n, s2));
+  GPRC_TRY(launch_row_reduce(s, st.Kf.p, n_pad, n_pad, n_pad, s2, t, st.red.p));        // K s2
+  GPRC_TRY(launch_gpc_scale(s, m->sw, t, t, n_pad));
+  GPRC_TRY(launch_trsv(s, m->packed, st.inv.p, n_pad, t, 0, m->work));
+  GPRC_TRY(launch_trsv(s, m->packed, st.inv.p, n_pad, t, 1, m->work));
+  GPRC_TRY(launch_gpc_a(s, s2, m->sw, t, u, n_pad));                                    // u = s2 - sw B^-1 sw K s2
+  const int64_t rows = grad_partial_rows();
+  DevMem part;
+  GPRC_TRY(part.alloc(rows * n_params));
+  GPRC_TRY(launch_gpc_grad_contract(s, m->ks, m->X, d, n, a, m->sw, u, g, W, n_pad, part.p));
+  std::vector<double> hp((size_t)(rows * n_params));
+  double lsum = 0.0;
+  GPRC_HIP(hipMemcpyAsync(hp.data(), part.p, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipMemcpyAsync(&lsum, ctx->scal_dev + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  std::vector<long double> acc((size_t)n_params, 0.0L);
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t k = 0; k < n_params; ++k) acc[(size_t)k] += (long double)hp[(size_t)(r * n_params + k)];
+  const double p0 = params[0], p1 = n_params > 1 ? params[1] : 0.0;
+  switch (kernel) {   // the factors that do not depend on (i, j): kernels_grad.hip
+    case GPRC_SQREXP: grad_out[0] = (double)(0.5L * acc[0] / ((long double)p0 * p0 * p0)); break;
+    case GPRC_GAMMAEXP:
+      grad_out[0] = (double)(0.5L * acc[0] * (long double)p1 / (long double)p0);
+      grad_out[1] = (double)(-0.25L * acc[1]);
+      break;
+    case GPRC_RATQUAD:
+      grad_out[0] = (double)(0.5L * acc[0] / ((long double)p0 * p0 * p0));
+      grad_out[1] = (double)(0.5L * acc[1]);
+      break;
+    default:
+      for (int k = 0; k < n_params; ++k) grad_out[k] = (double)(0.5L * acc[(size_t)k] / (long double)params[k]);
+  }
+  *logq_out = st.objective - lsum;
   return 0;
 }
 

@@ -45,7 +45,7 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 // ---- in-library event profiler (bench.py's live roofline numbers) ---------------------------------
 enum ProfKind { PK_FILL = 0, PK_POTF2 = 1, PK_TRSM_PANEL = 2, PK_GEMM_INNER = 3, PK_TRAILING = 4, PK_SOLVE_UPDATE = 5,
-                PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_INV_GEMM = 15, PK_GRAD_CONTRACT = 16, PK_COUNT = 17 };
+                PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_INV_GEMM = 15, PK_GRAD_CONTRACT = 16, PK_GPC_GRAD_CONTRACT = 17, PK_COUNT = 18 };
 bool prof_enabled();
 void prof_begin(hipStream_t s, int kind);
 void prof_end(hipStream_t s, int kind, double flops, double bytes);
@@ -91,6 +91,10 @@ int launch_set_identity_rows(hipStream_t s, double* vt, int64_t ld, int64_t rows
 int64_t grad_partial_rows();
 int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* alpha, const double* W,
                          int64_t ld, double* part);
+// the Laplace variant (gprc_gpc_logq_grad): W = -B^-1, B = I + sw K sw; part: grad_partial_rows() x ks.n_params doubles, row g = what
+// workgroup g summed of   sum_ij (a_i a_j + sw_i sw_j W_ij + u_i g_j + u_j g_i) dK_ij / dtheta_k   (no diagonal sum: dK_ii = 0)
+int launch_gpc_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* a, const double* sw,
+                             const double* u, const double* g, const double* W, int64_t ld, double* part);
 
 // ---- launchers (kernels_chol.hip) --------------------------------------------------------------
 // factor the 128x128 diagonal block at A (ld) in LDS, write L in place and its inverse to winv
@@ -159,6 +163,10 @@ int launch_gpc_objective(hipStream_t s, const double* a, const double* f, const 
 int launch_gpc_build_B(hipStream_t s, const double* Kfull, int64_t n_pad, const double* sw, double* packed);
 int launch_gpc_grad(hipStream_t s, const double* f, const double* y, int64_t n, double* g, double* sw);           // g=(y+1)/2-P
 int launch_gpc_class_prob(hipStream_t s, const double* fs, const double* vf, double* out, int64_t n);              // R/GPCclass.R:116-117
+// evidence gradient (gprc_gpc_logq_grad): s2_i = 1/2 Sigma_ii d3_i with Sigma_ii = (1 - (B^-1)_ii) / W_ii from the diagonal of
+// negBinv = -B^-1 (n_pad x n_pad, ld) and d3_i = W_i (2 pi_i - 1); zero in the padding.  W_i cancels: 1/2 (1 + negBinv_ii) (2 pi_i - 1)
+int launch_gpc_s2(hipStream_t s, const double* f, const double* negBinv, int64_t ld, int64_t n, double* s2);
+int launch_diag_log_sum(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, double* out);              // sum(log(diag(L)))
 // sampling support (kernels_eig.hip)
 int launch_pack_dense(hipStream_t s, const double* A, int64_t lda, int64_t m, int64_t n_pad, double* packed);
 int launch_sym_copy(hipStream_t s, const double* A, int64_t lda, int64_t m, double* W, double* V);

@@ -19,9 +19,16 @@
 // Order of summation is fixed: a lane's elements in column order, the 64 lanes by a shuffle tree, the four waves in wave order, a
 // workgroup's tiles in tile order (a fixed grid strides over the tile list), the workgroups by the host in long double.  No atomics:
 // two calls on the same input give the same bits.
+//
+// The LAPLACE variant (gprc_gpc_logq_grad, DESIGN.md "GPC evidence gradient") is the same pass over W = -B^-1, B = I + sw K sw, with
+//   M_ij = a_i a_j + sw_i sw_j W_ij + u_i g_j + u_j g_i
+// (explicit part a a^T - R, R = sw B^-1 sw, plus the rank-two form of the implicit part through the mode).  A tile stages the four
+// vectors of its 128 rows and 64 columns in LDS (6 KiB) and reads them there inside the column loop; there is no diagonal sum.
+// It is a compile-time parameter: the regression instantiations are the code they were.
 #include "gprc_internal.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace gprc {
 
@@ -41,6 +48,11 @@ struct GradArgs {
   int64_t ntiles;
   KernelSpec ks;   // derived constants, see make_grad_spec
 };
+struct LaplaceArgs : GradArgs {   // alpha: the mode search's a = K^-1 f
+  const double* sw;
+  const double* u;
+  const double* g;
+};
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -48,15 +60,18 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;  // lane 0 holds the sum
 }
 
-template <int KID>
-__global__ __launch_bounds__(256) void grad_contract_kernel(GradArgs a) {
+template <int KID, bool LAPLACE>
+__global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<LAPLACE, LaplaceArgs, GradArgs> a) {
   __shared__ __attribute__((aligned(16))) double As[GD][GT_R];
   __shared__ double Bs[GT_C][GD + 1];
   __shared__ double Al[GT_C];
   __shared__ double red[4][GD + 1];
   __shared__ double gacc[MAX_PARAMS + 1];
+  __shared__ __attribute__((aligned(16))) double Rv[LAPLACE ? 4 : 1][GT_R];   // Laplace: a, sw, u, g of the tile's rows ...
+  __shared__ double Cv[LAPLACE ? 4 : 1][GT_C];                                 // ... and of its columns
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int np = KID == GPRC_SQREXP_ARD ? (int)a.d : (KID == GPRC_SQREXP ? 1 : 2);
+  constexpr int NZ = LAPLACE ? 0 : 1;   // regression leaves one more sum per workgroup, the diagonal's
   for (int k = t; k <= np; k += 256) gacc[k] = 0.0;
   double a0 = 0.0, a1 = 0.0, nz = 0.0;  // isotropic kernels: this lane's sums over all its tiles; nz: the diagonal's M_ii
 
@@ -84,7 +99,17 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(GradArgs a) {
         if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
         Bs[j][r] = v;
       }
-      if (r0 == 0 && t < GT_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
+      if constexpr (LAPLACE) {
+        if (r0 == 0) {
+          const int v = t >> 6, j = t & 63;   // 4 vectors x 64 columns; 4 x 128 rows, two per thread
+          const double* src = v == 0 ? a.alpha : (v == 1 ? a.sw : (v == 2 ? a.u : a.g));
+          Cv[v][j] = (tj + j < a.n) ? src[tj + j] : 0.0;
+          Rv[v][j] = (ti + j < a.n) ? src[ti + j] : 0.0;
+          Rv[v][j + 64] = (ti + j + 64 < a.n) ? src[ti + j + 64] : 0.0;
+        }
+      } else {
+        if (r0 == 0 && t < GT_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
+      }
       __syncthreads();
     };
 
@@ -107,18 +132,27 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(GradArgs a) {
     }
 
     const int64_t gi0 = ti + 2 * lane;
-    const double al0 = (gi0 < a.n) ? a.alpha[gi0] : 0.0, al1 = (gi0 + 1 < a.n) ? a.alpha[gi0 + 1] : 0.0;
+    const double al0 = (!LAPLACE && gi0 < a.n) ? a.alpha[gi0] : 0.0, al1 = (!LAPLACE && gi0 + 1 < a.n) ? a.alpha[gi0 + 1] : 0.0;
     // rows < 128 ceil(n / 128) <= n_pad and columns <= 64 (2 bi + 1) + 63 < 128 (bi + 1): every load is inside the n_pad x n_pad matrix
     const double* wp = a.W + gi0 + (tj + wave * 16) * a.ld;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int64_t gj = tj + wave * 16 + c;
       const double2 w = *reinterpret_cast<const double2*>(wp + c * a.ld);
-      const double alj = Al[wave * 16 + c];
+      const double alj = LAPLACE ? 0.0 : Al[wave * 16 + c];
       double m0 = fma(al0, alj, w.x), m1 = fma(al1, alj, w.y);
       const bool jin = gj < a.n;
-      if (jin && gi0 == gj) nz += m0;
-      if (jin && gi0 + 1 == gj) nz += m1;
+      if constexpr (LAPLACE) {   // a_i a_j + sw_i sw_j W_ij + u_i g_j + u_j g_i, the eight vector entries from LDS
+        const int cj = wave * 16 + c;
+        const double2 ra = *reinterpret_cast<const double2*>(&Rv[0][2 * lane]), rs = *reinterpret_cast<const double2*>(&Rv[1][2 * lane]);
+        const double2 ru = *reinterpret_cast<const double2*>(&Rv[2][2 * lane]), rg = *reinterpret_cast<const double2*>(&Rv[3][2 * lane]);
+        const double aj = Cv[0][cj], sj = Cv[1][cj], uj = Cv[2][cj], gj_ = Cv[3][cj];
+        m0 = fma(ra.x, aj, (rs.x * sj) * w.x) + fma(ru.x, gj_, uj * rg.x);
+        m1 = fma(ra.y, aj, (rs.y * sj) * w.y) + fma(ru.y, gj_, uj * rg.y);
+      } else {
+        if (jin && gi0 == gj) nz += m0;
+        if (jin && gi0 + 1 == gj) nz += m1;
+      }
       m0 = (jin && gi0 < a.n && gi0 > gj) ? 2.0 * m0 : 0.0;          // the diagonal's dK / d theta is zero for all four kernels
       m1 = (jin && gi0 + 1 < a.n && gi0 + 1 > gj) ? 2.0 * m1 : 0.0;
       if constexpr (KID == GPRC_SQREXP) {
@@ -181,7 +215,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(GradArgs a) {
 
   a0 = wave_sum(a0);
   a1 = wave_sum(a1);
-  nz = wave_sum(nz);
+  if constexpr (!LAPLACE) nz = wave_sum(nz);
   __syncthreads();
   if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; red[wave][2] = nz; }
   __syncthreads();
@@ -190,10 +224,10 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(GradArgs a) {
       gacc[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
       if (np == 2) gacc[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
     }
-    gacc[np] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+    if constexpr (!LAPLACE) gacc[np] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
   }
   __syncthreads();
-  for (int k = t; k <= np; k += 256) a.part[(int64_t)blockIdx.x * (np + 1) + k] = gacc[k];
+  for (int k = t; k < np + NZ; k += 256) a.part[(int64_t)blockIdx.x * (np + NZ) + k] = gacc[k];
 }
 
 // the spec with the constants the kernel wants (ARD: p[k] = 1 / l_k)
@@ -225,11 +259,35 @@ int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, i
   const double elems = 0.5 * (double)n * (double)(n + 1);
   ProfScope ps(s, PK_GRAD_CONTRACT, elems * (3.0 * d + 60.0 + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)), 8.0 * (elems + (double)n * d + n));
   switch (ks.id) {
-    case GPRC_SQREXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP>), grid, block, 0, s, a); break;
-    case GPRC_GAMMAEXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_GAMMAEXP>), grid, block, 0, s, a); break;
-    case GPRC_RATQUAD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_RATQUAD>), grid, block, 0, s, a); break;
-    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP_ARD>), grid, block, 0, s, a); break;
+    case GPRC_SQREXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP, false>), grid, block, 0, s, a); break;
+    case GPRC_GAMMAEXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_GAMMAEXP, false>), grid, block, 0, s, a); break;
+    case GPRC_RATQUAD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_RATQUAD, false>), grid, block, 0, s, a); break;
+    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP_ARD, false>), grid, block, 0, s, a); break;
     default: set_error("logp_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
+  }
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_gpc_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* a_vec, const double* sw,
+                             const double* u, const double* g, const double* W, int64_t ld, double* part) {
+  if (n <= 0) return 0;
+  if ((ld & 1) || (reinterpret_cast<uintptr_t>(W) & 15)) { set_error("gpc_grad_contract: the inverse must be 16-byte aligned with an even leading dimension"); return GPRC_ERR_ARG; }
+  const int64_t R = (n + GT_R - 1) / GT_R;
+  if (ld < R * GT_R) { set_error("gpc_grad_contract: leading dimension smaller than the padded size"); return GPRC_ERR_ARG; }
+  const int np = ks.n_params;
+  LaplaceArgs a{{X, a_vec, W, part, n, d, ld, R * (R + 1), make_grad_spec(ks)}, sw, u, g};
+  GPRC_HIP(hipMemsetAsync(part, 0, sizeof(double) * (size_t)(GRAD_WGS * np), s));   // rows of workgroups that are not launched
+  const dim3 grid((unsigned)std::min<int64_t>(a.ntiles, GRAD_WGS)), block(256);
+  // as launch_grad_contract, plus the four vectors and the 9 flops of M
+  const double elems = 0.5 * (double)n * (double)(n + 1);
+  ProfScope ps(s, PK_GPC_GRAD_CONTRACT, elems * (3.0 * d + 69.0 + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)), 8.0 * (elems + (double)n * d + 4.0 * n));
+  switch (ks.id) {
+    case GPRC_SQREXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP, true>), grid, block, 0, s, a); break;
+    case GPRC_GAMMAEXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_GAMMAEXP, true>), grid, block, 0, s, a); break;
+    case GPRC_RATQUAD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_RATQUAD, true>), grid, block, 0, s, a); break;
+    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP_ARD, true>), grid, block, 0, s, a); break;
+    default: set_error("logq_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
   }
   GPRC_LAUNCH_CHECK();
   return 0;

@@ -384,6 +384,14 @@ __global__ __launch_bounds__(1024) void diag_sum_kernel(const double* packed, in
   if (threadIdx.x == 0) out[0] = t;
 }
 
+__global__ __launch_bounds__(1024) void diag_log_sum_kernel(const double* packed, int64_t n_pad, int64_t n, double* out) {
+  __shared__ double red[1024];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) s += log(*packed_at(packed, n_pad, i, i));
+  const double t = block_sum(s, red);
+  if (threadIdx.x == 0) out[0] = t;
+}
+
 __global__ __launch_bounds__(256) void unpack_kernel(const double* packed, int64_t n_pad, int64_t n, double* out, int64_t ld_out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -450,6 +458,14 @@ __global__ __launch_bounds__(256) void gpc_grad_kernel(const double* f, const do
   const double P = sigmoid(f[i]);
   sw[i] = sqrt(P * (1.0 - P));
   g[i] = (y[i] + 1.0) / 2.0 - P;
+}
+// s2 = 1/2 Sigma_ii d3_i = 1/2 (1 - (B^-1)_ii) (2 P - 1): the derivative of log q with respect to f_i through W (DESIGN.md "GPC evidence gradient")
+__global__ __launch_bounds__(256) void gpc_s2_kernel(const double* f, const double* negBinv, int64_t ld, int64_t n, int64_t n_pad, double* s2) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pad) return;
+  if (i >= n) { s2[i] = 0.0; return; }
+  const double P = sigmoid(f[i]);
+  s2[i] = 0.5 * (1.0 + negBinv[i + i * ld]) * (2.0 * P - 1.0);
 }
 __global__ __launch_bounds__(256) void mul_kernel(const double* a, const double* b, double* out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -661,6 +677,11 @@ int launch_diag_sum(hipStream_t s, const double* packed, int64_t n_pad, int64_t 
   GPRC_LAUNCH_CHECK();
   return 0;
 }
+int launch_diag_log_sum(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, double* out) {
+  hipLaunchKernelGGL(diag_log_sum_kernel, dim3(1), dim3(1024), 0, s, packed, n_pad, n, out);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
 int launch_unpack_L(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, double* out, int64_t ld_out) {
   if (n <= 0) return 0;
   const unsigned gy = (unsigned)(n < 16384 ? n : 16384);
@@ -677,6 +698,12 @@ int launch_gpc_pre(hipStream_t s, const double* f, const double* y, int64_t n, d
 int launch_gpc_grad(hipStream_t s, const double* f, const double* y, int64_t n, double* g, double* sw) {
   const int64_t n_pad = pad_up(n, NB);
   hipLaunchKernelGGL(gpc_grad_kernel, dim3(blocks(n_pad, 256)), dim3(256), 0, s, f, y, n, n_pad, g, sw);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+int launch_gpc_s2(hipStream_t s, const double* f, const double* negBinv, int64_t ld, int64_t n, double* s2) {
+  const int64_t n_pad = pad_up(n, NB);
+  hipLaunchKernelGGL(gpc_s2_kernel, dim3(blocks(n_pad, 256)), dim3(256), 0, s, f, negBinv, ld, n, n_pad, s2);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

@@ -21,6 +21,8 @@ Beside the reference-faithful fit() stands an EXACT path (no reference counterpa
 likelihood and its true gradient in one native call (gprc_gpr_logp_grad: the noisy K_y = K + noise I, a trace, every
 parameter and the noise), and `optimize` maximises it over log(theta) (and log(noise)) with the same vmmin.  It is what
 makes gammaexp / rationalquadratic searches move and what the d length scales of `sqrexp_ard` need.
+Classification has the same pair: `logq_grad` is the Laplace log evidence of GPC and its exact gradient (gprc_gpc_logq_grad: the
+mode search of GPC$new, then one contraction), `optimize_gpc` maximises it over log(theta).
 Parity status: unpinned (the reference holds no numeric expectations for fit(); tests/testthat/test-fit.R:12-17 only
 checks which kernel NAME wins); cross-checked against scipy's bounded Brent on the same native objective, and the
 BFGS branch against the same driver running on the CPU oracle's objective and gradient.
@@ -36,7 +38,7 @@ import numpy as np
 from . import _native as nat
 from .covfunc import CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "cov_dict", "brent_fmin", "vmmin"]
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "logq_grad", "optimize_gpc", "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
 cov_dict = {
@@ -102,6 +104,54 @@ def logp_grad(X, y, noise, name, v, ctx=None):
     return out.value, g
 
 
+def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):
+    """(logq, grad) of GP classification with kernel name(v) on (X, y), y in {-1, +1}: the Laplace approximation of the log
+    evidence and its exact gradient (explicit part and the part through the mode), one native call (gprc_gpc_logq_grad).
+    `logq` is the true evidence, -1/2 a.f + sum log sigmoid(y f) - sum(log(diag(L))): NOT GPC's `$logq`, which keeps the
+    reference's sum(diag(L)).  The mode search is GPC(X, y, k, epsilon, reference_stop=False)'s; the default epsilon 1e-10
+    (not GPC's 1e-5) is what a gradient accurate to 1e-10 needs.  Raises GprcError (ERR_MAXITER) when it does not converge
+    within max_iter (0: 1000) steps."""
+    func = grad_dict[name]
+    Xm = as_points(X)
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    d, n = Xm.shape
+    if y.size != n:
+        raise ValueError("length(y) == ncol(X) is not TRUE")
+    ctx = ctx or nat.default_context()
+    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    g = np.empty(p.size)
+    out = C.c_double()
+    nat.check(nat.lib().gprc_gpc_logq_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(epsilon),
+                                           int(max_iter), C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double)), None))
+    return out.value, g
+
+
+def _maximise_over_log(z0, value_and_grad_theta, maxit):
+    """vmmin on z = log(theta) of a function to MAXIMISE: value_and_grad_theta(theta) -> (value, d value / d theta); the chain
+    rule d / dz = theta * d / dtheta; an evaluation that raises NotPositiveDefinite / ArithmeticError / a native iteration cap,
+    or whose exp(z) over- or underflows, is the sentinel -10000 (optim_until_error).  Returns vmmin's tuple."""
+    last = {}   # vmmin asks for the gradient at the point whose value it has just accepted: one evaluation serves both
+
+    def evaluate(z):
+        key = z.tobytes()
+        if last.get("key") != key:
+            with np.errstate(over="ignore"):
+                t = np.exp(z)
+            if not (np.all(np.isfinite(t)) and np.all(t > 0)):
+                raise ArithmeticError("parameter out of range")
+            val, g = value_and_grad_theta(t)
+            last.update(key=key, val=float(val), grad=np.asarray(g, dtype=np.float64) * t)
+        return last["val"], last["grad"]
+
+    def fn(z):
+        try:
+            return -evaluate(z)[0]
+        except (nat.NotPositiveDefinite, ArithmeticError):
+            return -SENTINEL
+
+    return vmmin(z0, fn, lambda z: -evaluate(z)[1], maxit=maxit)
+
+
 def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, value_and_grad=None, ctx=None):
     """Maximise the log marginal likelihood of kernel `name` ("sqrexp", "gammaexp", "rationalquadratic", "sqrexp_ard")
     over its parameters, and over the noise when `optimize_noise` and noise > 0, with vmmin on z = log(theta): every
@@ -124,31 +174,49 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
         ctx = ctx or nat.default_context()
         value_and_grad = lambda theta, nz: logp_grad(Xm, y, nz, name, theta, ctx)   # noqa: E731
     z0 = np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0)
-    last = {}   # vmmin asks for the gradient at the point whose value it has just accepted: one evaluation serves both
 
-    def evaluate(z):
-        key = z.tobytes()
-        if last.get("key") != key:
-            with np.errstate(over="ignore"):
-                t = np.exp(z)
-            if not (np.all(np.isfinite(t)) and np.all(t > 0)):
-                raise ArithmeticError("parameter out of range")
-            val, g = value_and_grad(t[:npar].copy(), float(t[npar]) if with_noise else float(noise))
-            g = np.asarray(g, dtype=np.float64)
-            last.update(key=key, val=float(val), grad=(g if with_noise else g[:npar]) * t)
-        return last["val"], last["grad"]
+    def vg(t):
+        val, g = value_and_grad(t[:npar].copy(), float(t[npar]) if with_noise else float(noise))
+        g = np.asarray(g, dtype=np.float64)
+        return val, (g if with_noise else g[:npar])
 
-    def fn(z):
-        try:
-            return -evaluate(z)[0]
-        except (nat.NotPositiveDefinite, ArithmeticError):
-            return -SENTINEL
-
-    z, fmin, fncount, grcount, fail = vmmin(z0, fn, lambda z: -evaluate(z)[1], maxit=maxit)
+    z, fmin, fncount, grcount, fail = _maximise_over_log(z0, vg, maxit)
     t = np.exp(z)
     par = tuple(float(v) for v in t[:npar])
     return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
             "convergence": fail, "func": CovFunc(func, {"l": np.array(par)} if name == "sqrexp_ard" else func.bind(par, {}))}
+
+
+def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_grad=None, ctx=None):
+    """Maximise the Laplace log evidence of GP classification (y in {-1, +1}) over the parameters of kernel `name` ("sqrexp",
+    "gammaexp", "rationalquadratic", "sqrexp_ard") with vmmin on z = log(theta), exactly as `optimize` does for regression.
+    start: parameter vector (default: cov_dict's start values; ones(d) for sqrexp_ard).  value_and_grad(theta) -> (logq, grad)
+    replaces the native objective `logq_grad`.  An evaluation that fails (a mode search that does not converge, a parameter
+    over- or underflowing) counts as the sentinel -10000.  Returns dict(par, value, counts, convergence, func):
+    GPC(X, y, r["func"], reference_stop=False) is the fitted classifier; convergence 0: converged, 1: maxit reached."""
+    func = grad_dict[name]
+    Xm = as_points(X)
+    d = Xm.shape[0]
+    if start is None:
+        start = np.ones(d) if name == "sqrexp_ard" else cov_dict[name][2]
+    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
+    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
+        raise ValueError("optimize_gpc: start values must be finite and > 0")
+    if value_and_grad is None:
+        ctx = ctx or nat.default_context()
+
+        def value_and_grad(theta):
+            try:
+                return logq_grad(Xm, y, name, theta, epsilon, 0, ctx)
+            except nat.GprcError as e:
+                if e.status == nat.ERR_MAXITER:
+                    raise ArithmeticError("the mode search did not converge") from e
+                raise
+
+    z, fmin, fncount, grcount, fail = _maximise_over_log(np.log(theta0), lambda t: value_and_grad(t.copy()), maxit)
+    par = tuple(float(v) for v in np.exp(z))
+    return {"par": par, "value": -fmin, "counts": (fncount, grcount), "convergence": fail,
+            "func": CovFunc(func, {"l": np.array(par)} if name == "sqrexp_ard" else func.bind(par, {}))}
 
 
 def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):

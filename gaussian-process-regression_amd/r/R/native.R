@@ -133,6 +133,13 @@ covariance_matrix <- function(A, B, covariance_function) {
   y <- as.double(y)
   function(v, noise) .Call(gprc_R_logp_grad, id, as.double(v), X, y, as.double(noise))
 }
+# classification: function(v) -> c(logq, d logq / d v), the Laplace log evidence (the TRUE one: log of diag(L), not GPC$logq's
+# sum(diag(L))) and its exact gradient; a mode search that does not converge is an R error.  y in {-1, +1}
+.logq_grad_native <- function(id, X, y, epsilon = 1e-10) {
+  storage.mode(X) <- "double"
+  y <- as.double(y)
+  function(v) .Call(gprc_R_logq_grad, id, as.double(v), X, y, as.double(epsilon))
+}
 
 # multivariate_normal (R/GPRclass.R:360-370), native branch: rnorm() stays in R, the factorisation and L %*% Z move
 multivariate_normal <- function(n, mean, covariance, tol = 1e-6) {

@@ -316,6 +316,18 @@ SEXP gprc_R_logp_grad(SEXP kernel, SEXP params, SEXP X, SEXP y, SEXP noise) {
   return g;
 }
 
+/* Laplace log evidence of GPC and its exact gradient (gprc_gpc_logq_grad; no reference counterpart): c(logq, d/dparams...) */
+SEXP gprc_R_logq_grad(SEXP kernel, SEXP params, SEXP X, SEXP y, SEXP epsilon) {
+  const int64_t d = Rf_nrows(X), n = Rf_ncols(X);
+  SEXP g = PROTECT(Rf_allocVector(REALSXP, LENGTH(params) + 1));
+  int rc = gprc_gpc_logq_grad(ctx(), Rf_asInteger(kernel), REAL(params), LENGTH(params), REAL(X), d, n, REAL(y), Rf_asReal(epsilon), 0, REAL(g),
+                              REAL(g) + 1, NULL);
+  UNPROTECT(1);
+  if (rc > 0) Rf_error("the leading minor of order %d is not positive definite", rc);
+  if (rc != 0) Rf_error("gprc: %s", gprc_last_error());
+  return g;
+}
+
 /* multivariate_normal(n, mean, covariance, tol)  --  R/GPRclass.R:360-370.  Z = matrix(rnorm(n * length(mean)), nrow =
  * length(mean)) is drawn by the R caller, so set.seed() keeps governing the draws. */
 SEXP gprc_R_mvn_sample(SEXP mean, SEXP covariance, SEXP tol, SEXP Z) {
@@ -360,6 +372,7 @@ static const R_CallMethodDef call_methods[] = {
     {"gprc_R_log_marginal", (DL_FUNC)&gprc_R_log_marginal, 5},
     {"gprc_R_fit_gradient", (DL_FUNC)&gprc_R_fit_gradient, 4},
     {"gprc_R_logp_grad", (DL_FUNC)&gprc_R_logp_grad, 5},
+    {"gprc_R_logq_grad", (DL_FUNC)&gprc_R_logq_grad, 5},
     {"gprc_R_mvn_sample", (DL_FUNC)&gprc_R_mvn_sample, 4},
     {"gprc_R_combine_all", (DL_FUNC)&gprc_R_combine_all, 2},
     {"gprc_R_device_count", (DL_FUNC)&gprc_R_device_count, 0},

@@ -197,6 +197,22 @@ GPRC_API int gprc_gpc_predict_class(gprc_model* model, const double* X_star, int
 GPRC_API int gprc_class_probability(gprc_ctx* ctx, const double* fs_bar, const double* Vfs, int64_t n, double* prob_out);
 GPRC_API int gprc_gpc_get_f_hat(gprc_model* model, double* f_hat_out);
 GPRC_API int gprc_gpc_get_logq(gprc_model* model, double* logq_out);
+/* The Laplace approximation of the log evidence, log q(y | X, theta), and its exact gradient with respect to the kernel parameters
+ * (Rasmussen & Williams, Algorithm 5.1, logistic likelihood, y in {-1, +1}; no reference counterpart).  The mode f_hat is found by the
+ * loop of gprc_gpc_fit with flags = 0: from f = 0 until |delta objective| < epsilon; max_iter <= 0 selects 1000, GPRC_ERR_MAXITER when
+ * the cap is reached; *iters_out (may be NULL) = iterations used.  With a = K^-1 f_hat, B = I + sqrt(W) K sqrt(W) = L L^T:
+ *   *logq_out = -1/2 a.f_hat + sum_i log sigmoid(y_i f_hat_i) - sum_i log L_ii
+ * This is the TRUE Laplace evidence (the LOG of the factor's diagonal), NOT what gprc_gpc_get_logq returns: that reproduces the
+ * reference's sum(diag(L)) (R/GPCclass.R:103) and is no objective.  For a model fitted with the same epsilon and flags = 0:
+ *   *logq_out = gprc_gpc_get_logq + sum_i L_ii - sum_i log L_ii.
+ * grad_out: n_params doubles in HOST memory, d log q / d params[i] in the ABI's parameter order (GPRC_SQREXP {l}; GPRC_GAMMAEXP
+ * {l, gamma}; GPRC_RATQUAD {l, alpha}; GPRC_SQREXP_ARD {l_1..l_d}); explicit and implicit (through f_hat) parts together.  The
+ * gradient is that of the converged mode: epsilon = 1e-10 is what the 1e-10 accuracy of the gradient needs (with GPC$new's default
+ * 1e-5 the mode can be one Newton step short: 2.6e-9 at n = 3000).  X, y: host or device pointers.
+ * The dense K, the factor, L^-1 and B^-1 are held whole on the device: about 3.5 * gprc_pad(n)^2 doubles (GPRC_ERR_NOMEM when that
+ * does not fit; gprc_ctx_trim releases the workspace part).  Other kernel ids, null outputs, epsilon <= 0: GPRC_ERR_ARG. */
+GPRC_API int gprc_gpc_logq_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                                const double* y, double epsilon, int max_iter, double* logq_out, double* grad_out, int* iters_out);
 
 /* ---- device-level building blocks (multi-GPU driver, bench) ------------------------------- *
  * All pointers below are DEVICE pointers on the context's GPU.  The factor lives in the packed
@@ -376,7 +392,8 @@ GPRC_API int gprc_combine_all(gprc_ctx* ctx, const double* axis_values, const in
  * When enabled, every launch is bracketed by two hipEvents on the stream it is launched on.  Kinds:
  * 0 fill, 1 potf2_inv, 2 trsm_panel, 3 in-panel GEMM (K=128), 4 trailing update, 5 predict right
  * update (K=512), 6 trsv, 7 row reductions, 8 covariance SYRK, 9 derivative row sums, 10 Jacobi sweep, 11 predict
- * left-looking update, 12 trailing left-looking update, 13 fused panel factorisation, 14 fused in-panel solve of the predict.  flops/bytes are the ALGORITHMIC
+ * left-looking update, 12 trailing left-looking update, 13 fused panel factorisation, 14 fused in-panel solve of the predict, 15 inverse GEMM
+ * (-L^-T L^-1, lower), 16 gradient contraction (gprc_gpr_logp_grad), 17 Laplace gradient contraction (gprc_gpc_logq_grad).  flops/bytes are the ALGORITHMIC
  * figures of DESIGN.md for the launches seen, not counter readings. */
 GPRC_API int gprc_prof_enable(int on);
 /* With the environment variable GPRC_PANEL_TRACE=<p> set, the factor role of the fused panel kernel of panel p leaves
