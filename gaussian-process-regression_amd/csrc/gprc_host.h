@@ -1,0 +1,176 @@
+// gprc_host.h -- what the units of the host layer (gprc_ctx, gprc_sched, gprc_model: see gprc_internal.h) share: the two
+// handle types, scoped device memory and argument staging, the schedules and the owner of a model.
+#pragma once
+#include <atomic>
+#include <cstdio>
+#include <memory>
+#include <vector>
+
+#include "gprc_internal.h"
+
+constexpr int SVC_TRACE_PANELS = 48;
+
+struct gprc_ctx {
+  uint64_t id = 0;             // unique per context ever created: a model remembers (pointer, id), so a LATER context at the same address is not mistaken for its own
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int* info_dev = nullptr;     // LAPACK info written by the diagonal-block kernel
+  void* sync_dev = nullptr;    // 64 bytes of flags for the fused panel kernel (zeroed before every launch, stream-ordered)
+                               // + another 64 for launches on the look-ahead stream
+  // the factor service's persistent launch runs on a high-priority side stream beside the caller's kernels (factor_group_service)
+  hipStream_t side_stream = nullptr;
+  hipStream_t side_stream2 = nullptr;  // the shared service's second launch (the 4-wave roles) runs beside the first
+  void* svc_trace = nullptr;          // GPRC_SERVICE_TRACE: 16 stamps x SVC_TRACE_PANELS of the last factor-service sweep (measurement)
+  hipEvent_t ev_pool[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  unsigned ev_next = 0;
+  double* scal_dev = nullptr;  // 8 doubles of scalar results
+  size_t chunk_bytes = (size_t)40 << 30;  // budget for one K_star^T chunk (n* = n = 65536 in one piece: fewer, fuller launches)
+  // grow-only workspace slots (predict chunks): a multi-GiB hipMalloc/hipFree per call costs 100s of ms
+  double* ws[4] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t ws_cap[4] = {0, 0, 0, 0};
+  int64_t vt_pad = 0;                     // extra doubles in the chunk's leading dimension (keeps it off powers of two)
+  // Free-list of device blocks released by calls on this context (exact-size reuse).  fit() evaluates the same n
+  // dozens to hundreds of times; without it every dens(v) pays seven hipMalloc/hipFree pairs (each hipFree is a
+  // device-wide sync).  Reuse is safe without events: everything on a context runs on its one stream, in order.
+  struct Block { void* p; size_t bytes; };
+  std::vector<Block> pool;
+  size_t pool_bytes = 0;
+  size_t pool_cap = (size_t)16 << 30;     // GPRC_POOL_BYTES; blocks larger than the cap are never kept
+};
+
+enum ModelType { MODEL_GPR = 1, MODEL_GPC = 2 };
+
+struct gprc_model {
+  gprc_ctx* ctx = nullptr;
+  uint64_t ctx_id = 0;
+  int type = 0;
+  gprc::KernelSpec ks{};
+  int64_t n = 0, d = 0, n_pad = 0;
+  double* X = nullptr;       // d x n
+  double* y = nullptr;       // n_pad (zero padded)
+  double* packed = nullptr;  // factor, packed block columns
+  double* winv = nullptr;    // inverses of the 128x128 diagonal blocks
+  double* alpha = nullptr;   // n_pad (GPR) ; g = (y+1)/2 - P (GPC)
+  double* f_hat = nullptr;   // GPC
+  double* sw = nullptr;      // GPC sqrt(W)
+  double* work = nullptr;    // trsv partials
+  double logp = 0.0, noise = 0.0, logq = 0.0;
+  bool borrowed = false;     // X, y, packed, winv, alpha belong to the caller
+};
+
+namespace gprc {
+
+// ---- gprc_ctx.hip ------------------------------------------------------------------------------------
+int use_device(const gprc_ctx* ctx);   // hipSetDevice + whose pool the scoped temporaries below use (per host thread)
+int use_device_unless(const gprc_ctx* ctx, bool bad, const char* msg);   // ... then GPRC_ERR_ARG with msg if `bad`: an entry point's argument check
+bool ctx_alive(const gprc_ctx* c, uint64_t id);
+int pool_alloc(gprc_ctx* ctx, size_t bytes, void** out);
+void pool_release(gprc_ctx* ctx, void* p, size_t bytes);
+void pool_trim(gprc_ctx* ctx);
+bool is_device_ptr(const void* p);
+// workspace slot `slot` of the context, at least `count` doubles (contents undefined)
+int ws_get(gprc_ctx* ctx, int slot, int64_t count, double** out);
+
+struct DevMem {  // scoped device allocation from the current context's pool
+  double* p = nullptr;
+  gprc_ctx* owner = nullptr;
+  size_t bytes = 0;
+  ~DevMem() { if (p) pool_release(owner, p, bytes); }
+  int alloc(int64_t count);
+};
+struct IntMem {  // scoped int buffer, straight from the driver (not pooled)
+  int* p = nullptr;
+  ~IntMem() { if (p) (void)hipFree(p); }
+};
+// Input staging: device pointers pass through, host arrays are copied to a temporary.
+struct In {
+  const double* dev = nullptr;
+  DevMem tmp;
+  int set(hipStream_t s, const double* p, int64_t count) {
+    if (count <= 0) { dev = nullptr; return 0; }
+    if (!p) { set_error("null input pointer"); return GPRC_ERR_ARG; }
+    if (is_device_ptr(p)) { dev = p; return 0; }
+    GPRC_TRY(tmp.alloc(count));
+    GPRC_HIP(hipMemcpyAsync(tmp.p, p, tmp.bytes, hipMemcpyHostToDevice, s));
+    dev = tmp.p;
+    return 0;
+  }
+};
+// Output staging: device pointers are written in place; host arrays get a temporary + D2H at finish().  The matrix form (rows x
+// cols): a device pointer keeps the caller's leading dimension, a host array gets a compact temporary (ld = rows) that finish() copies
+// back with the caller's pitch, so rows beyond `rows` of the caller's array are never touched.
+struct Out {
+  double* dev = nullptr;
+  DevMem tmp;
+  double* host = nullptr;
+  int64_t ld = 0, ld_host = 0, cols = 0;   // matrix form only
+  int set(double* p, int64_t cnt) {
+    if (cnt <= 0) return 0;
+    if (!p) { set_error("null output pointer"); return GPRC_ERR_ARG; }
+    if (is_device_ptr(p)) { dev = p; return 0; }
+    host = p;
+    GPRC_TRY(tmp.alloc(cnt));
+    dev = tmp.p;
+    return 0;
+  }
+  int set(double* p, int64_t ld_out, int64_t rows, int64_t ncols) {   // rows, ncols >= 1: callers return early for an empty matrix
+    dev = p; ld = ld_out;
+    if (is_device_ptr(p)) return 0;
+    host = p; ld_host = ld_out; cols = ncols;
+    GPRC_TRY(tmp.alloc(rows * ncols));
+    dev = tmp.p; ld = rows;
+    return 0;
+  }
+  int finish(hipStream_t s) {
+    if (cols) GPRC_HIP(hipMemcpy2DAsync(host, sizeof(double) * ld_host, tmp.p, sizeof(double) * ld, sizeof(double) * ld, cols, hipMemcpyDeviceToHost, s));
+    else if (host) GPRC_HIP(hipMemcpyAsync(host, tmp.p, tmp.bytes, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+};
+
+// the end of an entry point: host outputs are copied back, then the stream is waited for
+inline int finish_sync(hipStream_t s, Out& a, Out* b = nullptr) {
+  GPRC_TRY(a.finish(s));
+  if (b) GPRC_TRY(b->finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- gprc_sched.hip ----------------------------------------------------------------------------------
+extern std::atomic<bool> g_service_off;
+int factor_subpanel(gprc_ctx* ctx, double* packed, int64_t n_pad, int64_t p, int j, int part, double* winv, int* info_dev);
+int factor_panel(gprc_ctx* ctx, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev);
+int factor_all_async(gprc_ctx* ctx, double* packed, int64_t n_pad, double* winv, int* info_dev, double* inv, bool* used_service = nullptr);
+int factor_all(gprc_ctx* ctx, double* packed, int64_t n_pad, double* winv, int* info_host, double* inv = nullptr, bool* used_service = nullptr);
+int solve_rows(gprc_ctx* ctx, const double* packed, const double* winv, int64_t n_pad, double* vt, int64_t ldv, int64_t m_pad,
+               double* sspart = nullptr, int64_t tri_row0 = -1, int64_t p_end = -1);
+bool identity_solve_dense();
+int64_t predict_partials(int64_t n_pad);
+int chunk_workspace(gprc_ctx* ctx, int64_t n_pad, int64_t ns, bool want_tmp, int64_t* rows_out, double** vt, double** part, double** tmp);
+
+// factor_all for callers that can rebuild the matrix.  If THIS call ran under the factor service and a device-side wait timed out
+// (see g_service_off), the service is switched off for the process (with one line on stderr: it is a permanent change of schedule),
+// the matrix is rebuilt (refill) and factored again with one fused launch per panel.  Decided per call, not once per process: two
+// host threads that time out in the same window (each with its own context) both retry.
+template <class Refill>
+int factor_all_or_refill(gprc_ctx* ctx, double* packed, int64_t n_pad, double* winv, int* info_host, double* inv, Refill refill) {
+  bool used_service = false;
+  int rc = factor_all(ctx, packed, n_pad, winv, info_host, inv, &used_service);
+  if (rc == GPRC_ERR_HIP && *info_host == GPRC_INFO_WAIT_TIMEOUT && used_service) {
+    if (!g_service_off.exchange(true))
+      std::fprintf(stderr, "gprc: a device-side wait of the factor service timed out (kernels of two streams did not run concurrently, e.g. under "
+                           "rocprofv3 --pmc); the service is now OFF for this process and the factorisation is repeated with one launch per panel\n");
+    GPRC_TRY(refill());
+    rc = factor_all(ctx, packed, n_pad, winv, info_host, inv);
+  }
+  return rc;
+}
+
+// ---- gprc_model.hip ----------------------------------------------------------------------------------
+int make_spec(int kernel, const double* params, int n_params, int64_t d, KernelSpec* ks);
+void free_model(gprc_model* m);
+struct ModelFree { void operator()(gprc_model* m) const { free_model(m); } };
+using ModelPtr = std::unique_ptr<gprc_model, ModelFree>;   // owns a model: every return frees it unless release() has handed it on
+
+}  // namespace gprc

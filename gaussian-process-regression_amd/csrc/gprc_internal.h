@@ -1,5 +1,11 @@
 // gprc_internal.h -- shared declarations of the gfx950 implementation behind include/gprc_native.h.
-// Host-side launchers live next to their kernels; the C ABI (gprc_api.hip) only composes them.
+// Host-side launchers live next to their kernels; the host layer only composes them, one unit per job (shared types: gprc_host.h):
+//   gprc_ctx.hip    errors, the event profiler, context lifetime, the block pool, workspace slots, argument staging, and the entry
+//                   points that are only staging around one launcher (kernel matrices, class probabilities, combine_all)
+//   gprc_sched.hip  the factor and solve schedules, chunk workspaces, every schedule knob of the host layer; the layout helpers and
+//                   the gprc_dev_* building blocks
+//   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
+//   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,9 +24,9 @@ constexpr int NBI = 128;  // inner block: one LDS-resident diagonal factorisatio
 constexpr int TPP = NB / NBI;  // 128-wide tile columns per panel
 constexpr int MAX_PARAMS = 256;  // kernel parameters travel as kernel arguments; only linear's per-coordinate sigma needs more than 2
 constexpr int MAX_DEVICES = 64;  // per-device one-time setup flags
-// written to the LAPACK-info word by a fused kernel whose device-side dependency wait ran out (never seen in practice:
-// it takes a faulted or never-scheduled producer); hosts turn it into GPRC_ERR_HIP instead of using the factor
-// GPRC_INFO_WAIT_TIMEOUT (-99, include/gprc_native.h): what info becomes when a device-side dependency wait runs out
+// GPRC_INFO_WAIT_TIMEOUT (-99, include/gprc_native.h): written to the LAPACK-info word by a fused kernel whose device-side dependency
+// wait ran out (never seen in practice: it takes a faulted or never-scheduled producer); hosts turn it into GPRC_ERR_HIP instead of
+// using the factor
 static_assert(NB % NBI == 0 && NB >= NBI, "panel width must be a multiple of the 128 block");
 
 __host__ __device__ static inline int64_t pad_up(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
@@ -111,11 +117,11 @@ int launch_trsm_panel(hipStream_t s, double* X, int64_t ldx, int64_t M, const do
 // kind PK_INV_GEMM (square, lower, A and B upper triangular): the tile of row tile r starts its products at column r 128
 int launch_gemm_nt(hipStream_t s, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
                    int64_t M, int64_t N, int64_t K, int lower, int kind);
-// trailing update of packed panels q_begin, q_begin+q_stride, ... < q_end with factored panel p
 // left-looking predict-solve step: vt[:, j NB:(j+G) NB] -= vt[:, 0:j NB] * L[j NB:(j+G) NB, 0:j NB]^T   (L packed)
 // tri_row0 >= 0: the rows of vt are rows tri_row0.. of the identity (zero left of their own column): per tile the pass starts there
 int launch_solve_left(hipStream_t s, double* vt, int64_t ldv, int64_t m_pad, const double* packed, int64_t n_pad, int64_t j, int64_t G,
                       int64_t tri_row0 = -1);
+// trailing update of packed panels q_begin, q_begin+q_stride, ... < q_end with factored panel p
 int launch_trailing_update(hipStream_t s, double* packed, int64_t n_pad, int64_t p, int64_t q_begin, int64_t q_end,
                            int64_t q_stride);
 // factor service (one-GPU right-looking sweep): the dependent chain of all panels in one persistent launch (side stream) + per panel
