@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
 
 #include "../../include/gprc_native.h"
@@ -32,6 +33,13 @@ static_assert(NB % NBI == 0 && NB >= NBI, "panel width must be a multiple of the
 __host__ __device__ static inline int64_t pad_up(int64_t n, int64_t m) { return (n + m - 1) / m * m; }
 __host__ __device__ static inline int64_t panel_offset(int64_t n_pad, int64_t p) { return (int64_t)NB * (p * n_pad - (int64_t)NB * p * (p - 1) / 2); }
 __host__ __device__ static inline int64_t panel_ld(int64_t n_pad, int64_t p) { return n_pad - p * NB; }
+// lower 128 x 128 tiles of packed panel q of P: TPP x TPP per NB rows, less the upper tiles of the diagonal block
+template <typename T>
+__host__ __device__ constexpr T panel_tiles(T P, T q) { return TPP * TPP * (P - q) - TPP * (TPP - 1) / 2; }
+// The factor service's resident workgroups (kernels_chol.hip, a CU each): SERVICE_CORE_WGS roles on the chain and around it, TPP more
+// when it also forms the explicit inverses, CHAIN_HELPERS more with the split chain.
+constexpr int SERVICE_CORE_WGS = 3 + TPP + TPP * (TPP + 1) / 2;
+constexpr int CHAIN_HELPERS = 4;                  // 32-row slices of a 128-row block
 
 // ---- error plumbing ---------------------------------------------------------------------------
 void set_error(const std::string& msg);
@@ -49,6 +57,20 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
   } while (0)
 #define GPRC_LAUNCH_CHECK() GPRC_HIP(hipGetLastError())
 
+// Raises Kernel's dynamic-LDS limit to `bytes` (its one launch configuration) once per device: the attribute is per device, one process
+// may hold contexts on several, and several host threads may launch at once (a second thread that also sets it does no harm).
+template <auto Kernel>
+int ensure_dynamic_lds(size_t bytes) {
+  static std::atomic<bool> set[MAX_DEVICES];
+  int dev = 0;
+  GPRC_HIP(hipGetDevice(&dev));
+  const bool known = dev >= 0 && dev < MAX_DEVICES;
+  if (known && set[dev].load(std::memory_order_acquire)) return 0;
+  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (known) set[dev].store(true, std::memory_order_release);
+  return 0;
+}
+
 // ---- in-library event profiler (bench.py's live roofline numbers) ---------------------------------
 enum ProfKind { PK_FILL = 0, PK_POTF2 = 1, PK_TRSM_PANEL = 2, PK_GEMM_INNER = 3, PK_TRAILING = 4, PK_SOLVE_UPDATE = 5,
                 PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_INV_GEMM = 15, PK_GRAD_CONTRACT = 16, PK_GPC_GRAD_CONTRACT = 17, PK_COUNT = 18 };
@@ -62,6 +84,17 @@ struct ProfScope {  // brackets one launch (or one launch sequence) with a pair 
   }
   ~ProfScope() { if (on) prof_end(s, kind, flops, bytes); }
 };
+
+// algorithmic flops and bytes of a trailing update: the lower triangle of the NB-wide diagonal block + everything below it of the target
+// panels q0, q0 + stride, ... < q1, K source columns deep; skip_first_diag: without the first target's diagonal block (the factor service's)
+inline void trailing_work(int64_t n_pad, int64_t q0, int64_t q1, int64_t stride, double K, bool skip_first_diag, double& fl, double& by) {
+  for (int64_t q = q0; q < q1; q += stride) {
+    const double rows = (double)(n_pad - q * NB);
+    const double elems = rows * NB - 0.5 * NB * (double)(NB - 1) - (skip_first_diag && q == q0 ? 0.5 * NB * (double)(NB + 1) : 0.0);
+    fl += 2.0 * elems * K;
+    by += 8.0 * (2.0 * elems + rows * K);
+  }
+}
 
 struct KernelSpec {
   int id;
@@ -102,12 +135,7 @@ int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, i
 int launch_gpc_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* a, const double* sw,
                              const double* u, const double* g, const double* W, int64_t ld, double* part);
 
-// ---- launchers (kernels_chol.hip) --------------------------------------------------------------
-// factor the 128x128 diagonal block at A (ld) in LDS, write L in place and its inverse to winv
-int launch_potf2_inv(hipStream_t s, double* A, int64_t lda, double* winv, int* info_dev, int col0);
-// the whole of panel p (four diagonal blocks, panel solves, in-panel updates) in ONE launch; sync16: 64 bytes of device
-// memory the launch may use for its flags (zeroed by the launcher, stream-ordered: one buffer serves a whole stream)
-int launch_panel_fused(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync16);
+// ---- launchers (kernels_gemm.hip: no flags between workgroups) ---------------------------------
 // the predict's in-panel solve of panel p in one launch (see solve_panel_fused_kernel)
 int launch_solve_panel_fused(hipStream_t s, double* vt, int64_t ldv, int64_t m_pad, const double* packed, int64_t n_pad, int64_t p,
                              const double* winv, double* sspart, int64_t ss_stride = 0);   // ss_stride: rows per block of sspart (0: m_pad)
@@ -124,26 +152,32 @@ int launch_solve_left(hipStream_t s, double* vt, int64_t ldv, int64_t m_pad, con
 // trailing update of packed panels q_begin, q_begin+q_stride, ... < q_end with factored panel p
 int launch_trailing_update(hipStream_t s, double* packed, int64_t n_pad, int64_t p, int64_t q_begin, int64_t q_end,
                            int64_t q_stride);
+// ... with the source panels [p_begin, p_end) in one pass (p_begin = 0, p_end = q_begin: the left-looking update of a group)
+int launch_trailing_range(hipStream_t s, double* packed, int64_t n_pad, int64_t p_begin, int64_t p_end, int64_t q_begin, int64_t q_end,
+                          int64_t q_stride);
+
+// ---- launchers (kernels_chol.hip: PanelSync flags, the wait records) --------------------------
+// (what they are told -- trace, split, part, forced, wgs, core, head_slices -- is decided in gprc_sched.hip)
+// factor the 128x128 diagonal block at A (ld) in LDS, write L in place and its inverse to winv
+int launch_potf2_inv(hipStream_t s, double* A, int64_t lda, double* winv, int* info_dev, int col0);
+// the whole of panel p (four diagonal blocks, panel solves, in-panel updates) in ONE launch; sync16: 64 bytes of device
+// memory the launch may use for its flags (zeroed by the launcher, stream-ordered: one buffer serves a whole stream)
+int launch_panel_fused(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync16, int trace);
 // factor service (one-GPU right-looking sweep): the dependent chain of all panels in one persistent launch (side stream) + per panel
 // the ordinary strips and the trailing update without the next diagonal block (caller's stream)
 size_t panel_service_sync_bytes(int64_t P);
 int launch_panel_service(hipStream_t s, double* packed, int64_t n_pad, double* winv, int* info_dev, void* sync, void* trace, double* inv,
-                         int64_t p_begin, int64_t p_end, int part = 0);
-bool service_shared(int64_t n_pad);   // the service's 4-wave roles share their CUs with one sweep workgroup each (two launches: parts 1 and 2)
+                         int64_t p_begin, int64_t p_end, bool split, int part);
 // inv (n_pad x NB doubles): per panel the explicit inverse of its NB x NB diagonal block, transposed -- what the vector solves use
 int launch_inv512(hipStream_t s, const double* packed, int64_t n_pad, const double* winv, double* inv, int64_t p_begin, int64_t p_end);
-int launch_service_gate(hipStream_t s, int64_t n_pad, int* info_dev, void* sync, int launches);
+int launch_service_gate(hipStream_t s, int64_t n_pad, int* info_dev, void* sync, int launches, bool forced);
 int launch_panel_strips(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync, void* trace);
 int launch_trailing_service(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync, void* trace, int64_t q_end);
 int launch_trailing_sweep(hipStream_t s, double* packed, int64_t n_pad, int64_t g0, int64_t g1, double* winv, int* info_dev, void* sync, void* trace,
-                          int service_wgs);
-int service_workgroups(bool with_inverse, int64_t n_pad);
-std::string wait_timeout_report();   // who gave up first in the last timed-out factorisation (kernels_chol.hip), "" if nobody
+                          int wgs, int core, int head_slices);
+std::string wait_timeout_report();   // who gave up first in the last timed-out factorisation, "" if nobody
 
 // ---- launchers (kernels_vec.hip) ---------------------------------------------------------------
-int launch_trailing_left(hipStream_t s, double* packed, int64_t n_pad, int64_t q_begin, int64_t q_end);
-int launch_trailing_range(hipStream_t s, double* packed, int64_t n_pad, int64_t p_begin, int64_t p_end, int64_t q_begin, int64_t q_end,
-                          int64_t q_stride);
 // vector solves: inv = the explicit diagonal-block inverses (launch_inv512 / the factor service), work = gprc_trsv_work_size doubles
 int launch_trsv_step(hipStream_t s, const double* packed, const double* inv, int64_t n_pad, double* b, int transpose, int p, double* work);
 int launch_trsv(hipStream_t s, const double* packed, const double* inv, int64_t n_pad, double* b, int transpose, double* work);

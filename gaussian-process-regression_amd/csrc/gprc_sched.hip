@@ -1,7 +1,9 @@
 // gprc_sched.hip -- the host-side schedules: which launchers run in which order for a factorisation (factor_subpanel .. factor_all)
 // and a triangular solve of many rows (solve_rows), and how a pass over test points is chunked (chunk_workspace).  Every schedule
 // knob of the host layer (GPRC_FACTOR, GPRC_SOLVE, GPRC_PANEL, GPRC_SERVICE, GPRC_SWEEP, GPRC_SOLVE_PANEL, GPRC_SERVICE_TRACE,
-// GPRC_FITGRAD_DENSE, GPRC_IGNORE_MEMINFO) is read in this file and nowhere else.  Its C entry points: the layout helpers and the
+// GPRC_FITGRAD_DENSE, GPRC_IGNORE_MEMINFO) and of the factor's launchers (GPRC_CHAIN_SPLIT, GPRC_SERVICE_SHARE, GPRC_SWEEP_WGS,
+// GPRC_HEAD_SLICES, GPRC_PANEL_TRACE, GPRC_POTF2_TRACE, GPRC_TEST_SERVICE_TIMEOUT: kernels_chol.hip takes what they decide as launch
+// parameters) is read in this file and nowhere else.  Its C entry points: the layout helpers and the
 // gprc_dev_* building blocks (the schedules themselves and the single launchers a caller composes with them), the two trace read-backs.
 #include <algorithm>
 #include <cstdlib>
@@ -41,8 +43,12 @@ int factor_subpanel(gprc_ctx* ctx, double* packed, int64_t n_pad, int64_t p, int
 
 // The whole panel: ONE launch (panel_fused_kernel: the four sub-steps overlap across row strips, dependencies carried by
 // device-side flags), bit-identical to the twelve launches of the sub-step form.  GPRC_PANEL=steps selects the latter.
+// GPRC_PANEL_TRACE=<p>: the factor role of panel p stamps its stages (read back with gprc_prof_panel_trace); with GPRC_POTF2_TRACE the
+// stamps are those of the SECOND diagonal block's potf2 instead.  Measurement only.
 int factor_panel(gprc_ctx* ctx, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev) {
-  if (!panel_steps()) return launch_panel_fused(ctx->stream, packed, n_pad, p, winv, info_dev, ctx->sync_dev);
+  static const long long trace_p = [] { const char* e = std::getenv("GPRC_PANEL_TRACE"); return e ? std::atoll(e) : -1LL; }();
+  static const int trace_mode = std::getenv("GPRC_POTF2_TRACE") != nullptr ? 2 : 1;
+  if (!panel_steps()) return launch_panel_fused(ctx->stream, packed, n_pad, p, winv, info_dev, ctx->sync_dev, trace_p == p ? trace_mode : 0);
   for (int j = 0; j < NB / NBI; ++j) GPRC_TRY(factor_subpanel(ctx, packed, n_pad, p, j, 0, winv, info_dev));
   return 0;
 }
@@ -72,6 +78,54 @@ static bool service_carries_inverse(int64_t n_pad) {
   return n_pad < 20480;   // measured (profiles/r03_experiments.txt): no difference up to 20480 (+0.5 % there without)
 }
 
+// The split chain (four more resident CUs) where the panel chain weighs: below n_pad = 20480, i.e. wherever the whole matrix is ONE group
+// of the service (measured, same box, profiles/r03_chain_split.txt; in the grouped schedule beyond it makes no difference and the four
+// CUs stay with the update).  GPRC_CHAIN_SPLIT=0 / 1 forces it off / on at every size.
+static bool chain_split(int64_t n_pad) {
+  static const int v = [] { const char* e = std::getenv("GPRC_CHAIN_SPLIT"); return e ? std::atoi(e) : -1; }();
+  return v >= 0 ? v != 0 : n_pad < 20480;
+}
+
+// The SHARED service.  A service workgroup asks for the factor role's 149 KB of LDS, so nothing else fits on its CU -- 21 to 25 CUs
+// that, where the update is the bound, mostly sleep on their flags.  From n_pad = 13312 on, the 4-wave roles (all but the factor role and
+// the chain helpers, whose 8 waves x 256 VGPRs fill a CU) are launched on their own, on a second side stream, with a GEMM team's LDS only
+// (launch_panel_service, part 2): ONE sweep workgroup then fits beside each of them and has the CU's matrix cores while the role waits.
+// Measured, same box (profiles/r03_chain_split.txt): n = 14336 19.45 -> 19.07 ms, 16384 27.3 -> 26.4, 18432 37.55 -> 35.97, 24576
+// 79.7 -> 78.9, 32768 172.5 -> 170.4, 65536 unchanged; 12288 and below unchanged or slower (the chain's own tiles run at half rate
+// beside a busy sweep workgroup), hence the threshold.  Raising the roles' wave priority (s_setprio 3) changes nothing measurable; it
+// stays.  GPRC_SERVICE_SHARE=0 / 1 forces it off / on (from n_pad = 10752, where the sweep runs two workgroups per CU).
+static bool service_shared(int64_t n_pad) {
+  static const int v = [] { const char* e = std::getenv("GPRC_SERVICE_SHARE"); return e ? std::atoi(e) : -1; }();
+  return n_pad >= 10752 && (v >= 0 ? v != 0 : n_pad >= 13312);
+}
+
+// workgroups the service keeps resident (a CU each)
+static int service_workgroups(bool with_inverse, int64_t n_pad) {
+  return SERVICE_CORE_WGS + (with_inverse ? TPP : 0) + (chain_split(n_pad) ? CHAIN_HELPERS : 0);
+}
+
+// The persistent sweep of a group (launch_trailing_sweep): its workgroups, its tile loop, and whether its head tiles go in slices.
+static int launch_group_sweep(gprc_ctx* ctx, double* packed, int64_t n_pad, int64_t g0, int64_t g1, double* winv, int* info_dev, void* sync, void* trace,
+                              int service_wgs) {
+  int dev = 0, cus = 0;
+  GPRC_HIP(hipGetDevice(&dev));
+  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  // Two workgroups per CU the service leaves free (all co-resident) -- except below n_pad = 10752, where the panel chain is the bound and
+  // what counts is how quickly a tile the chain waits for is done: ONE workgroup per CU has the CU's MFMA pipes to itself
+  // (measured, same box: n = 8192 6.28 -> 5.99 ms, 10240 9.44 -> 9.21; 12288 13.55 -> 14.60: profiles/r03_factor_schedules.txt).
+  // GPRC_SWEEP_WGS=<n> overrides.
+  static const int wgs_env = [] { const char* e = std::getenv("GPRC_SWEEP_WGS"); return e ? std::atoi(e) : 0; }();
+  const int per_cu = n_pad < 10752 ? 1 : 2;
+  // shared service: the resident 4-wave roles' CUs take ONE sweep workgroup each beside the role
+  const int shared = service_shared(n_pad) ? service_wgs - 1 - (chain_split(n_pad) ? CHAIN_HELPERS : 0) : 0;
+  const int wgs = wgs_env > 0 ? wgs_env : std::max(8, per_cu * (cus - service_wgs) + shared);
+  // The tile loop: 2 (no VALU instruction in the loop) where ONE workgroup has the CU; 1 (the first interleaved loop) where two share it:
+  // there the faster tile costs 5-8 % (chol_tile.h, trailing_sweep_kernel: profiles/r03_chain_split.txt).
+  const int core = (per_cu == 1 && wgs_env <= 0) ? 2 : 1;
+  static const int head_slices = [] { const char* e = std::getenv("GPRC_HEAD_SLICES"); return e ? std::atoi(e) : 1; }();   // 0: whole head tiles (A/B switch)
+  return launch_trailing_sweep(ctx->stream, packed, n_pad, g0, g1, winv, info_dev, sync, trace, wgs, core, core == 2 ? head_slices : 0);
+}
+
 // One GROUP of panels [g0, g1) with the FACTOR SERVICE (kernels_chol.hip): the group's columns have received every earlier panel
 // (left-looking pass, or g0 = 0); inside the group the sweep is right-looking with the whole dependent chain -- diagonal blocks, the
 // strips around them, the rows of the next diagonal block and that block's update -- in ONE persistent 21-workgroup launch on a side
@@ -85,15 +139,18 @@ static int factor_group_service(gprc_ctx* ctx, double* packed, int64_t n_pad, do
   // The explicit inverses ride in the service (four more resident workgroups, off the chain) below n_pad = 20480, where the whole
   // matrix is one group; in the grouped schedule beyond, one launch after the sweep computes them (factor_all_async) and the four
   // CUs go to the update.
-  const bool shared = service_shared(n_pad);
+  const bool shared = service_shared(n_pad), split = chain_split(n_pad);
   if (shared) {
     hipStream_t side2 = ctx->side_stream2;
     GPRC_TRY(stream_after(ctx, side2, s));
-    GPRC_TRY(launch_panel_service(side, packed, n_pad, winv, info_dev, sync, trace, service_carries_inverse(n_pad) ? inv : nullptr, g0, g1, 1));
-    GPRC_TRY(launch_panel_service(side2, packed, n_pad, winv, info_dev, sync, trace, service_carries_inverse(n_pad) ? inv : nullptr, g0, g1, 2));
+    GPRC_TRY(launch_panel_service(side, packed, n_pad, winv, info_dev, sync, trace, service_carries_inverse(n_pad) ? inv : nullptr, g0, g1, split, 1));
+    GPRC_TRY(launch_panel_service(side2, packed, n_pad, winv, info_dev, sync, trace, service_carries_inverse(n_pad) ? inv : nullptr, g0, g1, split, 2));
   } else
-  GPRC_TRY(launch_panel_service(side, packed, n_pad, winv, info_dev, sync, trace, service_carries_inverse(n_pad) ? inv : nullptr, g0, g1));
-  GPRC_TRY(launch_service_gate(s, n_pad, info_dev, sync, launches));   // nothing that waits on the service starts before the service is resident
+  GPRC_TRY(launch_panel_service(side, packed, n_pad, winv, info_dev, sync, trace, service_carries_inverse(n_pad) ? inv : nullptr, g0, g1, split, 0));
+  // GPRC_TEST_SERVICE_TIMEOUT=1 (test hook): the FIRST gate of the process waits for a residency count that cannot be reached and
+  // gives up at once -- the timeout / refill / service-off path of the fit entry points without a profiler.
+  static std::atomic<bool> fire{std::getenv("GPRC_TEST_SERVICE_TIMEOUT") != nullptr};
+  GPRC_TRY(launch_service_gate(s, n_pad, info_dev, sync, launches, fire.exchange(false)));   // nothing that waits on the service starts before the service is resident
   GPRC_TRY(launch_panel_strips(s, packed, n_pad, g0, winv, info_dev, sync, trace));        // the later panels' strips ride in the update kernels
   // (Round 3 measured a batched form of this loop -- panel s applied at once only to the next B + 1 panels, the batch's B panels
   //  to everything further in ONE K = 512 B pass, bit-identical -- and it was SLOWER at every size: n = 16384 29.9 -> 31.6 / 30.9 /
@@ -105,7 +162,7 @@ static int factor_group_service(gprc_ctx* ctx, double* packed, int64_t n_pad, do
   if (per_panel) {
     for (int64_t p = g0; p + 1 < g1; ++p) GPRC_TRY(launch_trailing_service(s, packed, n_pad, p, winv, info_dev, sync, trace, g1));
   } else {
-    GPRC_TRY(launch_trailing_sweep(s, packed, n_pad, g0, g1, winv, info_dev, sync, trace, service_workgroups(service_carries_inverse(n_pad) && inv, n_pad)));
+    GPRC_TRY(launch_group_sweep(ctx, packed, n_pad, g0, g1, winv, info_dev, sync, trace, service_workgroups(service_carries_inverse(n_pad) && inv, n_pad)));
   }
   GPRC_TRY(stream_after(ctx, s, side));
   if (shared) GPRC_TRY(stream_after(ctx, s, ctx->side_stream2));
@@ -114,7 +171,7 @@ static int factor_group_service(gprc_ctx* ctx, double* packed, int64_t n_pad, do
 
 // All panels of a packed matrix on one GPU, asynchronously (info stays on the device).  Schedule: the panels are taken
 // in GROUPS; before a group is factored its panels receive the contributions of every earlier panel in one
-// left-looking pass (trailing_left_kernel, K = g0 NB, C tile held in the accumulators); inside the group the panels
+// left-looking pass (trailing_range_kernel, K = g0 NB, C tile held in the accumulators); inside the group the panels
 // update each other right-looking.  Bit-identical to the plain right-looking sweep (same products, same order).  A
 // group is the shortest run of panels whose lower tiles number >= 8192: a left-looking tile is long (K / 512 x 110 us),
 // so a pass needs many generations of tiles per CU or the partially filled last one costs more than the saved
@@ -157,8 +214,8 @@ int factor_all_async(gprc_ctx* ctx, double* packed, int64_t n_pad, double* winv,
   auto sweep = [&]() -> int {
     for (int64_t g0 = 0; g0 < P;) {
       int64_t g1 = g0, tiles = 0;
-      while (g1 < P && tiles < want) { tiles += (int64_t)TPP * TPP * (P - g1) - TPP * (TPP - 1) / 2; ++g1; }
-      GPRC_TRY(launch_trailing_left(s, packed, n_pad, g0, g1));
+      while (g1 < P && tiles < want) { tiles += panel_tiles(P, g1); ++g1; }
+      GPRC_TRY(launch_trailing_range(s, packed, n_pad, 0, g0, g0, g1, 1));   // left-looking: every panel before the group, into the group
       if (service) {
         GPRC_TRY(factor_group_service(ctx, packed, n_pad, winv, info_dev, inv, g0, g1, sync.p, trace, ++launches));
       } else {

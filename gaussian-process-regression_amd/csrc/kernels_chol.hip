@@ -1,1045 +1,22 @@
-// kernels_chol.hip -- blocked right-looking fp64 Cholesky pieces for gfx950 (MI355X).
-//
-// Replaces L <- t(chol(K + noise * diag(n)))  (reference R/GPRclass.R:142, LAPACK dpotrf) and, through
-// the same GEMM tile, v <- solve(L, K_star) (R/GPRclass.R:162, which the reference runs as a general
-// pivoted dgesv).  The pieces:
-//   potf2_blocked_body  one workgroup factors a 128x128 diagonal block entirely in LDS and also forms
-//                     its inverse (so every panel / right-hand-side solve below is a GEMM);
-//   gemm tile core    128x128 output tile per 256-thread workgroup, 4 waves x (64x64) of
-//                     v_mfma_f64_16x16x4_f64, A/B strips staged through double-buffered LDS;
-//   wrappers          panel solve (X := X * Winv^T, in place), in-panel / general C -= A*B^T, and the
-//                     trailing update over the packed block-column layout (lower tiles only);
-//   panel_fused_kernel / panel_service_kernel   a whole panel's dependent chain in one launch / every panel's in one
-//                     persistent launch (the factor service), with the caller's-stream kernels that go with it.
-// The trailing update is the dominant kernel of the whole path: n^3/3 of the fit and n^2 n* of the
-// predict go through gemm_tile_128().
+// kernels_chol.hip -- the fp64 Cholesky's kernels that hand work over BETWEEN workgroups through agent-scope flags and counters
+// (PanelSync), each with its launcher, and the records their bounded waits leave when one gives up (g_wait_diag: one home, the library
+// is built without relocatable device code -- every kernel that can record a wait sits in this unit beside the host functions that
+// read the records).  panel_fused_kernel: a whole panel's dependent chain in one launch; panel_service_kernel: every panel's in one
+// persistent launch (the factor service), with the caller's-stream kernels that go with it (service gate, strips, trailing update per
+// panel or as one persistent sweep); the explicit inverse of a panel's diagonal block, a role of the service and a kernel of its own.
+// Tile core and diagonal-block factorisation: chol_tile.h.  Which of these run, and with which parameters: gprc_sched.hip.
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
-#include <utility>
+#include <mutex>
 
-#include "gprc_internal.h"
+#include "chol_tile.h"
 
 namespace gprc {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// ------------------------------------------------------------------------------------------------
-// Diagonal block: Cholesky + inverse of a 128 x 128 block in one sweep by one workgroup.
-// ------------------------------------------------------------------------------------------------
-constexpr int PB = 128;
-
-// ------------------------------------------------------------------------------------------------
-// Blocked diagonal-block kernel (default): the same factor + inverse, 16 columns at a time.
-// The 128 x 128 block lives in LDS (leading dimension 144: MFMA operand reads conflict-free).  Per 16-column step:
-//   A  wave 0 factors the 16 x 16 diagonal sub-block and inverts it with a register-resident scalar sweep (diag16:
-//      16 sequential pivots, a matrix row per lane, operands exchanged inside the 16-lane row by DPP row_newbcast; sqrt /
-//      reciprocal from a Newton-refined v_rsq_f64 -- ~60 dependent cycles instead of the ~600 of the library
-//      sqrt + division);
-//   B  panel rows below: X_I = A_I * Wd^T, and row s of the inverse: X_sJ = Wd * Y_sJ   (4 MFMAs per 16x16 block);
-//   C  Cholesky trailing blocks C_IJ -= X_I X_J^T and inverse blocks Y_IJ -= L_Is X_sJ  (4 MFMAs per block); wave 0
-//      updates the next diagonal block first and runs phase A of step s+1 beside the other waves' blocks,
-// one barrier after B and one after C.  L is kept in the lower triangle, the (unscaled-free) inverse transposed in the
-// upper triangle, its diagonal in a side array -- the layout of the output.  The sequential depth drops from 128
-// whole-workgroup steps to 128 single-wave steps on 16-row data.
-// ------------------------------------------------------------------------------------------------
-constexpr int BLD = 144;
-constexpr int PB_SMEM_DOUBLES = PB * BLD + 512 + PB;  // S, 2 x Wd, Wdiag
-
-// sqrt(d) and 1/sqrt(d) from v_rsq_f64 + two Newton steps (+ one correction of the root)
-__device__ __forceinline__ void sqrt_rsqrt(double d, double& root, double& rinv) {
-  double r = __builtin_amdgcn_rsq(d);
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const double e = fma(-(d * r), r, 1.0);  // 1 - d r^2
-    r = fma(0.5 * r, e, r);
-  }
-  double l = d * r;
-  l = fma(0.5 * r, fma(-l, l, d), l);
-  root = l;
-  rinv = r;
-}
-
-// Phase A: one wave factors the 16x16 block at D (LDS, ld BLD; lower triangle valid) in place, writes its inverse dense to
-// Wd[16][16] (column-major), transposed-strict-lower into D's upper triangle and the diagonal to wdiag.
-//
-// Outer-product Cholesky with the rank-1 update on the matrix core.  The wave holds the full SYMMETRIC working block A and a
-// unit-lower-triangular V (Gauss-Jordan on [A | I]: W = diag(rinv) V at the end) in the accumulator layout of
-// v_mfma_f64_16x16x4: lane (q = lane >> 4, r = lane & 15), register rr <-> element (x = q + 4 rr, y = r).  Row J of either matrix
-// is then ONE register (rr = J / 4) of ONE 16-lane row (q = J % 4), indexed by the lane -- exactly the shape of an MFMA operand
-// in k-slot q.  Pivot J:
-//   u = row J of A (= column J: the block stays bitwise symmetric, l_x l_y and l_y l_x are the same product)
-//   d = u[J] (DPP row_newbcast inside the 16-lane row), rinv = 1/sqrt(d) (v_rsq_f64 + two Newton steps)
-//   l = u rinv below the diagonal, 0 elsewhere and in the other three lane rows;  m = -l rinv
-//   A -= l l^T      one MFMA: both operands are l, k-slot J % 4, the other slots zero
-//   V += m v_J^T    one MFMA: v_J = row J of V (V starts as I, so column J receives m and V[J][J] stays 1)
-// The dependent chain of a column is DPP mov -> rsqrt -> one multiply -> one MFMA (~200 cycles: tools/microbench/dp_latency.hip has
-// the instruction latencies), all 64 lanes work, and a pivot is ~35 instructions.  (An f64 MFMA runs on the SIMD's double-precision
-// lanes: no VALU instruction of the wave issues beside it, so the second MFMA and the column's stores add to the chain rather than
-// hide behind it -- ~400 cycles per pivot measured.)  (Round 2's sweep kept a
-// row per lane quadruple and exchanged six operands per pivot by ds_bpermute: ~85 instructions and ~600 cycles per pivot, 3.7 us per
-// sweep; a row-per-lane form with v_fmac_f64_dpp -- DPP on 64-bit operands issues at ~13 cycles -- reached 3.3 us.)
-// No exec-masked branch and no store inside the sweep: a column's entries of L stay in a register of the lane row that computed
-// them, a non-positive pivot is only noted for one atomic after the sweep.
-template <int SRC>
-__device__ __forceinline__ double row_bcast(double v) {   // lane SRC's v, in every lane of the same 16-lane row
-  return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + SRC, 0xf, 0xf, true);   // DPP_ROW_NEWBCAST0 + SRC
-}
-
-template <int J>
-__device__ __forceinline__ void diag16_pivot(double4_t& A, double4_t& V, double (&rinvs)[4], double (&lcol)[4], unsigned& bad, int q, int r) {
-  constexpr int QJ = J & 3, RJ = J >> 2;
-  const bool inrow = q == QJ;
-  const bool below = inrow && r > J;
-  // ---- the chain (a wave issues in order: the sched_barriers make the program order the schedule)
-  const double u = A[RJ];                             // row J of the working block (lane row QJ)
-  const double d = row_bcast<J>(u);                   // the pivot
-  double rinv = __builtin_amdgcn_rsq(d);              // sqrt_rsqrt's rinv: v_rsq_f64 + two Newton steps
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const double e = fma(-(d * rinv), rinv, 1.0);
-    rinv = fma(0.5 * rinv, e, rinv);
-  }
-  const double t = u * rinv;
-  const double lv = below ? t : 0.0;                  // column J of L below the diagonal; zero in the other k-slots
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (J < 15) A = __builtin_amdgcn_mfma_f64_16x16x4f64(lv, lv, A, 0, 0, 1);   // A -= l l^T
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- behind the chain's MFMA
-  if constexpr (J < 15) {
-    const double mv = below ? -(t * rinv) : 0.0;
-    const double vrow = inrow ? V[RJ] : 0.0;                                   // row J of V
-    V = __builtin_amdgcn_mfma_f64_16x16x4f64(mv, vrow, V, 0, 0, 0);            // V += m v_J^T
-  }
-  lcol[RJ] = inrow ? lv : lcol[RJ];                   // column J of L below the diagonal: stored after the sweep by lane row QJ
-  rinvs[RJ] = inrow ? rinv : rinvs[RJ];               // rows x = q + 4 rr of this lane: their pivots are seen by lane row q
-  bad |= ((__builtin_amdgcn_fcmp(d, 0.0, 2 /* ogt */) >> (16 * QJ)) & 1ull) ? 0u : (1u << J);
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int... J>
-__device__ __forceinline__ void diag16_sweep(double4_t& A, double4_t& V, double (&rinvs)[4], double (&lcol)[4], unsigned& bad, int q, int r,
-                                             std::integer_sequence<int, J...>) {
-  (diag16_pivot<J>(A, V, rinvs, lcol, bad, q, r), ...);
-}
-
-__device__ __forceinline__ void diag16(double* D, double* Wd, double* wdiag, int* info, int col) {
-  const int l = threadIdx.x & 63, r = l & 15, q = l >> 4;
-  double4_t A, V;
-  double rinvs[4] = {1.0, 1.0, 1.0, 1.0}, lcol[4] = {0.0, 0.0, 0.0, 0.0};
-  unsigned bad = 0;
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int x = q + 4 * rr;
-    A[rr] = (x >= r) ? D[x + r * BLD] : D[r + x * BLD];   // the upper triangle mirrors the lower one
-    V[rr] = (x == r) ? 1.0 : 0.0;
-  }
-  diag16_sweep(A, V, rinvs, lcol, bad, q, r, std::make_integer_sequence<int, 16>{});
-  if (bad != 0 && l == 0) atomicCAS(info, 0, col + __builtin_ctz(bad) + 1);  // LAPACK info: first non-PD leading minor
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int x = q + 4 * rr;                        // W[x][r] = rinv_x V[x][r]
-    if (r == x) {                                    // the pivot of row x is still where it was read (later updates add l_x l_y with l_x = 0)
-      double ljj, rinv;
-      sqrt_rsqrt(A[rr], ljj, rinv);
-      D[x + x * BLD] = ljj;
-    }
-    if (r > x) D[r + x * BLD] = lcol[rr];            // column x of L: lane row q = x % 4 kept it
-    const double w = (r <= x) ? V[rr] * rinvs[rr] : 0.0;
-    Wd[x + r * 16] = w;
-    if (r < x) D[r + x * BLD] = w;                    // strict lower part of the inverse, transposed into the upper triangle
-    if (r == x) wdiag[x] = w;
-  }
-}
-
-// 16x16x16 block product on one wave: acc (+/-)= Aop * Bop with Aop[x][k] = pa[x + k*lda_], Bop[k][y] = pb[y + k*ldb_]
-// (both operands are addressed "row index contiguous"), acc lane layout D[x = (lane>>4) + 4r][y = lane&15].
-template <int NEG>
-__device__ __forceinline__ double4_t block_mma(const double* pa, int lda_, const double* pb, int ldb_, double4_t acc) {
-  const int l = threadIdx.x & 63, q = l >> 4, r = l & 15;
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[r + (4 * kk + q) * lda_], pb[r + (4 * kk + q) * ldb_], acc, 0, 0, NEG);
-  return acc;
-}
-
-// one 16x16 block of phase C: b < nchol -> Cholesky trailing block, else inverse block (see the kernel)
-__device__ __forceinline__ void potf2_phase_c_block(double* S, const double* Wd, int s, int c0, int m, int b, int lane, int q, int r) {
-  const int nchol = m * (m + 1) / 2;
-  if (b < nchol) {
-    int ii = 0;
-    while ((ii + 1) * (ii + 2) / 2 <= b) ++ii;
-    const int I = s + 1 + ii, J = s + 1 + (b - ii * (ii + 1) / 2);
-    // D'[x][y] = C_IJ[y][x]: lanes run down the rows of C_IJ (contiguous in LDS)
-    double4_t acc;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) acc[rr] = S[(16 * I + r) + (16 * J + q + 4 * rr) * BLD];
-    acc = block_mma<1>(S + 16 * J + c0 * BLD, BLD, S + 16 * I + c0 * BLD, BLD, acc);
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) S[(16 * I + r) + (16 * J + q + 4 * rr) * BLD] = acc[rr];
-  } else {
-    const int e = b - nchol;
-    const int I = s + 1 + e / (s + 1), J = e % (s + 1);
-    // Y_IJ[a][b'] -= sum_k L_Is[a][k] * X_sJ[k][b'];  Y_IJ[a][b'] sits transposed at S[(16J + b') + (16I + a) * BLD]
-    double4_t acc;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) acc[rr] = S[(16 * J + r) + (16 * I + q + 4 * rr) * BLD];
-    if (J < s) acc = block_mma<1>(S + 16 * I + c0 * BLD, BLD, S + 16 * J + c0 * BLD, BLD, acc);
-    else {  // X_ss = Wd: Bop[k][b'] = Wd[k][b'] = Wd[k + b' * 16]  -> "row index contiguous" means pb[b' + k * ld] with the transposed view
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(S[(16 * I + (lane & 15)) + (c0 + 4 * kk + (lane >> 4)) * BLD],
-                                                   Wd[(4 * kk + (lane >> 4)) + (lane & 15) * 16], acc, 0, 0, 1);
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) S[(16 * J + r) + (16 * I + q + 4 * rr) * BLD] = acc[rr];
-  }
-}
-
-// the body: NW waves (16: the stand-alone kernel; 8: the factor role of panel_fused_kernel), sm = PB_SMEM_DOUBLES doubles
-// of LDS.  Which wave computes a 16x16 block has no influence on the block's arithmetic: same bits for any NW.
-// ptr (may be null; GPRC_POTF2_TRACE): s_memrealtime stamps of thread 0 -- [0] entry, [1] block loaded, [2] first 16x16 sweep done,
-// [3 + 2 s] / [4 + 2 s] after the two barriers of step s, [19] exit (stores issued).  Measurement only.
-#define POTF2_STAMP(k) do { if (ptr && threadIdx.x == 0) ptr[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-// preloaded: S already holds the block (gemm_tile_128<.., LDSOUT>), the loads from A are skipped.
-template <int NW>
-__device__ __attribute__((noinline)) void potf2_blocked_body(double* sm, double* A, int64_t lda, double* winv, int* info, int col0,
-                                                             unsigned long long* ptr = nullptr, bool preloaded = false) {
-  static_assert(NW >= 8, "phase B needs one wave per task: 7 tasks per step");
-  constexpr int TYS = NW / 2;          // column groups of the 128-row load / store loops (NW * 64 threads / 128 rows)
-  double* S = sm;                      // PB x BLD
-  double* Wd2 = sm + PB * BLD;         // 2 x (16 x 16): the 16x16 inverse of step s lives in buffer s & 1
-  double* Wdiag = Wd2 + 512;           // PB
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int q = lane >> 4, r = lane & 15;
-  POTF2_STAMP(0);
-  if (!preloaded) {
-    // all the loads of a thread's 128 / TYS columns are issued before the first LDS store (the loop with one conditional load
-    // per iteration took 4 us of a 46-us block); entries above the diagonal are read too -- allocated storage -- and dropped
-    const int i = t & 127, ty = t >> 7;
-    constexpr int BATCH = (NW == 8) ? 32 : 16;      // loads in flight per thread (the 16-wave kernel is capped at 128 VGPRs)
-    for (int k0 = 0; k0 < PB / TYS; k0 += BATCH) {
-      double v[BATCH];
-#pragma unroll
-      for (int k = 0; k < BATCH; ++k) v[k] = A[i + (int64_t)(ty + TYS * (k0 + k)) * lda];
-#pragma unroll
-      for (int k = 0; k < BATCH; ++k) S[i + (ty + TYS * (k0 + k)) * BLD] = (i >= ty + TYS * (k0 + k)) ? v[k] : 0.0;
-    }
-  }
-  __syncthreads();
-  POTF2_STAMP(1);
-  if (wave == 0) diag16(S, Wd2, Wdiag, info, col0);  // phase A of step 0
-  __syncthreads();
-  POTF2_STAMP(2);
-  for (int s = 0; s < 8; ++s) {
-    const int c0 = 16 * s, m = 7 - s;
-    const double* Wd = Wd2 + (s & 1) * 256;
-    // ---- phase B: m blocks of the panel below and s blocks of inverse row s -- always 7 tasks, one wave each
-    if (wave < m) {
-      const int I = s + 1 + wave;
-      // D'[x][y] = sum_k Wd[x][k] * A_I[y][k] = X_I[y][x]
-      double4_t acc = block_mma<0>(Wd, 16, S + 16 * I + c0 * BLD, BLD, (double4_t){0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) S[(16 * I + r) + (c0 + q + 4 * rr) * BLD] = acc[rr];
-    } else if (wave - m < s) {
-      const int J = wave - m;
-      // X_sJ[a][b] = sum_k Wd[a][k] * Y_sJ[k][b]; Y_sJ[k][b] sits transposed at S[(16J + b) + (c0 + k) * BLD]
-      double4_t acc = block_mma<0>(Wd, 16, S + 16 * J + c0 * BLD, BLD, (double4_t){0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) S[(16 * J + r) + (c0 + q + 4 * rr) * BLD] = acc[rr];
-    }
-    __syncthreads();
-    POTF2_STAMP(3 + 2 * s);
-    // ---- phase C with look-ahead: m(m+1)/2 Cholesky blocks then m*(s+1) inverse blocks.  Wave 0 takes block 0 -- the
-    // next diagonal block (s+1, s+1) -- and goes straight on to phase A of step s+1 (the sequential 16-pivot sweep,
-    // the longest single piece of the kernel) while the other waves work through the other blocks; nothing they touch
-    // overlaps that block, and its 16x16 inverse goes to the other Wd buffer.
-    const int total = m * (m + 1) / 2 + m * (s + 1);
-    if (wave == 0) {
-      if (s < 7) {
-        potf2_phase_c_block(S, Wd, s, c0, m, 0, lane, q, r);
-        diag16(S + (c0 + 16) + (c0 + 16) * BLD, Wd2 + ((s + 1) & 1) * 256, Wdiag + c0 + 16, info, col0 + c0 + 16);
-      }
-    } else {
-      for (int b = wave; b < total; b += NW - 1) potf2_phase_c_block(S, Wd, s, c0, m, b, lane, q, r);
-    }
-    // (a preloaded block's stores to memory -- gemm_tile_128<.., LDSOUT> did not wait for them -- are complete in every wave before
-    // this barrier, hence before any wave stores the factored block over them below; free after the first step)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    POTF2_STAMP(4 + 2 * s);
-  }
-  {
-    const int i = t & 127, ty = t >> 7;
-    const double wd = Wdiag[i];
-    constexpr int BATCH = 8;
-    for (int k0 = 0; k0 < PB / TYS; k0 += BATCH) {  // LDS reads of a batch first (S[c + i BLD]: a row walk, stride BLD), then its stores back to back
-      double lv[BATCH], wv[BATCH];
-#pragma unroll
-      for (int k = 0; k < BATCH; ++k) {
-        const int c = ty + TYS * (k0 + k);
-        lv[k] = S[i + c * BLD];
-        wv[k] = (i > c) ? S[c + i * BLD] : (i == c ? wd : 0.0);
-      }
-#pragma unroll
-      for (int k = 0; k < BATCH; ++k) {
-        const int c = ty + TYS * (k0 + k);
-        if (i >= c) A[i + (int64_t)c * lda] = lv[k];
-        winv[i + c * PB] = wv[k];
-      }
-    }
-  }
-  POTF2_STAMP(19);
-}
 
 __global__ __launch_bounds__(1024) void potf2_inv_blocked_kernel(double* A, int64_t lda, double* winv, int* info, int col0) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   potf2_blocked_body<16>(sm, A, lda, winv, info, col0);
 }
-
-// ------------------------------------------------------------------------------------------------
-// GEMM tile core: acc(128x128) = A(128 x K) * B(128 x K)^T, A and B column-major strips.
-//
-// LDS image per operand and buffer: [KB=16][LDT=144] doubles, i.e. one k-slice of the strip per row
-// of 128 contiguous matrix rows + 16 pad.  The pad moves consecutive k-slices by 32 banks, so the
-// ds_read_b64 of an MFMA operand (16 matrix rows x 2 k per 32-lane half) is conflict-free, and the
-// 16-byte staging stores of one wave cover 1 KiB contiguous.
-// MFMA operands are swapped (A-operand <- B strip, B-operand <- A strip): the accumulator then holds
-// C[row = 16m + (lane&15)][col = 16n + (lane>>4) + 4r], i.e. 16 consecutive ROWS per lane group,
-// which is the contiguous direction of the column-major C tile.
-// ------------------------------------------------------------------------------------------------
-constexpr int G_KB = 16;
-constexpr int G_LDT = 144;
-constexpr int G_BUF = G_KB * G_LDT;           // doubles per operand per buffer
-constexpr int G_SMEM_DOUBLES = 4 * G_BUF;     // A,B x 2 buffers = 73,728 B -> 2 workgroups per CU
-
-// operands of one k-step (4 consecutive k) for this wave's 64x64 sub-tile: 4 A + 4 B doubles per lane
-__device__ __forceinline__ void read_ops(const double* Ac, const double* Bc, int kk, double (&a)[4], double (&b)[4]) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m) a[m] = Ac[kk * 4 * G_LDT + m * 16];
-#pragma unroll
-  for (int n = 0; n < 4; ++n) b[n] = Bc[kk * 4 * G_LDT + n * 16];
-}
-// NEG = 1 sets the f64 MFMA's negate-A bit (the BLGP field is the NEG set on f64 MFMA; verified on gfx950 by
-// tools/microbench/mfma_neg.hip): acc = acc - op_a * op_b, exactly.
-template <int NEG>
-__device__ __forceinline__ void mma_step(const double (&a)[4], const double (&b)[4], double4_t (&acc)[4][4]) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[n], a[m], acc[m][n], 0, 0, NEG);
-}
-
-// LDS-DMA of one k-tile of both strips: wave w moves k-slices w, w+4, w+8, w+12 of A and of B; one
-// global_load_lds_dwordx4 per slice = 64 lanes x 16 B = the slice's 128 rows, landing contiguously at a
-// wave-uniform LDS row (the 128-byte row pad survives because a row is exactly one instruction).
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-__device__ __forceinline__ void dma_ktile(const double* Ag, int64_t lda, const double* Bg, int64_t ldb, double* Asb, double* Bsb) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    __builtin_amdgcn_global_load_lds((gptr_t)(Ag + (int64_t)(4 * i) * lda), (lptr_t)(Asb + 4 * i * G_LDT), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gptr_t)(Bg + (int64_t)(4 * i) * ldb), (lptr_t)(Bsb + 4 * i * G_LDT), 16, 0, 0);
-  }
-}
-
-// Where k-tile kt of an operand strip lives (this lane's 16 bytes of k-slice `wave`).  Plain: a column-major strip with
-// one leading dimension.  SEG: the strip is rows [brow, brow + 128) of the PACKED factor across its first K columns
-// (B = packed base, ldb = n_pad): every NB columns it moves to the next panel, with that panel's own leading dimension.
-template <bool SEG>
-__device__ __forceinline__ const double* strip_ktile(const double* B, int64_t ldb, int64_t brow, int kt, int lane, int wave, int64_t& ld) {
-  if constexpr (SEG) {
-    const int pp = kt / (NB / 16);                    // panel that holds k-tile kt
-    ld = panel_ld(ldb, pp);
-    return B + panel_offset(ldb, pp) + (brow - (int64_t)pp * NB) + (int64_t)((kt % (NB / 16)) * 16 + wave) * ld + 2 * lane;
-  } else {
-    ld = ldb;
-    return B + 2 * lane + (int64_t)(kt * 16 + wave) * ldb;
-  }
-}
-
-// The same place WITHOUT the lane's part: the wave-uniform address of k-slice `wave` of k-tile kt (the lane adds 16 bytes x lane as a
-// 32-bit VGPR offset of the LDS-DMA instruction, whose base is then an SGPR pair: no VALU address arithmetic in the loop).
-template <bool SEG>
-__device__ __forceinline__ const char* strip_ktile_s(const double* B, int64_t ldb, int64_t brow, int kt, int wave, int64_t& ld) {
-  if constexpr (SEG) {
-    const int pp = kt / (NB / 16);
-    ld = panel_ld(ldb, pp);
-    return reinterpret_cast<const char*>(B + panel_offset(ldb, pp) + (brow - (int64_t)pp * NB) + (int64_t)((kt % (NB / 16)) * 16 + wave) * ld);
-  } else {
-    ld = ldb;
-    return reinterpret_cast<const char*>(B + (int64_t)(kt * 16 + wave) * ldb);
-  }
-}
-
-// SSQ (the predict's panel solve only): besides storing the tile, leave in ssq[0..127] the sum of squares of each of the
-// tile's 128 rows over its 128 columns -- these columns of v^T are final after this tile, so colSums(v * v)
-// (R/GPRclass.R:164) is assembled from these per-block partials and the pass that re-read the whole solved chunk is gone.
-// Fixed order: a lane's 16 columns (n, r ascending), the four lanes of a row (xor 16, xor 32), the two column waves.
-// LDSOUT: the finished tile ALSO goes to lds_out as the 128 x 128 LDS image potf2_blocked_body works on (leading dimension 144,
-// zero above the diagonal) -- the factor role hands the updated diagonal block to the factorisation without the round trip
-// through memory (one more workgroup barrier than without: every wave must be past its last operand read, the image overlaps
-// the staging buffers).
-// ILV: the main loop with every non-MFMA instruction in the shadow of an MFMA (below) -- the throughput kernels; false keeps the
-// block-structured loop for the roles of the fused panel / service kernels, which inline this function several times and spill
-// with the larger body (their tiles are short -- K = 128..384 -- and paced by flags, not by the loop).
-// CORE (interleaved loops only): 2 = the loop without VALU instructions (the plain throughput kernels), 1 = the first interleaved loop
-// (kept for the tiles that run beside the factor service -- sweep kernel, trailing_service_kernel: measured, see the loops' comments).
-// WT: the tile is stored WRITE-THROUGH (sc1: global_store ... sc1, the agent-scope relaxed atomic store), leaving no dirty line in the XCD's L2.
-template <bool SET, bool SEG = false, bool SEGA = false, bool SSQ = false, bool LDSOUT = false, bool ILV = true, int CORE = 2, bool WT = false>
-__device__ __forceinline__ void gemm_tile_128(double* C, int64_t ldc, const double* A, int64_t lda, const double* B,
-                                              int64_t ldb, int K, double* smem, int64_t brow = 0, int64_t arow = 0, int kt0 = 0,
-                                              double* ssq = nullptr, int tid = -1, double* lds_out = nullptr) {
-  const int t = tid < 0 ? (int)threadIdx.x : tid, lane = t & 63;   // tid: a 256-thread team inside a larger workgroup
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-  const int fk = lane >> 4, fr = lane & 15;
-  double* As = smem;
-  double* Bs = smem + 2 * G_BUF;
-
-  // C -= A*B^T: the accumulators START as the C tile (its loads fly with the first DMA) and every MFMA
-  // subtracts, so the epilogue is stores only.  SET: accumulators start at zero, plain products.
-  constexpr int NEG = SET ? 0 : 1;
-  double* Cw = C + (wr * 64 + fr) + (int64_t)(wc * 64 + fk) * ldc;
-  double4_t acc[4][4];
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) acc[m][n][r] = SET ? 0.0 : Cw[m * 16 + (int64_t)(n * 16 + 4 * r) * ldc];
-
-  int64_t ldak, ldbk;
-  // kt0 (first k-tile of the pass) addresses the PACKED operands only: a plain strip is handed over already pointing at
-  // its first k-tile (the running pointer below restarts from it)
-  const double* Ag = strip_ktile<SEGA>(A, lda, arow, SEGA ? kt0 : 0, lane, wave, ldak);  // this lane's 16 bytes of k-slice `wave`
-  const double* Bg = strip_ktile<SEG>(B, ldb, brow, SEG ? kt0 : 0, lane, wave, ldbk);
-  const int srow = wave * G_LDT;                          // LDS row of that slice (wave-uniform)
-  const int foff = fr + fk * G_LDT;                       // this lane's MFMA operand element
-
-  // Software pipeline, operand reads TWO k-steps ahead.  Four named operand sets (one per k-step of a tile).
-  // Every k-step is:  s_waitcnt lgkmcnt(0)  ->  issue the reads of step +2  ->  16 MFMAs of this step.
-  // The wait therefore only ever covers reads issued one whole MFMA block (>= 1000 cycles) earlier; with the
-  // reads issued right in front of the compiler's own lgkmcnt(0) they were waited for on the spot.
-  //   step (t,0): reads (t,2)          step (t,1): reads (t,3)   <- last LDS reads of tile t's buffer
-  //   step (t,2): vmcnt(0) + barrier [tile t+1 landed, tile t's buffer drained]; DMA tile t+2; reads (t+1,0)
-  //   step (t,3): reads (t+1,1)
-  // so a DMA has 64 MFMAs (4096 cycles) to land, as before.
-  constexpr int LGKM0 = 0xC07F;  // s_waitcnt lgkmcnt(0), vmcnt/expcnt untouched
-  const int KT = K / G_KB;
-  dma_ktile(Ag, ldak, Bg, ldbk, As + srow, Bs + srow);
-  // vmcnt(0) through the BUILTIN, not inline asm, so that the compiler's waitcnt pass knows the C-tile loads
-  // above have completed and does not re-wait vmcnt(0) (draining fresh DMAs) inside the loop.  0x0F70 = vmcnt(0).
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
-  if (KT > 1) {
-    Ag = strip_ktile<SEGA>(A, lda, arow, (SEGA ? kt0 : 0) + 1, lane, wave, ldak);
-    Bg = strip_ktile<SEG>(B, ldb, brow, (SEG ? kt0 : 0) + 1, lane, wave, ldbk);
-    dma_ktile(Ag, ldak, Bg, ldbk, As + G_BUF + srow, Bs + G_BUF + srow);
-  }
-  if constexpr (!SEGA) Ag = A + 2 * lane + (int64_t)(2 * G_KB + wave) * lda;  // next tile to request: kt + 2
-  if constexpr (!SEG) Bg = B + 2 * lane + (int64_t)(2 * G_KB + wave) * ldb;
-  double a0[4], b0[4], a1[4], b1[4], a2[4], b2[4], a3[4], b3[4];
-  read_ops(As + wr * 64 + foff, Bs + wc * 64 + foff, 0, a0, b0);
-  read_ops(As + wr * 64 + foff, Bs + wc * 64 + foff, 1, a1, b1);
-#ifndef GPRC_CORE_CLUMPED
-  constexpr bool interleaved = ILV;
-#else
-  constexpr bool interleaved = false;
-#endif
-  if constexpr (interleaved && CORE == 2) {
-  // ---- Main loop (round 3, second form): no VALU instruction but the MFMAs ------------------------------------------------------
-  // An f64 MFMA executes on the SIMD's double-precision lanes, and a VALU instruction issued behind it -- a 32-bit address add as
-  // much as an FMA -- takes the pipe away from the next MFMA: tools/microbench/mfma_valu_mix.hip measures 64 cycles per MFMA for a
-  // pure stream, +14 with one v_add_u32 behind each MFMA, +18 with two; SALU and LDS instructions cost nothing.  The first
-  // interleaved loop still carried ~20 VALU instructions per k-tile and wave (ISA: 8 v_lshl_add_u64 for the LDS-DMA addresses, 12
-  // v_add_u32 / v_subrev_u32 for the ds_read2 bases) -- ~5 % of the pipe.  Here the loop has none:
-  //   * LDS-DMA with an SGPR base: global_load_lds_dwordx4 v_off, s[base:base+1] -- the k-slice's address is wave-uniform, the lane
-  //     contributes a constant 32-bit offset (16 B x lane); the compiler has no such selection for the builtin, hence inline assembly
-  //     (m0 = the slice's LDS row, set by s_mov in the same statement);
-  //   * operand reads as ds_read_b64 with 16-bit immediate offsets from TWO loop-invariant base registers (one per operand): every
-  //     buffer / k-step / block offset is a constant of the instruction once the loop is unrolled by two k-tiles (ds_read2_b64's 8-bit
-  //     offsets reach 2 KB only, and the compiler paid a v_add_u32 per pair for them);
-  //   * the waits for those reads counted by hand (the compiler does not see assembly loads): the reads of a k-step are issued two
-  //     blocks ahead, eight per block, in order: s_waitcnt lgkmcnt(8) in front of a block leaves exactly the next block's in flight.
-  // Same products, same k order, same accumulators as before: identical bits.
-  const unsigned lane_off = 16u * (unsigned)lane;
-  const unsigned ldsA = (unsigned)(uintptr_t)(lptr_t)(As + srow), ldsB = (unsigned)(uintptr_t)(lptr_t)(Bs + srow);                    // wave-uniform
-  const unsigned aBase = (unsigned)(uintptr_t)(lptr_t)(As + wr * 64 + foff), bBase = (unsigned)(uintptr_t)(lptr_t)(Bs + wc * 64 + foff);  // per lane
-  // next tile to request (k-tile 2): wave-uniform addresses
-  int64_t ldas, ldbs;
-  const char* Asg = strip_ktile_s<SEGA>(A, lda, arow, (SEGA ? kt0 : 0) + 2, wave, ldas);
-  const char* Bsg = strip_ktile_s<SEG>(B, ldb, brow, (SEG ? kt0 : 0) + 2, wave, ldbs);
-#define GPRC_SB __builtin_amdgcn_sched_barrier(0);
-#define GPRC_M(A_, B_, i) acc[(i) >> 2][(i) & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(B_[(i) & 3], A_[(i) >> 2], acc[(i) >> 2][(i) & 3], 0, 0, NEG); GPRC_SB
-#define GPRC_RD(dst, base, off) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "n"(off));
-  // two reads (blocks 2r, 2r+1) of k-step kk in buffer buf
-#define GPRC_RA(buf, kk, r, A_) GPRC_RD(A_[2 * (r)], aBase, ((buf) * G_BUF + (kk) * 4 * G_LDT + (2 * (r)) * 16) * 8) GPRC_RD(A_[2 * (r) + 1], aBase, ((buf) * G_BUF + (kk) * 4 * G_LDT + (2 * (r) + 1) * 16) * 8) GPRC_SB
-#define GPRC_RB(buf, kk, r, B_) GPRC_RD(B_[2 * (r)], bBase, ((buf) * G_BUF + (kk) * 4 * G_LDT + (2 * (r)) * 16) * 8) GPRC_RD(B_[2 * (r) + 1], bBase, ((buf) * G_BUF + (kk) * 4 * G_LDT + (2 * (r) + 1) * 16) * 8) GPRC_SB
-#define GPRC_READY(cnt, A_, B_) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(A_[0]), "+v"(A_[1]), "+v"(A_[2]), "+v"(A_[3]), "+v"(B_[0]), "+v"(B_[1]), "+v"(B_[2]), "+v"(B_[3])); GPRC_SB
-#define GPRC_BLOCK_R(A_, B_, buf, kk, RA_, RB_, cond)                                                               \
-  GPRC_M(A_, B_, 0) GPRC_M(A_, B_, 1) if (cond) { GPRC_RA(buf, kk, 0, RA_) }                                        \
-  GPRC_M(A_, B_, 2) GPRC_M(A_, B_, 3) if (cond) { GPRC_RA(buf, kk, 1, RA_) }                                        \
-  GPRC_M(A_, B_, 4) GPRC_M(A_, B_, 5) if (cond) { GPRC_RB(buf, kk, 0, RB_) }                                        \
-  GPRC_M(A_, B_, 6) GPRC_M(A_, B_, 7) if (cond) { GPRC_RB(buf, kk, 1, RB_) }                                        \
-  GPRC_M(A_, B_, 8) GPRC_M(A_, B_, 9) GPRC_M(A_, B_, 10) GPRC_M(A_, B_, 11) GPRC_M(A_, B_, 12) GPRC_M(A_, B_, 13) GPRC_M(A_, B_, 14) GPRC_M(A_, B_, 15)
-  // one LDS-DMA: k-slice wave + 4 i of the tile at Asg / Bsg into buffer buf (m0 <- the slice's LDS row; one wait state before its use)
-#define GPRC_DMA(i, buf, more2)                                                                                      \
-  if (more2) {                                                                                                      \
-    if ((i) < 4) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(lane_off), "s"(Asg + (int64_t)(4 * (i)) * ldas * 8), "s"(ldsA + (unsigned)(((buf) * G_BUF + 4 * (i) * G_LDT) * 8)) : "memory"); \
-    else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(lane_off), "s"(Bsg + (int64_t)(4 * ((i) - 4)) * ldbs * 8), "s"(ldsB + (unsigned)(((buf) * G_BUF + 4 * ((i) - 4) * G_LDT) * 8)) : "memory"); \
-    GPRC_SB                                                                                                         \
-  }
-  // one k-tile in buffer buf (the next one in 1 - buf); more1 / more2: a tile kt+1 / kt+2 exists; kt: this tile's index
-#define GPRC_KTILE(buf, more1, more2)                                                                                \
-  {                                                                                                                 \
-    GPRC_SB                                                                                                         \
-    GPRC_READY(8, a0, b0)                                                                                           \
-    GPRC_BLOCK_R(a0, b0, buf, 2, a2, b2, true)                                                                      \
-    GPRC_READY(8, a1, b1)                                                                                           \
-    GPRC_BLOCK_R(a1, b1, buf, 3, a3, b3, true)                                                                      \
-    GPRC_READY(8, a2, b2)                                                                                           \
-    GPRC_M(a2, b2, 0) GPRC_M(a2, b2, 1) GPRC_M(a2, b2, 2) GPRC_M(a2, b2, 3)                                         \
-    if (more1) {                                                                                                    \
-      /* this wave's reads of buffer buf have returned (lgkmcnt) and its share of tile kt+1 has landed (vmcnt); after the */ \
-      /* barrier that holds for every wave: tile kt+1 may be read and buffer buf overwritten */                     \
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                   \
-      __builtin_amdgcn_s_barrier();                                                                                 \
-      GPRC_SB                                                                                                       \
-    }                                                                                                               \
-    GPRC_M(a2, b2, 4) if (more1) { GPRC_RA(1 - (buf), 0, 0, a0) }                                                   \
-    GPRC_M(a2, b2, 5) if (more1) { GPRC_RA(1 - (buf), 0, 1, a0) }                                                   \
-    GPRC_M(a2, b2, 6) if (more1) { GPRC_RB(1 - (buf), 0, 0, b0) }                                                   \
-    GPRC_M(a2, b2, 7) if (more1) { GPRC_RB(1 - (buf), 0, 1, b0) }                                                   \
-    GPRC_M(a2, b2, 8) GPRC_DMA(0, buf, more2) GPRC_M(a2, b2, 9) GPRC_DMA(4, buf, more2) GPRC_M(a2, b2, 10) GPRC_DMA(1, buf, more2) GPRC_M(a2, b2, 11) GPRC_DMA(5, buf, more2) \
-    GPRC_M(a2, b2, 12) GPRC_DMA(2, buf, more2) GPRC_M(a2, b2, 13) GPRC_DMA(6, buf, more2) GPRC_M(a2, b2, 14) GPRC_DMA(3, buf, more2) GPRC_M(a2, b2, 15) GPRC_DMA(7, buf, more2) \
-    if (more2) {   /* the tile after the one just requested: 16 columns on, or the next panel of a packed strip (scalar arithmetic) */ \
-      if constexpr (SEGA) { if (((kt0 + kt + 3) % (NB / 16)) == 0) Asg = strip_ktile_s<true>(A, lda, arow, kt0 + kt + 3, wave, ldas); else Asg += (int64_t)G_KB * ldas * 8; } \
-      else Asg += (int64_t)G_KB * ldas * 8;                                                                         \
-      if constexpr (SEG) { if (((kt0 + kt + 3) % (NB / 16)) == 0) Bsg = strip_ktile_s<true>(B, ldb, brow, kt0 + kt + 3, wave, ldbs); else Bsg += (int64_t)G_KB * ldbs * 8; } \
-      else Bsg += (int64_t)G_KB * ldbs * 8;                                                                         \
-      GPRC_SB                                                                                                       \
-    }                                                                                                               \
-    if (more1) { GPRC_READY(8, a3, b3) } else { GPRC_READY(0, a3, b3) }                                             \
-    GPRC_BLOCK_R(a3, b3, 1 - (buf), 1, a1, b1, more1)                                                               \
-  }
-  {   // KT is even and >= 4: every caller's K is a multiple of 128 (eight k-tiles); launch_gemm_nt, the one launcher with a free K, checks it
-    int kt = 0;
-    for (; kt + 2 < KT; kt += 2) {
-      GPRC_KTILE(0, true, true)
-      ++kt;
-      GPRC_KTILE(1, true, true)
-      --kt;
-    }
-    GPRC_KTILE(0, true, false)
-    ++kt;
-    GPRC_KTILE(1, false, false)
-  }
-#undef GPRC_KTILE
-#undef GPRC_DMA
-#undef GPRC_BLOCK_R
-#undef GPRC_READY
-#undef GPRC_RA
-#undef GPRC_RB
-#undef GPRC_RD
-#undef GPRC_M
-#undef GPRC_SB
-  } else if constexpr (interleaved) {
-  // ---- Main loop, every non-MFMA instruction in the shadow of an MFMA (round 3, first form) -----------------------------------
-  // (Still ~20 VALU instructions per k-tile and wave.  It stays for the K = 512 tiles of the kernels that run BESIDE the factor
-  //  service: with the VALU-free loop their tiles are a third faster, the memory system correspondingly busier, and the service's
-  //  latency-bound roles -- and with them the whole mid-size factorisation -- slower: n = 12288 13.55 -> 14.66 ms, 16384 27.44 -> 28.27,
-  //  same box, profiles/r03_factor_schedules.txt.)
-  // Counters on the shipped loop (profiles/r03_c4_core_counters.txt): the MFMA pipes were busy 91.7 % of the kernel's cycles at
-  // 2.37 GHz, and per 64 MFMAs a wave issues 73 other instructions -- 16 ds_read2, 8 LDS-DMA with their m0 / address set-up, the
-  // s_waitcnt / s_barrier, loop arithmetic.  In the block-structured loop they sat in CLUMPS between the 16-MFMA blocks: four
-  // operand-read groups and, once per k-tile, vmcnt(0) + barrier + 8 DMA issues + 4 reads with nothing but the block's last MFMA
-  // in flight.  A wave is in order: while it works through a clump it issues no MFMA, and its SIMD's pipe runs dry unless the
-  // partner wave happens to be inside a block (a wave alone on its SIMD reached 75 %).  Here every MFMA is followed by at most
-  // one other operation (a ds_read2, or one DMA with its set-up), the barrier sits BETWEEN two MFMAs of block 2 with four MFMAs
-  // of the same wave still queued on the pipe, and the order is pinned by a sched_barrier after every statement.  The products,
-  // their k order and the accumulator each one lands in are unchanged: identical bits.
-  //   block 0 (a0,b0): reads (t,2) after MFMAs 1,3,5,7          block 1 (a1,b1): reads (t,3) after 1,3,5,7
-  //   block 2 (a2,b2): MFMAs 0-3 | lgkmcnt(0) vmcnt(0) s_barrier | reads (t+1,0) after 4,5,6,7 | DMA slice i of tile t+2 after 8+i
-  //   block 3 (a3,b3): reads (t+1,1) after 1,3,5,7
-#define GPRC_SB __builtin_amdgcn_sched_barrier(0);
-  // (timing experiments only -- wrong results: GPRC_EXP_NOVM drops the wait for the landed DMA, GPRC_EXP_NOBAR the workgroup barrier)
-#ifdef GPRC_EXP_NOVM
-#define GPRC_TILE_WAIT asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-#define GPRC_TILE_WAIT asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-#ifdef GPRC_EXP_NOBAR
-#define GPRC_TILE_BARRIER
-#else
-#define GPRC_TILE_BARRIER __builtin_amdgcn_s_barrier();
-#endif
-#define GPRC_M(A_, B_, i) acc[(i) >> 2][(i) & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(B_[(i) & 3], A_[(i) >> 2], acc[(i) >> 2][(i) & 3], 0, 0, NEG); GPRC_SB
-  // one ds_read2_b64 each: RA r = 0, 1 -> a[2r], a[2r+1]; RB r = 0, 1 -> b[2r], b[2r+1]
-#define GPRC_RA(Ap_, kk, r, A_) A_[2 * (r)] = (Ap_)[(kk) * 4 * G_LDT + (2 * (r)) * 16]; A_[2 * (r) + 1] = (Ap_)[(kk) * 4 * G_LDT + (2 * (r) + 1) * 16]; GPRC_SB
-#define GPRC_RB(Bp_, kk, r, B_) B_[2 * (r)] = (Bp_)[(kk) * 4 * G_LDT + (2 * (r)) * 16]; B_[2 * (r) + 1] = (Bp_)[(kk) * 4 * G_LDT + (2 * (r) + 1) * 16]; GPRC_SB
-#define GPRC_BLOCK_R(A_, B_, Ap_, Bp_, kk, RA_, RB_, cond)                                                          \
-  GPRC_M(A_, B_, 0) GPRC_M(A_, B_, 1) if (cond) { GPRC_RA(Ap_, kk, 0, RA_) }                                        \
-  GPRC_M(A_, B_, 2) GPRC_M(A_, B_, 3) if (cond) { GPRC_RA(Ap_, kk, 1, RA_) }                                        \
-  GPRC_M(A_, B_, 4) GPRC_M(A_, B_, 5) if (cond) { GPRC_RB(Bp_, kk, 0, RB_) }                                        \
-  GPRC_M(A_, B_, 6) GPRC_M(A_, B_, 7) if (cond) { GPRC_RB(Bp_, kk, 1, RB_) }                                        \
-  GPRC_M(A_, B_, 8) GPRC_M(A_, B_, 9) GPRC_M(A_, B_, 10) GPRC_M(A_, B_, 11) GPRC_M(A_, B_, 12) GPRC_M(A_, B_, 13) GPRC_M(A_, B_, 14) GPRC_M(A_, B_, 15)
-#define GPRC_DMA(i, more2)                                                                                           \
-  if (more2) {                                                                                                      \
-    if ((i) < 4) __builtin_amdgcn_global_load_lds((gptr_t)(Ag + (int64_t)(4 * (i)) * ldak), (lptr_t)(As + cur + srow + 4 * (i) * G_LDT), 16, 0, 0); \
-    else __builtin_amdgcn_global_load_lds((gptr_t)(Bg + (int64_t)(4 * ((i) - 4)) * ldbk), (lptr_t)(Bs + cur + srow + 4 * ((i) - 4) * G_LDT), 16, 0, 0); \
-    GPRC_SB                                                                                                         \
-  }
-  // one k-tile; more1 / more2: a tile kt+1 / kt+2 exists (compile-time true in the steady-state loop, so that it has no branches)
-#define GPRC_KTILE(more1, more2)                                                                                     \
-  {                                                                                                                 \
-    const int cur = (kt & 1) * G_BUF, nxt = G_BUF - cur;                                                            \
-    const double* Ac = As + cur + wr * 64 + foff;                                                                   \
-    const double* Bc = Bs + cur + wc * 64 + foff;                                                                   \
-    const double* An = As + nxt + wr * 64 + foff;                                                                   \
-    const double* Bn = Bs + nxt + wc * 64 + foff;                                                                   \
-    GPRC_SB                                                                                                         \
-    GPRC_BLOCK_R(a0, b0, Ac, Bc, 2, a2, b2, true)                                                                   \
-    GPRC_BLOCK_R(a1, b1, Ac, Bc, 3, a3, b3, true)                                                                   \
-    GPRC_M(a2, b2, 0) GPRC_M(a2, b2, 1) GPRC_M(a2, b2, 2) GPRC_M(a2, b2, 3)                                         \
-    if (more1) {                                                                                                    \
-      /* this wave's reads of buffer `cur` have returned (lgkmcnt) and its share of tile kt+1 has landed (vmcnt); after the */ \
-      /* barrier that holds for every wave: tile kt+1 may be read and buffer `cur` overwritten */                   \
-      GPRC_TILE_WAIT                                                                                                \
-      GPRC_TILE_BARRIER                                                                                             \
-      GPRC_SB                                                                                                       \
-      if (more2) {                                                                                                  \
-        if constexpr (SEGA || SEG) {                                                                                \
-          const bool boundary = ((kt0 + kt + 2) % (NB / 16)) == 0;                                                  \
-          if constexpr (SEGA) { if (boundary) Ag = strip_ktile<true>(A, lda, arow, kt0 + kt + 2, lane, wave, ldak); else Ag += (int64_t)G_KB * ldak; } \
-          if constexpr (SEG) { if (boundary) Bg = strip_ktile<true>(B, ldb, brow, kt0 + kt + 2, lane, wave, ldbk); else Bg += (int64_t)G_KB * ldbk; } \
-        }                                                                                                           \
-        GPRC_SB                                                                                                     \
-      }                                                                                                             \
-    }                                                                                                               \
-    GPRC_M(a2, b2, 4) if (more1) { GPRC_RA(An, 0, 0, a0) }                                                          \
-    GPRC_M(a2, b2, 5) if (more1) { GPRC_RA(An, 0, 1, a0) }                                                          \
-    GPRC_M(a2, b2, 6) if (more1) { GPRC_RB(Bn, 0, 0, b0) }                                                          \
-    GPRC_M(a2, b2, 7) if (more1) { GPRC_RB(Bn, 0, 1, b0) }                                                          \
-    GPRC_M(a2, b2, 8) GPRC_DMA(0, more2) GPRC_M(a2, b2, 9) GPRC_DMA(4, more2) GPRC_M(a2, b2, 10) GPRC_DMA(1, more2) GPRC_M(a2, b2, 11) GPRC_DMA(5, more2) \
-    GPRC_M(a2, b2, 12) GPRC_DMA(2, more2) GPRC_M(a2, b2, 13) GPRC_DMA(6, more2) GPRC_M(a2, b2, 14) GPRC_DMA(3, more2) GPRC_M(a2, b2, 15) GPRC_DMA(7, more2) \
-    if (more2) {                                                                                                    \
-      if constexpr (!SEGA) Ag += (int64_t)G_KB * lda;                                                               \
-      if constexpr (!SEG) Bg += (int64_t)G_KB * ldb;                                                                \
-    }                                                                                                               \
-    GPRC_BLOCK_R(a3, b3, An, Bn, 1, a1, b1, more1)                                                                  \
-  }
-  {
-    int kt = 0;
-    for (; kt + 2 < KT; ++kt) GPRC_KTILE(true, true)
-    for (; kt < KT; ++kt) {
-      const bool more1 = kt + 1 < KT;
-      GPRC_KTILE(more1, false)
-    }
-  }
-#undef GPRC_KTILE
-#undef GPRC_TILE_WAIT
-#undef GPRC_TILE_BARRIER
-#undef GPRC_DMA
-#undef GPRC_BLOCK_R
-#undef GPRC_RA
-#undef GPRC_RB
-#undef GPRC_M
-#undef GPRC_SB
-  } else {
-  for (int kt = 0; kt < KT; ++kt) {
-    const int cur = (kt & 1) * G_BUF, nxt = G_BUF - cur;
-    const double* Ac = As + cur + wr * 64 + foff;
-    const double* Bc = Bs + cur + wc * 64 + foff;
-    const double* An = As + nxt + wr * 64 + foff;
-    const double* Bn = Bs + nxt + wc * 64 + foff;
-    // sched_barrier(0) after every MFMA block: register-only MFMAs otherwise drift across the explicit waits and
-    // the compiler merges blocks, putting the reads back in front of a wait
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    read_ops(Ac, Bc, 2, a2, b2);
-    mma_step<NEG>(a0, b0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    read_ops(Ac, Bc, 3, a3, b3);
-    mma_step<NEG>(a1, b1, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    if (kt + 1 < KT) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile kt+1 has landed (this wave's share)
-      __syncthreads();                                   // ... everyone's share; and buffer `cur` is drained
-      if (kt + 2 < KT) {
-        // packed operands: inside a panel the next k-tile is 16 columns further on (same leading dimension); only at a
-        // panel boundary (every NB / 16 k-tiles) is the address rebuilt from the panel geometry -- the full index
-        // arithmetic (64-bit multiplies) on every k-tile cost ~2 % of the long-K passes
-        if constexpr (SEGA || SEG) {
-          const bool boundary = ((kt0 + kt + 2) % (NB / 16)) == 0;
-          if constexpr (SEGA) { if (boundary) Ag = strip_ktile<true>(A, lda, arow, kt0 + kt + 2, lane, wave, ldak); else Ag += (int64_t)G_KB * ldak; }
-          if constexpr (SEG) { if (boundary) Bg = strip_ktile<true>(B, ldb, brow, kt0 + kt + 2, lane, wave, ldbk); else Bg += (int64_t)G_KB * ldbk; }
-        }
-        dma_ktile(Ag, ldak, Bg, ldbk, As + cur + srow, Bs + cur + srow);
-        if constexpr (!SEGA) Ag += (int64_t)G_KB * lda;
-        if constexpr (!SEG) Bg += (int64_t)G_KB * ldb;
-      }
-      read_ops(An, Bn, 0, a0, b0);
-    }
-    mma_step<NEG>(a2, b2, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    if (kt + 1 < KT) read_ops(An, Bn, 1, a1, b1);
-    mma_step<NEG>(a3, b3, acc);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-
-  }
-
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        if constexpr (WT) __hip_atomic_store(&Cw[m * 16 + (int64_t)(n * 16 + 4 * r) * ldc], acc[m][n][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else Cw[m * 16 + (int64_t)(n * 16 + 4 * r) * ldc] = acc[m][n][r];
-      }
-
-  if constexpr (LDSOUT) {
-    __syncthreads();  // every wave is past its last operand read: the staging buffers are free
-    constexpr int LDO = 144;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const int row = wr * 64 + fr + m * 16, col = wc * 64 + fk + n * 16 + 4 * r;
-          lds_out[row + col * LDO] = (row >= col) ? acc[m][n][r] : 0.0;
-        }
-  }
-
-  if constexpr (SSQ) {
-    double rs[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      double q = 0.0;
-#pragma unroll
-      for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) q = fma(acc[m][n][r], acc[m][n][r], q);
-      q += __shfl_xor(q, 16, 64);
-      q += __shfl_xor(q, 32, 64);
-      rs[m] = q;
-    }
-    __syncthreads();  // every wave is past its last operand read: the staging buffers are free
-    if (fk == 0) {
-#pragma unroll
-      for (int m = 0; m < 4; ++m) smem[wc * 128 + wr * 64 + m * 16 + fr] = rs[m];
-    }
-    __syncthreads();
-    if (t < 128) ssq[t] = smem[t] + smem[128 + t];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// 256 x 128 macro-tile on 8 waves (512 threads, one workgroup per CU): the same wave-level 64 x 64 MFMA core as
-// gemm_tile_128, but the four row-waves share ONE B strip and the A strip is twice as tall -- 384 strip rows staged per k-tile
-// for 256 x 128 outputs instead of 2 x 256 for two independent 128 x 128 workgroups: -25 % LDS-DMA traffic per flop.  Every
-// output element still accumulates k ascending in the same v_mfma_f64_16x16x4 steps from the loaded C value: bit-identical.
-// A: plain column-major strip (256 rows), B: rows [brow, brow + 128) of the PACKED factor starting at k-tile kt0 (the predict's
-// left-looking pass).  LDS: A [2][16][272] + B [2][16][144] doubles = 106,496 B.
-// ------------------------------------------------------------------------------------------------
-constexpr int T2_LDA = 272, T2_LDB = 144;
-constexpr int T2_BUFA = G_KB * T2_LDA, T2_BUFB = G_KB * T2_LDB;
-constexpr int T2_SMEM_DOUBLES = 2 * T2_BUFA + 2 * T2_BUFB;
-
-__device__ __forceinline__ void read_ops2(const double* Ac, const double* Bc, int kk, double (&a)[4], double (&b)[4]) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m) a[m] = Ac[kk * 4 * T2_LDA + m * 16];
-#pragma unroll
-  for (int n = 0; n < 4; ++n) b[n] = Bc[kk * 4 * T2_LDB + n * 16];
-}
-
-__device__ __forceinline__ void gemm_tile_256x128_seg(double* C, int64_t ldc, const double* A, int64_t lda, const double* Bpk, int64_t n_pad,
-                                                      int K, double* smem, int64_t brow, int kt0) {
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // 0..7
-  const int wr = wave >> 1, wc = wave & 1;
-  const int fk = lane >> 4, fr = lane & 15;
-  double* As = smem;
-  double* Bs = smem + 2 * T2_BUFA;
-  double* Cw = C + (wr * 64 + fr) + (int64_t)(wc * 64 + fk) * ldc;
-  double4_t acc[4][4];
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) acc[m][n][r] = Cw[m * 16 + (int64_t)(n * 16 + 4 * r) * ldc];
-
-  // wave w stages k-slices w and w + 8 of a k-tile: A rows 0..127, A rows 128..255, B rows 0..127 -- three 1-KiB wave-instructions each
-  int64_t ldbk;
-  const double* Ag = A + 2 * lane + (int64_t)wave * lda;                                   // k-slice `wave` of k-tile 0
-  const double* Bg = strip_ktile<true>(Bpk, n_pad, brow, kt0, lane, wave, ldbk);
-  auto dma2 = [&](const double* ag, const double* bg, int64_t ldb_, double* Asb, double* Bsb) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      __builtin_amdgcn_global_load_lds((gptr_t)(ag + (int64_t)(8 * i) * lda), (lptr_t)(Asb + (wave + 8 * i) * T2_LDA), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)(ag + 128 + (int64_t)(8 * i) * lda), (lptr_t)(Asb + (wave + 8 * i) * T2_LDA + 128), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)(bg + (int64_t)(8 * i) * ldb_), (lptr_t)(Bsb + (wave + 8 * i) * T2_LDB), 16, 0, 0);
-    }
-  };
-  constexpr int LGKM0 = 0xC07F;
-  const int KT = K / G_KB;
-  dma2(Ag, Bg, ldbk, As, Bs);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
-  if (KT > 1) {
-    Ag += (int64_t)G_KB * lda;
-    Bg = strip_ktile<true>(Bpk, n_pad, brow, kt0 + 1, lane, wave, ldbk);
-    dma2(Ag, Bg, ldbk, As + T2_BUFA, Bs + T2_BUFB);
-  }
-  const int foffA = fr + fk * T2_LDA, foffB = fr + fk * T2_LDB;
-  double a0[4], b0[4], a1[4], b1[4], a2[4], b2[4], a3[4], b3[4];
-  read_ops2(As + wr * 64 + foffA, Bs + wc * 64 + foffB, 0, a0, b0);
-  read_ops2(As + wr * 64 + foffA, Bs + wc * 64 + foffB, 1, a1, b1);
-  for (int kt = 0; kt < KT; ++kt) {
-    const int cur = kt & 1;
-    const double* Ac = As + cur * T2_BUFA + wr * 64 + foffA;
-    const double* Bc = Bs + cur * T2_BUFB + wc * 64 + foffB;
-    const double* An = As + (1 - cur) * T2_BUFA + wr * 64 + foffA;
-    const double* Bn = Bs + (1 - cur) * T2_BUFB + wc * 64 + foffB;
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    read_ops2(Ac, Bc, 2, a2, b2);
-    mma_step<1>(a0, b0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    read_ops2(Ac, Bc, 3, a3, b3);
-    mma_step<1>(a1, b1, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    if (kt + 1 < KT) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (kt + 2 < KT) {
-        Ag += (int64_t)G_KB * lda;
-        if (((kt0 + kt + 2) % (NB / 16)) == 0) Bg = strip_ktile<true>(Bpk, n_pad, brow, kt0 + kt + 2, lane, wave, ldbk);
-        else Bg += (int64_t)G_KB * ldbk;
-        dma2(Ag, Bg, ldbk, As + cur * T2_BUFA, Bs + cur * T2_BUFB);
-      }
-      read_ops2(An, Bn, 0, a0, b0);
-    }
-    mma_step<1>(a2, b2, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(LGKM0);
-    if (kt + 1 < KT) read_ops2(An, Bn, 1, a1, b1);
-    mma_step<1>(a3, b3, acc);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) Cw[m * 16 + (int64_t)(n * 16 + 4 * r) * ldc] = acc[m][n][r];
-}
-
-// blockIdx -> logical id so that each XCD (blocks b, b+8, ... share one) owns a contiguous id range
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-// C[M x N] -= A * B^T, 1-D grid of (M/128)*(N/128) tiles visited in 8-row groups.  ROLE only gives
-// each use its own symbol (rocprof / event profiler tell them apart): in-panel update (K = 128),
-// predict-side right update (K = 512), posterior-covariance SYRK (K = n).
-template <int ROLE>
-__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(double* C, int64_t ldc, const double* A, int64_t lda,
-                                                         const double* B, int64_t ldb, int tiles_m, int tiles_n, int K,
-                                                         int lower, int group) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  // Normally one tile per workgroup (gridDim.x == ntiles).  GPRC_PERSIST=N launches N workgroups that walk the tile list
-  // with stride N instead (N a multiple of 8 keeps the XCD-contiguous id ranges); measured 4% slower at N=512.
-  const unsigned ntiles = (unsigned)tiles_m * (unsigned)tiles_n;
-  const int width = group * tiles_n;
-  for (unsigned t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    // (PK_INV_GEMM: a tile's length falls with its row, so the ids stay round-robin over the XCDs -- every XCD the same mix, as solve_left_kernel)
-    const unsigned id = ROLE == PK_INV_GEMM ? t : xcd_remap(t, ntiles);
-    const int g = id / width, first_m = g * group;
-    const int gsize = (tiles_m - first_m < group) ? (tiles_m - first_m) : group;
-    const int tr = first_m + (int)(id % width) % gsize;
-    const int tc = (int)(id % width) / gsize;
-    if (lower && tc > tr) continue;
-    // PK_INV_GEMM (K_y^-1 = L^-T L^-1, A = B = L^-T, lower tiles): rows tr 128.. of an UPPER-triangular matrix are zero left of
-    // column tr 128 >= tc 128, so the products start there -- n^3 / 3 instead of n^3; what is skipped is exact zeros
-    const int64_t k0 = ROLE == PK_INV_GEMM ? (int64_t)tr * 128 : 0;
-    gemm_tile_128<false>(C + (int64_t)tr * 128 + (int64_t)tc * 128 * ldc, ldc, A + (int64_t)tr * 128 + k0 * lda, lda,
-                         B + (int64_t)tc * 128 + k0 * ldb, ldb, K - (int)k0, smem);
-    __syncthreads();  // every wave has left the tile (LDS reads done) before the next tile's first DMA lands
-  }
-}
-
-// X[M x 128] := X * W^T (W = inverse of the diagonal block, lower triangular), in place: a workgroup
-// owns a full 128-row strip, and every load of it precedes the epilogue stores.
-template <bool SSQ>
-__global__ __launch_bounds__(256, 2) void trsm_panel_kernel(double* X, int64_t ldx, const double* winv, double* ssq) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* Xs = X + (int64_t)blockIdx.x * 128;
-  gemm_tile_128<true, false, false, SSQ>(Xs, ldx, Xs, ldx, winv, 128, 128, smem, 0, 0, 0, SSQ ? ssq + (int64_t)blockIdx.x * 128 : nullptr);
-}
-
-// Trailing update over the packed layout: for every target panel q in {q_begin, q_begin+stride, ..}
-// C_q -= L_p[rows of q] * L_p[rows of q's diagonal block]^T, lower tiles only.
-__global__ __launch_bounds__(256, 2) void trailing_kernel(double* packed, int64_t n_pad, int p, int q_begin, int q_stride,
-                                                          int n_targets, int ntiles) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int P = (int)(n_pad / NB);
-  constexpr int DIAG_TILES = TPP * (TPP + 1) / 2;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {  // persistent, as gemm_nt_kernel
-    int id = (int)xcd_remap((unsigned)t, (unsigned)ntiles);
-    // locate the target panel: panel q holds TPP*TPP*(P-q) - TPP*(TPP-1)/2 lower tiles
-    int q = q_begin, s = 0;
-    for (; s < n_targets; ++s, q += q_stride) {
-      const int tq = TPP * TPP * (P - q) - TPP * (TPP - 1) / 2;
-      if (id < tq) break;
-      id -= tq;
-    }
-    if (s >= n_targets) continue;
-    int tr, tc;
-    if (id < DIAG_TILES) {  // the diagonal NB x NB block: lower tiles (0,0) (1,0) (1,1) (2,0) ...
-      tr = 0;
-      while ((tr + 1) * (tr + 2) / 2 <= id) ++tr;
-      tc = id - tr * (tr + 1) / 2;
-    } else {
-      tr = TPP + (id - DIAG_TILES) / TPP;
-      tc = (id - DIAG_TILES) % TPP;
-    }
-    const int64_t ldp = panel_ld(n_pad, p), ldq = panel_ld(n_pad, q);
-    const double* Lp = packed + panel_offset(n_pad, p) + (int64_t)(q - p) * NB;  // row q*NB of panel p
-    double* Cq = packed + panel_offset(n_pad, q);
-    gemm_tile_128<false>(Cq + (int64_t)tr * 128 + (int64_t)tc * 128 * ldq, ldq, Lp + (int64_t)tr * 128, ldp,
-                         Lp + (int64_t)tc * 128, ldp, NB, smem);
-    __syncthreads();
-  }
-}
-
-
-// Left-looking step of the predict solve: the columns of panels [j, j + G) of vt receive, in ONE pass with the C tile
-// held in the accumulators, everything the right-looking form would have subtracted panel by panel:
-//   vt[:, j NB : (j+G) NB] -= vt[:, 0 : j NB] * L[j NB : (j+G) NB, 0 : j NB]^T          (K = j NB).
-// Same products in the same order (k ascending from the loaded C value), so the result is bit-identical; what
-// changes is that a C tile is loaded and stored once instead of j times -- the per-tile prologue (C preload + first
-// DMA, ~7 % of a K = 512 tile during which the tile's waves issue no MFMA) is paid once per j NB of K.
-// [kp0, kp1): the source panels of this launch (kp0 = 0, kp1 = j: the whole pass; GPRC_KCHUNK splits it into K-chunks)
-// tri_row0 >= 0 (fit()'s gradient: the rows of vt are rows tri_row0, tri_row0 + 1, ... of the IDENTITY, so row i is zero left of
-// column tri_row0 + i and stays zero there): a tile's pass starts at its first row's column instead of column 0 -- the skipped
-// products are exact zeros, so the bits are those of the full pass -- and a tile whose rows start right of the pass has nothing to do.
-__global__ __launch_bounds__(256, 2) void solve_left_kernel(double* vt, int64_t ldv, const double* packed, int64_t n_pad, int j,
-                                                            int tiles_m, int tiles_n, int group, int kp0, int kp1, int64_t tri_row0) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const unsigned ntiles = (unsigned)tiles_m * (unsigned)tiles_n;
-  // (the triangular form keeps block id -> tile: a tile's length falls with its row, and XCD-contiguous id ranges would hand one XCD
-  //  all the long tiles and another none -- measured 27 TFLOP/s; round-robin over the XCDs every one gets the same mix)
-  const unsigned id = tri_row0 >= 0 ? blockIdx.x : xcd_remap(blockIdx.x, ntiles);
-  const int width = group * tiles_n;
-  const int g = id / width, first_m = g * group;
-  const int gsize = (tiles_m - first_m < group) ? (tiles_m - first_m) : group;
-  const int tr = first_m + (int)(id % width) % gsize;
-  const int tc = (int)(id % width) / gsize;
-  const int64_t col = (int64_t)j * NB + (int64_t)tc * 128;
-  int kt_first = kp0 * (NB / 16);
-  const int kt_end = kp1 * (NB / 16);
-  if (tri_row0 >= 0) {
-    const int64_t first_col = tri_row0 + (int64_t)tr * 128;      // a multiple of 128: whole k-tiles
-    if (first_col / 16 > kt_first) kt_first = (int)(first_col / 16);
-    if (kt_first >= kt_end) return;
-  }
-  gemm_tile_128<false, true>(vt + (int64_t)tr * 128 + col * ldv, ldv, vt + (int64_t)tr * 128 + (int64_t)kt_first * 16 * ldv, ldv, packed, n_pad,
-                             (kt_end - kt_first) * 16, smem, col, 0, kt_first);
-}
-
-
-// The predict's in-panel solve in ONE launch: panel p of vt := vt L^-T once everything left of the panel has been applied.
-// Per 128-row strip of vt the four 128-column sub-steps are C(.,j) -= vt(., panel columns < j) L(j, < j)^T  (K = 128 j), then
-// C(.,j) := C(.,j) Winv_j^T [+ the per-row sums of squares of the finished block].  L and Winv are final, so strips are
-// independent: what used to be seven dependent launches per panel (each draining the GPU, each latency-bound for the 64-tile
-// slices of an 8-rank run) is one workgroup per strip running its seven tiles back to back.  The same gemm_tile_128 calls in the
-// same order per strip: bit-identical.
-template <bool SSQ>
-__global__ __launch_bounds__(256, 2) void solve_panel_fused_kernel(double* vt, int64_t ldv, const double* packed, int64_t n_pad, int p,
-                                                                   const double* winv, double* sspart, int64_t m_pad) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int64_t ld = panel_ld(n_pad, p);
-  const double* pan = packed + panel_offset(n_pad, p);
-  double* strip = vt + (int64_t)blockIdx.x * 128 + (int64_t)p * NB * ldv;   // my 128 rows, first column of the panel
-  for (int j = 0; j < TPP; ++j) {
-    double* C = strip + (int64_t)j * NBI * ldv;
-    if (j > 0) {
-      gemm_tile_128<false>(C, ldv, strip, ldv, pan + (int64_t)j * NBI, ld, j * NBI, smem);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the updated block is re-read (LDS-DMA) by all four waves
-      __syncthreads();
-    }
-    const double* wblk = winv + ((int64_t)p * TPP + j) * NBI * NBI;
-    double* ssq = SSQ ? sspart + ((int64_t)p * TPP + j) * m_pad + (int64_t)blockIdx.x * 128 : nullptr;
-    gemm_tile_128<true, false, false, SSQ>(C, ldv, C, ldv, wblk, 128, 128, smem, 0, 0, 0, ssq);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // block j is an operand of the next sub-step's update
-    __syncthreads();
-  }
-}
-
-// the same pass on 256 x 128 macro-tiles (GPRC_TILE256=1; m_pad a multiple of 256)
-__global__ __launch_bounds__(512) void solve_left_kernel256(double* vt, int64_t ldv, const double* packed, int64_t n_pad, int j,
-                                                            int tiles_m, int tiles_n, int group, int kp0, int kp1) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const unsigned ntiles = (unsigned)tiles_m * (unsigned)tiles_n;
-  const unsigned id = xcd_remap(blockIdx.x, ntiles);
-  const int width = group * tiles_n;
-  const int g = id / width, first_m = g * group;
-  const int gsize = (tiles_m - first_m < group) ? (tiles_m - first_m) : group;
-  const int tr = first_m + (int)(id % width) % gsize;
-  const int tc = (int)(id % width) / gsize;
-  const int64_t col = (int64_t)j * NB + (int64_t)tc * 128;
-  gemm_tile_256x128_seg(vt + (int64_t)tr * 256 + col * ldv, ldv, vt + (int64_t)tr * 256 + (int64_t)kp0 * NB * ldv, ldv, packed, n_pad,
-                        (kp1 - kp0) * NB, smem, col, kp0 * (NB / 16));
-}
-
-// Trailing update by a RANGE of source panels [p_begin, p_end) in one pass: every lower tile of the target panels
-// q_begin, q_begin + q_stride, ... (n_targets of them) receives
-//   A[R.., C..] -= L[R.., p_begin NB : p_end NB] * L[C.., p_begin NB : p_end NB]^T,
-// both operand strips walking through the packed panels.  Same products, same order as the single-panel passes
-// p = p_begin .. p_end - 1 (k ascending from the loaded C value): bit-identical, one C load/store and one tile prologue
-// instead of p_end - p_begin.  p_begin = 0 is the left-looking sweep of one GPU; the multi-rank driver uses it to apply
-// the panels it has received in batches.
-__global__ __launch_bounds__(256, 2) void trailing_range_kernel(double* packed, int64_t n_pad, int p_begin, int p_end, int q_begin,
-                                                                int q_stride, int n_targets, int ntiles) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int P = (int)(n_pad / NB);
-  constexpr int DIAG_TILES = TPP * (TPP + 1) / 2;
-  int id = (int)xcd_remap(blockIdx.x, (unsigned)ntiles);
-  int q = q_begin, s = 0;
-  for (; s < n_targets; ++s, q += q_stride) {
-    const int tq = TPP * TPP * (P - q) - TPP * (TPP - 1) / 2;
-    if (id < tq) break;
-    id -= tq;
-  }
-  if (s >= n_targets) return;
-  int tr, tc;
-  if (id < DIAG_TILES) {
-    tr = 0;
-    while ((tr + 1) * (tr + 2) / 2 <= id) ++tr;
-    tc = id - tr * (tr + 1) / 2;
-  } else {
-    tr = TPP + (id - DIAG_TILES) / TPP;
-    tc = (id - DIAG_TILES) % TPP;
-  }
-  const int64_t ldq = panel_ld(n_pad, q);
-  double* Cq = packed + panel_offset(n_pad, q);
-  const int64_t row = (int64_t)q * NB + (int64_t)tr * 128, col = (int64_t)q * NB + (int64_t)tc * 128;
-  gemm_tile_128<false, true, true>(Cq + (int64_t)tr * 128 + (int64_t)tc * 128 * ldq, ldq, packed, n_pad, packed, n_pad,
-                                   (p_end - p_begin) * NB, smem, col, row, p_begin * (NB / 16));
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // One launch per 512-column panel: diagonal blocks, panel solves and in-panel updates of all four 128-column sub-steps.
@@ -1106,27 +83,29 @@ __device__ __attribute__((noinline)) void wait_diag(int site, int need, int seen
 // microsecond instead of every ~50 ns.  Hundreds of workgroups polling flags and counters at full rate slow every device-scope access
 // down -- the chain's own publishes and polls included (measured with the round-3 tile core, whose faster tiles left the sweep's
 // workgroups waiting longer: ticket atomics 6 -> 16 us, n = 8192 factorisation 6.27 -> 6.71 ms; tools/sweep_prof.py).
-__device__ __forceinline__ void poll_pause(bool relaxed) {
-  if (relaxed) __builtin_amdgcn_s_sleep(32);      // 32 x 64 clocks ~ 0.9 us
-  else __builtin_amdgcn_s_sleep(2);
-}
+__device__ __forceinline__ void relaxed_pause() { __builtin_amdgcn_s_sleep(32); }   // 32 x 64 clocks ~ 0.9 us
 
-__device__ __forceinline__ void panel_flag_wait(int* flag, PanelSync* sy, int* info, bool relaxed = false) {   // the whole workgroup calls it
+// THE bounded wait; the whole workgroup calls it.  One lane polls -- satisfied() loads the awaited word(s) with relaxed agent-scope loads and
+// compares -- and pauses between two looks (s_sleep SLEEP; relaxed: relaxed_pause instead); at every 256th miss it checks the two ways out every
+// wave reaches.  record(site) leaves the wait_diag record of what was still missing.  Then the acquire side of the hand-off protocol.
+template <int SITE, int SLEEP, typename Satisfied, typename Record>
+__device__ __forceinline__ void bounded_wait(PanelSync* sy, int* info, bool relaxed, Satisfied satisfied, Record record) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's own stores: its team-mates re-read them after the barrier
   if (threadIdx.x == 0) {
     int spins = 0;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-      poll_pause(relaxed);
+    while (!satisfied()) {
+      if (relaxed) relaxed_pause();
+      else __builtin_amdgcn_s_sleep(SLEEP);
       if ((++spins & 255) != 0) continue;
       // somebody has already given up (e.g. a profiler that serialises dispatches keeps producer and consumer kernels apart): every
       // later wait of the factorisation returns at once instead of running out its own bound
-      if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == GPRC_INFO_WAIT_TIMEOUT) { wait_diag(11, 1, 0, flag, sy); break; }
+      if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == GPRC_INFO_WAIT_TIMEOUT) { record(SITE + 10); break; }
       // exit condition every wave reaches (a producer that never publishes must not leave this workgroup spinning on the GPU
       // for ever): after WAIT_LIMIT_TICKS of wall time give up, let the grid drain, and tell the host through the ONE word it
       // always reads after a factorisation -- info = GPRC_INFO_WAIT_TIMEOUT (< 0; LAPACK infos are > 0)
       if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) {
-        wait_diag(1, 1, 0, flag, sy);
+        record(SITE);
         __hip_atomic_store(&sy->failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         atomicExch(info, GPRC_INFO_WAIT_TIMEOUT);
         break;
@@ -1136,6 +115,11 @@ __device__ __forceinline__ void panel_flag_wait(int* flag, PanelSync* sy, int* i
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
+}
+#define GPRC_PEEK(word) __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+__device__ __forceinline__ void panel_flag_wait(int* flag, PanelSync* sy, int* info, bool relaxed = false) {
+  bounded_wait<1, 2>(sy, info, relaxed, [&] { return GPRC_PEEK(flag) != 0; }, [&](int site) { wait_diag(site, 1, 0, flag, sy); });
 }
 
 __device__ __forceinline__ void panel_flag_publish(int* flag) {               // the whole workgroup calls it
@@ -1148,55 +132,14 @@ __device__ __forceinline__ void panel_flag_publish(int* flag) {               //
   }
 }
 
-__device__ __forceinline__ void panel_ready_wait(int* ctr, int need, PanelSync* sy, int* info, bool relaxed = false) {   // the whole workgroup calls it
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (threadIdx.x == 0) {
-    int spins = 0;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-      poll_pause(relaxed);
-      if ((++spins & 255) != 0) continue;
-      if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == GPRC_INFO_WAIT_TIMEOUT) {
-        wait_diag(12, need, __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ctr, sy);
-        break;
-      }
-      if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) {   // bounded in wall time (see panel_flag_wait)
-        wait_diag(2, need, __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ctr, sy);
-        __hip_atomic_store(&sy->failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        atomicExch(info, GPRC_INFO_WAIT_TIMEOUT);
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
+__device__ __forceinline__ void panel_ready_wait(int* ctr, int need, PanelSync* sy, int* info, bool relaxed = false) {
+  bounded_wait<2, 2>(sy, info, relaxed, [&] { return GPRC_PEEK(ctr) >= need; }, [&](int site) { wait_diag(site, need, GPRC_PEEK(ctr), ctr, sy); });
 }
 
 // waits until the 8-bit field at `shift` of *ctr has reached `need` (the look-ahead strips' per-sub-step counts in LA)
-__device__ __forceinline__ void panel_field_wait(int* ctr, int shift, int need, PanelSync* sy, int* info) {   // the whole workgroup calls it
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (threadIdx.x == 0) {
-    int spins = 0;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (((__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> shift) & 0xff) < need) {
-      __builtin_amdgcn_s_sleep(2);
-      if ((++spins & 255) != 0) continue;
-      if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == GPRC_INFO_WAIT_TIMEOUT) {
-        wait_diag(13, need << shift, __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ctr, sy);
-        break;
-      }
-      if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) {   // bounded in wall time (see panel_flag_wait)
-        wait_diag(3, need << shift, __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ctr, sy);
-        __hip_atomic_store(&sy->failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        atomicExch(info, GPRC_INFO_WAIT_TIMEOUT);
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
+__device__ __forceinline__ void panel_field_wait(int* ctr, int shift, int need, PanelSync* sy, int* info) {
+  bounded_wait<3, 2>(sy, info, false, [&] { return ((GPRC_PEEK(ctr) >> shift) & 0xff) >= need; },
+                     [&](int site) { wait_diag(site, need << shift, GPRC_PEEK(ctr), ctr, sy); });
 }
 
 __device__ __forceinline__ void panel_count_publish(int* ctr, int add) {      // the whole workgroup calls it
@@ -1232,8 +175,6 @@ constexpr int GPRC_CHAIN_PROF_PANEL = GPRC_CHAIN_PROF;
 #else
 constexpr int GPRC_CHAIN_PROF_PANEL = -1;
 #endif
-constexpr int CHAIN_HELPERS = 4;                  // 32-row slices of a 128-row block
-constexpr int PANEL_DIAG_TILES = TPP * (TPP + 1) / 2;   // lower 128 x 128 tiles of a panel's diagonal block
 constexpr int PANEL_LA_TILES = TPP * TPP;             // tiles of a panel's rows [NB, 2 NB)
 constexpr int AUX_STRIDE = 2 * TPP + PANEL_LA_TILES;  // ints per panel in the sync block's last array: 2 TPP early-chunk flags, then the slice counts of the sweep's head tiles
 constexpr int CHAIN_LDS_LD = 48;                  // doubles per k-slice of the A image: 32 rows + 16 pad (consecutive k-slices 32 banks apart)
@@ -1251,33 +192,17 @@ __device__ unsigned long long g_chain_prof[64];
 
 // waits until ((*a >> sa) & ma) >= va and (b == null or ((*b >> sb) & mb) >= vb); the whole workgroup calls it; the polls fly together
 __device__ __forceinline__ void chain_wait2(int* a, int sa, int ma, int va, int* b, int sb, int mb, int vb, PanelSync* sy, int* info) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (threadIdx.x == 0) {
-    int spins = 0;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-      const int xa = (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> sa) & ma;
-      const int xb = b ? (__hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> sb) & mb : vb;
-      if (xa >= va && xb >= vb) break;
-      __builtin_amdgcn_s_sleep(1);
-      if ((++spins & 255) != 0) continue;
-      if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == GPRC_INFO_WAIT_TIMEOUT) {
-        if (xa < va) wait_diag(14, va << sa, __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a, sy);
-        else wait_diag(14, vb << sb, __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b, sy);
-        break;
-      }
-      if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) {   // bounded in wall time (see panel_flag_wait)
-        if (xa < va) wait_diag(4, va << sa, __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a, sy);
-        else wait_diag(4, vb << sb, __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b, sy);
-        __hip_atomic_store(&sy->failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        atomicExch(info, GPRC_INFO_WAIT_TIMEOUT);
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
+  int xa, xb;
+  bounded_wait<4, 1>(sy, info, false,
+                     [&] {
+                       xa = (GPRC_PEEK(a) >> sa) & ma;
+                       xb = b ? (GPRC_PEEK(b) >> sb) & mb : vb;
+                       return xa >= va && xb >= vb;
+                     },
+                     [&](int site) {
+                       if (xa < va) wait_diag(site, va << sa, GPRC_PEEK(a), a, sy);
+                       else wait_diag(site, vb << sb, GPRC_PEEK(b), b, sy);
+                     });
 }
 
 // C (32 rows x 128 columns, column-major) = (SET ? 0 : C) -/+ A (32 x 128) B (128 x 128)^T on 512 threads: wave w the columns
@@ -1627,9 +552,8 @@ constexpr int SERVICE_WGS = SERVICE_H0 + CHAIN_HELPERS;
 __device__ __forceinline__ void panel_next_diag_role(double* smem, const double* pan, int64_t ld, double* Dn, int64_t ldn, int* info,
                                                      PanelSync* sy, int idx, int tid, unsigned long long* stamp, bool hand_last = false,
                                                      int* aux = nullptr) {
-  int tr = 0;
-  while ((tr + 1) * (tr + 2) / 2 <= idx) ++tr;
-  const int tc = idx - tr * (tr + 1) / 2;
+  int tr, tc;
+  diag_tile(idx, tr, tc);
   double* C = Dn + (int64_t)tr * 128 + (int64_t)tc * 128 * ldn;
   // aux (split chain; null otherwise): this role also applies, between its own k-chunks, the EARLY k-chunks of one look-ahead strip's
   // block -- with the chain down to ~200 us a look-ahead strip's ten tiles (~220 us on its one CU) had become the bound
@@ -1738,8 +662,9 @@ __global__ __launch_bounds__(512) void panel_service_kernel(double* packed, int6
 
 // First kernel of the caller's stream: one wave that returns once every service workgroup is resident.  Whatever waits on the
 // service is ordered behind it, so a GPU full of waiting workgroups can never keep the service out.
-// limit_ticks: patience in s_memrealtime ticks (WAIT_LIMIT_TICKS; the test hook GPRC_TEST_SERVICE_TIMEOUT passes 0 with an
-// unreachable `need` once: the gate gives up at its first look, every wait behind it returns at once, info = GPRC_INFO_WAIT_TIMEOUT).
+// (Not a bounded_wait either: one wave, nobody to hand over to -- no fence, no barrier, no PanelSync.)
+// limit_ticks: patience in s_memrealtime ticks (WAIT_LIMIT_TICKS; the test hook GPRC_TEST_SERVICE_TIMEOUT, launch_service_gate's `forced`, passes 0 with an
+// unreachable `need`: the gate gives up at its first look, every wait behind it returns at once, info = GPRC_INFO_WAIT_TIMEOUT).
 __global__ void service_gate_kernel(int* alive, int need, int* info, unsigned long long limit_ticks) {
   if (threadIdx.x == 0) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -1786,7 +711,7 @@ __global__ __launch_bounds__(256, 2) void trailing_service_kernel(double* packed
   const int P = (int)(n_pad / NB);
   constexpr int DIAG = PANEL_DIAG_TILES;
   PanelSync* sy = sy_base + p;
-  const int T0 = TPP * TPP * (P - p - 1) - TPP * (TPP - 1) / 2;   // tiles of panel p + 1 (>= DIAG + LAT: there are >= 2 targets)
+  const int T0 = panel_tiles(P, p + 1);   // tiles of panel p + 1 (>= DIAG + LAT: there are >= 2 targets)
   const int n_first = T0 - DIAG;
   // Only the first `base` workgroups (the waiting roles and what they wait for) take tickets; the rest map block id -> tile directly,
   // so that block id mod 8 -- the XCD -- still selects a contiguous range of tiles (ticket order would scatter an XCD's tiles and
@@ -1825,7 +750,7 @@ __global__ __launch_bounds__(256, 2) void trailing_service_kernel(double* packed
       s = 2;
       for (;; ++s) {
         if (p + 1 + s >= q_end) return;
-        const int tq = TPP * TPP * (P - p - 1 - s) - TPP * (TPP - 1) / 2;
+        const int tq = panel_tiles(P, p + 1 + s);
         if (id < tq) break;
         id -= tq;
       }
@@ -1834,14 +759,7 @@ __global__ __launch_bounds__(256, 2) void trailing_service_kernel(double* packed
   }
   const int q = p + 1 + s;
   int tr, tc;
-  if (local < DIAG) {
-    tr = 0;
-    while ((tr + 1) * (tr + 2) / 2 <= local) ++tr;
-    tc = local - tr * (tr + 1) / 2;
-  } else {
-    tr = TPP + (local - DIAG) / TPP;
-    tc = (local - DIAG) % TPP;
-  }
+  panel_tile(local, tr, tc);
   if (s == 0) panel_ready_wait(&sy->LA, TPP << (8 * (TPP - 1)), sy, info);
   if (t == 0) SERVICE_STAMP(p, 10);
   const int64_t ldp = panel_ld(n_pad, p), ldq = panel_ld(n_pad, q);
@@ -1893,6 +811,34 @@ struct SweepSync {          // views into the sync block behind PanelSync[P], re
   int* aux;                 // [P][AUX_STRIDE]: from 2 TPP on, the finished 32-row slices of the head tiles of the update INTO panel q (sweep_slice_32)
 };
 
+// The sync block of a factorisation under the service (zeroed by the caller, stream-ordered before the first launch), carved in ONE place:
+//   sy[P]                   the flags of every panel
+//   ready[3 P]              ready, ready_la, ready_d2 (P ints each)
+//   resident[16]            the service's "resident" counter (and padding)
+//   rowcnt[P][TPP P]        per panel, per 128-row strip, the tiles of that strip which have received the previous panel
+//   sw                      the persistent sweep's flags (trailing_sweep_kernel): stripdone[P][TPP P], rest_ticket[P][8], ver[P][TPP P][TPP],
+//                           aux[P][AUX_STRIDE]  (panel_service_kernel reaches aux from `ready`: the same sums)
+struct SyncView {
+  PanelSync* sy;
+  int *ready, *resident, *rowcnt;
+  SweepSync sw;
+  size_t bytes;
+  SyncView(void* sync, int64_t P) : sy(static_cast<PanelSync*>(sync)), bytes((size_t)P * sizeof(PanelSync)) {
+    auto carve = [&](int64_t ints) {
+      int* at = reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(sync) + bytes);
+      bytes += (size_t)ints * sizeof(int);
+      return at;
+    };
+    ready = carve(3 * P);
+    resident = carve(16);
+    rowcnt = carve(P * TPP * P);
+    sw.stripdone = carve(P * TPP * P);
+    sw.rest_ticket = carve(8 * P);
+    sw.ver = carve(P * TPP * P * TPP);
+    sw.aux = carve(P * AUX_STRIDE);
+  }
+};
+
 // a ticket of counter ctr, or `limit` when it is used up (one lane; one device-scope round trip -- a counter past its limit is harmless)
 __device__ __forceinline__ int sweep_take(int* ctr, int limit) {
   const int t = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1901,6 +847,7 @@ __device__ __forceinline__ int sweep_take(int* ctr, int limit) {
 
 // waits until *a >= va, *b >= vb, *c >= vc (null pointers are skipped; the three polls fly together), then one acquire for all.
 // false: somebody's wait has timed out (info = GPRC_INFO_WAIT_TIMEOUT) -- the caller leaves.
+// (Not a bounded_wait: its checks come at the first miss and every 64th, and it hands a result to the whole workgroup through sh_dead.)
 __device__ __forceinline__ bool sweep_wait3(int* a, int va, int* b, int vb, int* c, int vc, int* failed, int* info, int* sh_dead) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (threadIdx.x == 0) {
@@ -1911,14 +858,14 @@ __device__ __forceinline__ bool sweep_wait3(int* a, int va, int* b, int vb, int*
       const int xb = b ? __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : vb;
       const int xc = c ? __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : vc;
       if (xa >= va && xb >= vb && xc >= vc) break;
-      poll_pause(true);
+      relaxed_pause();
       if ((++spins & 63) != 1) continue;              // at the first miss and every 64th from there
       if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == GPRC_INFO_WAIT_TIMEOUT) {
         if (xa < va) wait_diag(15, va, xa, a, failed - 1); else if (xb < vb) wait_diag(15, vb, xb, b, failed - 1); else wait_diag(15, vc, xc, c, failed - 1);
         *sh_dead = 1;
         break;
       }
-      if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) {   // bounded in wall time (see panel_flag_wait)
+      if (__builtin_amdgcn_s_memrealtime() - t0 > WAIT_LIMIT_TICKS) {   // bounded in wall time (see bounded_wait)
         if (xa < va) wait_diag(5, va, xa, a, failed - 1); else if (xb < vb) wait_diag(5, vb, xb, b, failed - 1); else wait_diag(5, vc, xc, c, failed - 1);
         __hip_atomic_store(failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         atomicExch(info, GPRC_INFO_WAIT_TIMEOUT);
@@ -2010,12 +957,12 @@ struct SweepCursor {
   __device__ void enter(int p_, int P, int64_t n_pad, int q_end) {
     p = p_; phase = 0;
     constexpr int DIAG = PANEL_DIAG_TILES;
-    const int T0 = TPP * TPP * (P - p - 1) - TPP * (TPP - 1) / 2;   // lower tiles of panel p + 1
+    const int T0 = panel_tiles(P, p + 1);                           // lower tiles of panel p + 1
     n_first = T0 - DIAG;                                            // ... without its diagonal block (the service's)
     const int ld1 = (int)(panel_ld(n_pad, p + 1) / 128);
     nstrips = ld1 > 2 * TPP ? ld1 - 2 * TPP : 0;
     int ntiles = -DIAG;
-    for (int q = p + 1; q < q_end; ++q) ntiles += TPP * TPP * (P - q) - TPP * (TPP - 1) / 2;
+    for (int q = p + 1; q < q_end; ++q) ntiles += panel_tiles(P, q);
     nrest = ntiles - n_first;
     T1 = T0 - TPP * TPP;                                            // lower tiles of panel p + 2
   }
@@ -2075,7 +1022,7 @@ __global__ __launch_bounds__(256, 2) void trailing_sweep_kernel(double* packed, 
         id -= cur.T1;
         int s = 2;
         for (; cur.p + 1 + s < q_end; ++s) {
-          const int tq = TPP * TPP * (P - cur.p - 1 - s) - TPP * (TPP - 1) / 2;
+          const int tq = panel_tiles(P, cur.p + 1 + s);
           if (id < tq) break;
           id -= tq;
         }
@@ -2106,14 +1053,7 @@ __global__ __launch_bounds__(256, 2) void trailing_sweep_kernel(double* packed, 
       // ---- one tile of the update with panel p: target q = p + 1 + s, tile (tr, tc) of that panel (kind 2: 32 rows of it)
       const int q = p + 1 + it.s, local = it.local;
       int tr, tc;
-      if (local < DIAG) {
-        tr = 0;
-        while ((tr + 1) * (tr + 2) / 2 <= local) ++tr;
-        tc = local - tr * (tr + 1) / 2;
-      } else {
-        tr = TPP + (local - DIAG) / TPP;
-        tc = (local - DIAG) % TPP;
-      }
+      panel_tile(local, tr, tc);
       const int stage = p - p_begin;                                // versions the tiles of this panel's update wait for
       const int ra = (q - p) * TPP + tr, rb = (q - p) * TPP + tc;   // the operands' 128-row strips of panel p
       int* verp = sw.ver + ((int64_t)q * TPP * P + tr) * TPP + tc;
@@ -2172,66 +1112,22 @@ __global__ __launch_bounds__(256, 2) void trailing_sweep_kernel(double* packed, 
   SWEEP_T(tkern1);
   SWEEP_ADD(7, tkern0, tkern1);
 }
-}  // namespace
-}  // namespace gprc
-// include/gprc_native.h: the raw records of the timed-out waits, see wait_diag; clears them
-extern "C" __attribute__((visibility("default"))) int gprc_prof_wait_timeout(int* out, int ints) {   // out[0]: records written; 8 ints per record from out[8]
-  if (!out || ints < 8) return -1;
-  const size_t bytes = sizeof(int) * (size_t)std::min(ints, 8 * (gprc::WAIT_DIAG_RECORDS + 1));
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gprc::g_wait_diag), bytes) != hipSuccess) return -1;
-  static const int z[8 * (gprc::WAIT_DIAG_RECORDS + 1)] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(gprc::g_wait_diag), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-namespace gprc {
-namespace {
-#ifdef GPRC_CHAIN_PROF
-}  // namespace
-}  // namespace gprc
-extern "C" __attribute__((visibility("default"))) int gprc_debug_chain_prof(unsigned long long* out64) {
-  return hipMemcpyFromSymbol(out64, HIP_SYMBOL(gprc::g_chain_prof), 512) == hipSuccess ? 0 : -1;
-}
-namespace gprc {
-namespace {
-#endif
-#ifdef GPRC_SWEEP_PROF
-}  // namespace
-}  // namespace gprc
-extern "C" __attribute__((visibility("default"))) int gprc_debug_sweep_prof(unsigned long long* out8, int reset) {
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(gprc::g_sweep_prof), 64) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[8] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(gprc::g_sweep_prof), z, 64) != hipSuccess) return -1; }
-  return 0;
-}
-namespace gprc {
-namespace {
-#endif
 
 }  // namespace
 
 int launch_potf2_inv(hipStream_t s, double* A, int64_t lda, double* winv, int* info_dev, int col0) {
   ProfScope ps(s, PK_POTF2, 128.0 * 128 * 128 / 3 * 2, 8.0 * 3 * 128 * 128);
-  static bool attr_set[MAX_DEVICES] = {};  // the attribute is per device: one process may hold contexts on several
-  const size_t smem = PB_SMEM_DOUBLES * sizeof(double);
-  int dev = 0;
-  GPRC_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= MAX_DEVICES || !attr_set[dev]) {
-    GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(potf2_inv_blocked_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    if (dev >= 0 && dev < MAX_DEVICES) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(potf2_inv_blocked_kernel, dim3(1), dim3(1024), smem, s, A, lda, winv, info_dev, col0);
+  GPRC_TRY(ensure_dynamic_lds<potf2_inv_blocked_kernel>(PB_SMEM_BYTES));
+  hipLaunchKernelGGL(potf2_inv_blocked_kernel, dim3(1), dim3(1024), PB_SMEM_BYTES, s, A, lda, winv, info_dev, col0);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_panel_fused(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync16) {
-  static bool attr_set[MAX_DEVICES] = {};
-  const size_t smem = PB_SMEM_DOUBLES * sizeof(double);
+// trace: 0 none; 1 the factor role stamps its stages (24 x 8 bytes at sync16 + 64 .. sync16 + 256; read back with gprc_prof_panel_trace);
+// 2 the stamps are those of the SECOND diagonal block's potf2 instead.  Measurement only.
+int launch_panel_fused(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync16, int trace) {
   static_assert(PB_SMEM_DOUBLES >= 2 * G_SMEM_DOUBLES, "two GEMM teams must fit beside each other in the factor role's LDS");
-  int dev = 0;
-  GPRC_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= MAX_DEVICES || !attr_set[dev]) {
-    GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    if (dev >= 0 && dev < MAX_DEVICES) attr_set[dev] = true;
-  }
+  GPRC_TRY(ensure_dynamic_lds<panel_fused_kernel>(PB_SMEM_BYTES));
   const int64_t ld = panel_ld(n_pad, p), S = ld / 128;
   const unsigned grid = (unsigned)(1 + TPP + (S - TPP + 1) / 2);
   GPRC_HIP(hipMemsetAsync(sync16, 0, sizeof(PanelSync), s));
@@ -2239,51 +1135,35 @@ int launch_panel_fused(hipStream_t s, double* packed, int64_t n_pad, int64_t p, 
   double fl = 0.0;
   for (int j = 0; j < TPP; ++j) fl += 2.0 * (double)(ld - j * NBI) * NBI * (j * NBI) + (double)(ld - (j + 1) * NBI) * NBI * NBI + 2.0 * NBI * NBI * NBI / 3.0;
   ProfScope ps(s, PK_PANEL_FUSED, fl, 8.0 * 2.0 * (double)ld * NB);
-  // GPRC_PANEL_TRACE=<p>: the factor role of panel p stamps its stages (24 x 8 bytes at sync + 64 .. sync + 256; read back with
-  // gprc_prof_panel_trace).  Measurement only.
-  static const long long trace_p = [] { const char* e = std::getenv("GPRC_PANEL_TRACE"); return e ? std::atoll(e) : -1LL; }();
-  unsigned long long* trace = (trace_p == p) ? reinterpret_cast<unsigned long long*>(static_cast<char*>(sync16) + 64) : nullptr;
-  static const int potf2_trace = std::getenv("GPRC_POTF2_TRACE") != nullptr;   // the stamps are those of the SECOND diagonal block's potf2 instead
-  hipLaunchKernelGGL(panel_fused_kernel, dim3(grid), dim3(512), smem, s, packed, n_pad, (int)p, winv, info_dev, reinterpret_cast<PanelSync*>(sync16), trace,
-                     potf2_trace);
+  unsigned long long* stamps = trace ? reinterpret_cast<unsigned long long*>(static_cast<char*>(sync16) + 64) : nullptr;
+  hipLaunchKernelGGL(panel_fused_kernel, dim3(grid), dim3(512), PB_SMEM_BYTES, s, packed, n_pad, (int)p, winv, info_dev, reinterpret_cast<PanelSync*>(sync16), stamps,
+                     trace == 2 ? 1 : 0);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
 
-static int ensure_gemm_attrs();
+size_t panel_service_sync_bytes(int64_t P) { return SyncView(nullptr, P).bytes; }
 
-// flags of every panel | ready, ready_la, ready_d2 (P ints each) + the service's "resident" counter | rowcnt (P x 4 P ints: per panel,
-// per 128-row strip, the tiles of that strip which have received the previous panel)
-// ... and behind them the persistent sweep's flags (trailing_sweep_kernel): stripdone[P][TPP P], rest_ticket[P][8], ver[P][TPP P][TPP]
-size_t panel_service_sync_bytes(int64_t P) {
-  return (size_t)P * sizeof(PanelSync) + (3 * (size_t)P + 16) * sizeof(int) + (size_t)P * TPP * P * sizeof(int) +
-         ((size_t)P * TPP * P + 8 * (size_t)P + (size_t)P * TPP * P * TPP) * sizeof(int) + (size_t)P * AUX_STRIDE * sizeof(int);   // ... and aux[P][AUX_STRIDE]
-}
-
-// sync: panel_service_sync_bytes(P) bytes of device memory, zeroed by the caller (stream-ordered before this launch)
 int launch_inv512(hipStream_t s, const double* packed, int64_t n_pad, const double* winv, double* inv, int64_t p_begin, int64_t p_end) {
   if (p_end <= p_begin) return 0;
-  GPRC_TRY(ensure_gemm_attrs());
-  hipLaunchKernelGGL(inv512_kernel, dim3((unsigned)((p_end - p_begin) * TPP)), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad, winv, inv,
-                     (int)p_begin);
+  GPRC_TRY(ensure_dynamic_lds<inv512_kernel>(G_SMEM_BYTES));
+  hipLaunchKernelGGL(inv512_kernel, dim3((unsigned)((p_end - p_begin) * TPP)), dim3(256), G_SMEM_BYTES, s, packed, n_pad, winv, inv, (int)p_begin);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
 
-// The split chain (four more resident CUs) where the panel chain weighs: below n_pad = 20480, i.e. wherever the whole matrix is ONE group
-// of the service (measured, same box, profiles/r03_chain_split.txt; in the grouped schedule beyond it makes no difference and the four
-// CUs stay with the update).  GPRC_CHAIN_SPLIT=0 / 1 forces it off / on at every size.
-bool chain_split(int64_t n_pad) {
-  static const int v = [] { const char* e = std::getenv("GPRC_CHAIN_SPLIT"); return e ? std::atoi(e) : -1; }();
-  return v >= 0 ? v != 0 : n_pad < 20480;
-}
+// two contexts may time out together: the records' copy-and-clear is one step (here and in gprc_prof_wait_timeout)
+static std::mutex g_wait_diag_host;
+static const int g_wait_diag_zero[8 * (WAIT_DIAG_RECORDS + 1)] = {};
 
 // the records the timed-out waits left (wait_diag), as text for the host's error message; clears them
 std::string wait_timeout_report() {
-  static int v[8 * (WAIT_DIAG_RECORDS + 1)];
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_wait_diag), sizeof(v)) != hipSuccess || v[0] == 0) return "";
-  static const int z[8 * (WAIT_DIAG_RECORDS + 1)] = {};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wait_diag), z, sizeof(z));
+  int v[8 * (WAIT_DIAG_RECORDS + 1)];
+  {
+    std::lock_guard<std::mutex> lock(g_wait_diag_host);
+    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_wait_diag), sizeof(v)) != hipSuccess || v[0] == 0) return "";
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wait_diag), g_wait_diag_zero, sizeof(g_wait_diag_zero));
+  }
   static const char* const site[] = {"?", "flag", "count", "field", "chain", "sweep", "gate"};
   std::string out = " [waits that gave up (+10: still waiting when somebody else had):";
   const int n = v[0] < WAIT_DIAG_RECORDS ? v[0] : WAIT_DIAG_RECORDS;
@@ -2296,53 +1176,25 @@ std::string wait_timeout_report() {
   return out + (v[0] > 8 ? "; ... " + std::to_string(v[0]) + " in all]" : "]");
 }
 
-// The SHARED service.  A service workgroup asks for the factor role's 149 KB of LDS, so nothing else fits on its CU -- 21 to 25 CUs
-// that, where the update is the bound, mostly sleep on their flags.  From n_pad = 13312 on, the 4-wave roles (all but the factor role and
-// the chain helpers, whose 8 waves x 256 VGPRs fill a CU) are launched on their own, on a second side stream, with a GEMM team's LDS only
-// (launch_panel_service, part 2): ONE sweep workgroup then fits beside each of them and has the CU's matrix cores while the role waits.
-// Measured, same box (profiles/r03_chain_split.txt): n = 14336 19.45 -> 19.07 ms, 16384 27.3 -> 26.4, 18432 37.55 -> 35.97, 24576
-// 79.7 -> 78.9, 32768 172.5 -> 170.4, 65536 unchanged; 12288 and below unchanged or slower (the chain's own tiles run at half rate
-// beside a busy sweep workgroup), hence the threshold.  Raising the roles' wave priority (s_setprio 3) changes nothing measurable; it
-// stays.  GPRC_SERVICE_SHARE=0 / 1 forces it off / on (from n_pad = 10752, where the sweep runs two workgroups per CU).
-bool service_shared(int64_t n_pad) {
-  static const int v = [] { const char* e = std::getenv("GPRC_SERVICE_SHARE"); return e ? std::atoi(e) : -1; }();
-  return n_pad >= 10752 && (v >= 0 ? v != 0 : n_pad >= 13312);
-}
-
-// workgroups the service keeps resident (a CU each)
-int service_workgroups(bool with_inverse, int64_t n_pad) { return SERVICE_INV0 + (with_inverse ? TPP : 0) + (chain_split(n_pad) ? CHAIN_HELPERS : 0); }
-
-// part: 0 the whole service; 1 / 2 the two launches of the shared service (on two streams: they run side by side)
+// split: with the chain helpers (four more resident workgroups); part: 0 the whole service; 1 / 2 the two launches of the shared service
+// (on two streams: they run side by side)
 int launch_panel_service(hipStream_t s, double* packed, int64_t n_pad, double* winv, int* info_dev, void* sync, void* trace, double* inv,
-                         int64_t p_begin, int64_t p_end, int part) {
-  static bool attr_set[MAX_DEVICES] = {};
-  const size_t smem = PB_SMEM_DOUBLES * sizeof(double);
-  int dev = 0;
-  GPRC_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= MAX_DEVICES || !attr_set[dev]) {
-    GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_service_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    if (dev >= 0 && dev < MAX_DEVICES) attr_set[dev] = true;
-  }
+                         int64_t p_begin, int64_t p_end, bool split, int part) {
+  GPRC_TRY(ensure_dynamic_lds<panel_service_kernel>(PB_SMEM_BYTES));
   const int64_t P = n_pad / NB;
-  PanelSync* sy = reinterpret_cast<PanelSync*>(sync);
-  int* ready = reinterpret_cast<int*>(static_cast<char*>(sync) + (size_t)P * sizeof(PanelSync));
+  const SyncView v(sync, P);
   ProfScope ps(s, PK_PANEL_FUSED, 0.0, 0.0);
   const unsigned grid = part == 0 ? SERVICE_WGS : part == 1 ? 1 + CHAIN_HELPERS : SERVICE_H0 - 1;
-  hipLaunchKernelGGL(panel_service_kernel, dim3(grid), dim3(512), part == 2 ? G_SMEM_DOUBLES * sizeof(double) : smem, s, packed, n_pad, winv, info_dev, sy,
-                     ready, (int)P, static_cast<unsigned long long*>(trace), inv, (int)p_begin, (int)p_end, chain_split(n_pad) ? 1 : 0, part);
+  hipLaunchKernelGGL(panel_service_kernel, dim3(grid), dim3(512), part == 2 ? G_SMEM_BYTES : PB_SMEM_BYTES, s, packed, n_pad, winv, info_dev, v.sy,
+                     v.ready, (int)P, static_cast<unsigned long long*>(trace), inv, (int)p_begin, (int)p_end, split ? 1 : 0, part);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
 
 // launches: service launches so far on this sync buffer, this one included (the "resident" counter is cumulative)
-int launch_service_gate(hipStream_t s, int64_t n_pad, int* info_dev, void* sync, int launches) {
-  const int64_t P = n_pad / NB;
-  int* ready = reinterpret_cast<int*>(static_cast<char*>(sync) + (size_t)P * sizeof(PanelSync));
-  // GPRC_TEST_SERVICE_TIMEOUT=1 (test hook): the FIRST gate of the process waits for a residency count that cannot be reached and
-  // gives up at once -- the timeout / refill / service-off path of the fit entry points without a profiler.
-  static std::atomic<bool> fire{std::getenv("GPRC_TEST_SERVICE_TIMEOUT") != nullptr};
-  const bool forced = fire.exchange(false);
-  hipLaunchKernelGGL(service_gate_kernel, dim3(1), dim3(64), 0, s, ready + 3 * P, forced ? (1 << 30) : SERVICE_WGS * launches, info_dev,
+// forced (the test hook GPRC_TEST_SERVICE_TIMEOUT): the gate waits for a residency count that cannot be reached and gives up at once
+int launch_service_gate(hipStream_t s, int64_t n_pad, int* info_dev, void* sync, int launches, bool forced) {
+  hipLaunchKernelGGL(service_gate_kernel, dim3(1), dim3(64), 0, s, SyncView(sync, n_pad / NB).resident, forced ? (1 << 30) : SERVICE_WGS * launches, info_dev,
                      forced ? 0ULL : WAIT_LIMIT_TICKS);
   GPRC_LAUNCH_CHECK();
   return 0;
@@ -2352,14 +1204,20 @@ int launch_service_gate(hipStream_t s, int64_t n_pad, int* info_dev, void* sync,
 int launch_panel_strips(hipStream_t s, double* packed, int64_t n_pad, int64_t p, double* winv, int* info_dev, void* sync, void* trace) {
   const int64_t ld = panel_ld(n_pad, p), S = ld / 128;
   if (S <= 2 * TPP) return 0;
-  GPRC_TRY(ensure_gemm_attrs());
+  GPRC_TRY(ensure_dynamic_lds<panel_strips_kernel>(G_SMEM_BYTES));
   double fl = 0.0;
   for (int j = 0; j < TPP; ++j) fl += 2.0 * (double)(ld - 2 * NB) * NBI * (j * NBI) + (double)(ld - 2 * NB) * NBI * NBI;
   ProfScope ps(s, PK_GEMM_INNER, fl, 8.0 * 2.0 * (double)(ld - 2 * NB) * NB);
-  hipLaunchKernelGGL(panel_strips_kernel, dim3((unsigned)(S - 2 * TPP)), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad, (int)p, winv,
-                     info_dev, reinterpret_cast<PanelSync*>(sync) + p, static_cast<unsigned long long*>(trace));
+  hipLaunchKernelGGL(panel_strips_kernel, dim3((unsigned)(S - 2 * TPP)), dim3(256), G_SMEM_BYTES, s, packed, n_pad, (int)p, winv,
+                     info_dev, SyncView(sync, n_pad / NB).sy + p, static_cast<unsigned long long*>(trace));
   GPRC_LAUNCH_CHECK();
   return 0;
+}
+
+// ordinary strips (rows from 2 NB below the top) of panel q, and the flops of their strip roles riding in an update kernel
+static int64_t ordinary_strips(int64_t n_pad, int64_t q) { return std::max<int64_t>(0, panel_ld(n_pad, q) / 128 - 2 * TPP); }
+static void add_strip_flops(int64_t nstrips, double& fl) {
+  for (int j = 0; j < TPP; ++j) fl += nstrips * (2.0 * 128 * NBI * (j * NBI) + 128.0 * NBI * NBI);
 }
 
 // the caller's-stream kernel of panel p under the service: the trailing update of panel p over the targets (p, q_end) (everything
@@ -2368,268 +1226,70 @@ int launch_trailing_service(hipStream_t s, double* packed, int64_t n_pad, int64_
   const int64_t P = n_pad / NB;
   if (q_end > P) q_end = P;
   if (q_end - p - 1 < 1 || p + 2 >= P) return 0;   // no target, or the only target is the last panel: its diagonal block is all there is
-  GPRC_TRY(ensure_gemm_attrs());
+  GPRC_TRY(ensure_dynamic_lds<trailing_service_kernel>(G_SMEM_BYTES));
   int64_t tiles = -(int64_t)PANEL_DIAG_TILES;
+  for (int64_t q = p + 1; q < q_end; ++q) tiles += panel_tiles(P, q);
   double fl = 0.0, by = 0.0;
-  for (int64_t q = p + 1; q < q_end; ++q) {
-    tiles += (int64_t)TPP * TPP * (P - q) - TPP * (TPP - 1) / 2;
-    const double rows = (double)(n_pad - q * NB);
-    const double elems = rows * NB - 0.5 * NB * (double)(NB - 1) - (q == p + 1 ? 0.5 * NB * (double)(NB + 1) : 0.0);
-    fl += 2.0 * elems * NB;
-    by += 8.0 * (2.0 * elems + rows * NB);
-  }
-  const int64_t ld1 = panel_ld(n_pad, p + 1);
-  const int64_t nstrips = std::max<int64_t>(0, ld1 / 128 - 2 * TPP);
-  for (int j = 0; j < TPP; ++j) fl += nstrips * (2.0 * 128 * NBI * (j * NBI) + 128.0 * NBI * NBI);
+  trailing_work(n_pad, p + 1, q_end, 1, NB, true, fl, by);
+  const int64_t nstrips = ordinary_strips(n_pad, p + 1);
+  add_strip_flops(nstrips, fl);
   ProfScope ps(s, PK_TRAILING, fl, by);
-  PanelSync* sy = reinterpret_cast<PanelSync*>(sync);
-  int* ready = reinterpret_cast<int*>(static_cast<char*>(sync) + (size_t)P * sizeof(PanelSync));
-  int* rowcnt = ready + 3 * P + 16;
-  const int64_t n_first = (int64_t)TPP * TPP * (P - p - 1) - TPP * (TPP - 1) / 2 - PANEL_DIAG_TILES;
+  const SyncView v(sync, P);
+  const int64_t n_first = panel_tiles(P, p + 1) - PANEL_DIAG_TILES;
   const int64_t base = (n_first + nstrips + 7) & ~(int64_t)7;     // ticketed workgroups, padded to a multiple of the XCD count
-  hipLaunchKernelGGL(trailing_service_kernel, dim3((unsigned)(base + (tiles - n_first))), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad, (int)p,
-                     (int)tiles, (int)nstrips, sy, ready, rowcnt, winv, info_dev, static_cast<unsigned long long*>(trace), (int)q_end);
+  hipLaunchKernelGGL(trailing_service_kernel, dim3((unsigned)(base + (tiles - n_first))), dim3(256), G_SMEM_BYTES, s, packed, n_pad, (int)p,
+                     (int)tiles, (int)nstrips, v.sy, v.ready, v.rowcnt, winv, info_dev, static_cast<unsigned long long*>(trace), (int)q_end);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
 
-// the caller's-stream work of the panels [g0, g1) of a group under the service in ONE persistent launch (trailing_sweep_kernel);
-// service_wgs: workgroups the service keeps resident (they hold a CU each)
+// the caller's-stream work of the panels [g0, g1) of a group under the service in ONE persistent launch (trailing_sweep_kernel) of wgs
+// workgroups; core: the kernel's tile loop (1 or 2, see the kernel); head_slices (core 2 only): the head tiles in 32-row slices
 int launch_trailing_sweep(hipStream_t s, double* packed, int64_t n_pad, int64_t g0, int64_t g1, double* winv, int* info_dev, void* sync, void* trace,
-                          int service_wgs) {
+                          int wgs, int core, int head_slices) {
   const int64_t P = n_pad / NB;
   const int64_t q_end = std::min(g1, P);
   int64_t p_last = g0;                                              // one past the last panel with something to do (launch_trailing_service's rule)
   for (int64_t p = g0; p + 1 < g1; ++p)
     if (!(q_end - p - 1 < 1 || p + 2 >= P)) p_last = p + 1;
   if (p_last == g0) return 0;
-  GPRC_TRY(ensure_gemm_attrs());
+  GPRC_TRY(core == 2 ? ensure_dynamic_lds<trailing_sweep_kernel<2>>(G_SMEM_BYTES) : ensure_dynamic_lds<trailing_sweep_kernel<1>>(G_SMEM_BYTES));
   double fl = 0.0, by = 0.0;
   for (int64_t p = g0; p < p_last; ++p) {
-    for (int64_t q = p + 1; q < q_end; ++q) {
-      const double rows = (double)(n_pad - q * NB);
-      const double elems = rows * NB - 0.5 * NB * (double)(NB - 1) - (q == p + 1 ? 0.5 * NB * (double)(NB + 1) : 0.0);
-      fl += 2.0 * elems * NB;
-      by += 8.0 * (2.0 * elems + rows * NB);
-    }
-    const int64_t nstrips = std::max<int64_t>(0, panel_ld(n_pad, p + 1) / 128 - 2 * TPP);
-    for (int j = 0; j < TPP; ++j) fl += nstrips * (2.0 * 128 * NBI * (j * NBI) + 128.0 * NBI * NBI);
+    trailing_work(n_pad, p + 1, q_end, 1, NB, true, fl, by);
+    add_strip_flops(ordinary_strips(n_pad, p + 1), fl);
   }
   ProfScope ps(s, PK_TRAILING, fl, by);
-  PanelSync* sy = reinterpret_cast<PanelSync*>(sync);
-  int* ready = reinterpret_cast<int*>(static_cast<char*>(sync) + (size_t)P * sizeof(PanelSync));
-  int* rowcnt = ready + 3 * P + 16;
-  SweepSync sw;
-  sw.stripdone = rowcnt + P * TPP * P;
-  sw.rest_ticket = sw.stripdone + P * TPP * P;
-  sw.ver = sw.rest_ticket + 8 * P;
-  sw.aux = sw.ver + P * TPP * P * TPP;
-  int dev = 0, cus = 0;
-  GPRC_HIP(hipGetDevice(&dev));
-  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  // Two workgroups per CU the service leaves free (all co-resident) -- except below n_pad = 10752, where the panel chain is the bound and
-  // what counts is how quickly a tile the chain waits for is done: ONE workgroup per CU has the CU's MFMA pipes to itself
-  // (measured, same box: n = 8192 6.28 -> 5.99 ms, 10240 9.44 -> 9.21; 12288 13.55 -> 14.60: profiles/r03_factor_schedules.txt).
-  // GPRC_SWEEP_WGS=<n> overrides.
-  static const int wgs_env = [] { const char* e = std::getenv("GPRC_SWEEP_WGS"); return e ? std::atoi(e) : 0; }();
-  const int per_cu = n_pad < 10752 ? 1 : 2;
-  // shared service: the resident 4-wave roles' CUs take ONE sweep workgroup each beside the role
-  const int shared = service_shared(n_pad) ? service_wgs - 1 - (chain_split(n_pad) ? CHAIN_HELPERS : 0) : 0;
-  const int wgs = wgs_env > 0 ? wgs_env : std::max(8, per_cu * (cus - service_wgs) + shared);
-  static const int head_slices = [] { const char* e = std::getenv("GPRC_HEAD_SLICES"); return e ? std::atoi(e) : 1; }();   // 0: whole head tiles (A/B switch)
-  if (per_cu == 1 && wgs_env <= 0)
-    hipLaunchKernelGGL(trailing_sweep_kernel<2>, dim3((unsigned)wgs), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad, (int)g0, (int)p_last,
-                       (int)q_end, sy, ready, rowcnt, sw, winv, info_dev, static_cast<unsigned long long*>(trace), head_slices);
+  const SyncView v(sync, P);
+  if (core == 2)
+    hipLaunchKernelGGL(trailing_sweep_kernel<2>, dim3((unsigned)wgs), dim3(256), G_SMEM_BYTES, s, packed, n_pad, (int)g0, (int)p_last,
+                       (int)q_end, v.sy, v.ready, v.rowcnt, v.sw, winv, info_dev, static_cast<unsigned long long*>(trace), head_slices);
   else
-    hipLaunchKernelGGL(trailing_sweep_kernel<1>, dim3((unsigned)wgs), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad, (int)g0, (int)p_last,
-                       (int)q_end, sy, ready, rowcnt, sw, winv, info_dev, static_cast<unsigned long long*>(trace), 0);
+    hipLaunchKernelGGL(trailing_sweep_kernel<1>, dim3((unsigned)wgs), dim3(256), G_SMEM_BYTES, s, packed, n_pad, (int)g0, (int)p_last,
+                       (int)q_end, v.sy, v.ready, v.rowcnt, v.sw, winv, info_dev, static_cast<unsigned long long*>(trace), 0);
   GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-static int ensure_gemm_attrs() {
-  static bool done[MAX_DEVICES] = {};  // per device, as above
-  int dev = 0;
-  GPRC_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < MAX_DEVICES && done[dev]) return 0;
-  const int smem = (int)(G_SMEM_DOUBLES * sizeof(double));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_GEMM_INNER>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_SOLVE_UPDATE>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_COV_SYRK>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<PK_INV_GEMM>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trsm_panel_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trsm_panel_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_panel_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_panel_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trailing_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_strips_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trailing_service_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trailing_sweep_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trailing_sweep_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(inv512_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_left_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trailing_range_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  if (dev >= 0 && dev < MAX_DEVICES) done[dev] = true;
-  return 0;
-}
-
-int launch_solve_left(hipStream_t s, double* vt, int64_t ldv, int64_t m_pad, const double* packed, int64_t n_pad, int64_t j, int64_t G,
-                      int64_t tri_row0) {
-  if (j <= 0 || m_pad <= 0 || G <= 0) return 0;
-  if (m_pad % 128) { set_error("solve_left: m_pad must be a multiple of 128"); return GPRC_ERR_ARG; }
-  if ((j + G) * NB > n_pad) { set_error("solve_left: panel group beyond the factor"); return GPRC_ERR_ARG; }
-  GPRC_TRY(ensure_gemm_attrs());
-  const int64_t N = G * NB, tiles = (m_pad / 128) * (N / 128);
-  // GPRC_KCHUNK=<panels>: the pass is cut into launches of at most that many source panels (K = 512 x panels): the tiles an
-  // XCD runs concurrently are re-aligned at every launch boundary, so its L2 keeps serving the shared operand strips;
-  // the price is one more C tile load/store per chunk.  Same products, same order: bit-identical.  Default: one launch.
-  static const int64_t kchunk = [] { const char* e = std::getenv("GPRC_KCHUNK"); return e ? std::atoll(e) : 0; }();
-  const int64_t step = kchunk > 0 ? kchunk : j;
-  // GPRC_TILE256=1: 256 x 128 macro-tiles on 8 waves (experiment: -25 % operand staging per flop); needs m_pad % 256 == 0
-  static const bool tile256 = [] { const char* e = std::getenv("GPRC_TILE256"); return e && std::atoi(e) == 1; }();
-  const bool use256 = tile256 && m_pad % 256 == 0;
-  if (use256) {
-    static bool attr_set[MAX_DEVICES] = {};
-    int dev = 0;
-    GPRC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= MAX_DEVICES || !attr_set[dev]) {
-      GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_left_kernel256), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(T2_SMEM_DOUBLES * sizeof(double))));
-      if (dev >= 0 && dev < MAX_DEVICES) attr_set[dev] = true;
-    }
-  }
-  for (int64_t kp0 = 0; kp0 < j; kp0 += step) {
-    const int64_t kp1 = std::min(j, kp0 + step), K = (kp1 - kp0) * NB;
-    double fl = 2.0 * (double)m_pad * N * (double)K;
-    if (tri_row0 >= 0) {   // algorithmic work of the triangular form: per 128-row tile only the columns from its first row on
-      fl = 0.0;
-      for (int64_t tr = 0; tr < m_pad / 128; ++tr) fl += 2.0 * 128.0 * N * (double)std::max<int64_t>(0, kp1 * NB - std::max<int64_t>(kp0 * NB, tri_row0 + tr * 128));
-    }
-    ProfScope ps(s, PK_SOLVE_LEFT, fl, 8.0 * (2.0 * m_pad * N + (double)m_pad * K + (double)N * K));
-    if (use256 && tri_row0 < 0)
-      hipLaunchKernelGGL(solve_left_kernel256, dim3((unsigned)(tiles / 2)), dim3(512), T2_SMEM_DOUBLES * sizeof(double), s, vt, ldv, packed, n_pad,
-                         (int)j, (int)(m_pad / 256), (int)(N / 128), 8, (int)kp0, (int)kp1);
-    else
-      hipLaunchKernelGGL(solve_left_kernel, dim3((unsigned)tiles), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, vt, ldv, packed, n_pad,
-                         (int)j, (int)(m_pad / 128), (int)(N / 128), 8, (int)kp0, (int)kp1, tri_row0);
-    GPRC_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// ssq != nullptr: also ssq[i] = sum_j X_new[i][j]^2 for the M rows (the predict's fused colSums(v * v) partial of this block column)
-// vt[:, panel p] := vt[:, panel p] L_pp^-T (in place; everything left of panel p already applied); sspart (may be null):
-// per-row sums of squares of the four finished 128-column blocks at sspart[(4 p + j) * m_pad + row]
-int launch_solve_panel_fused(hipStream_t s, double* vt, int64_t ldv, int64_t m_pad, const double* packed, int64_t n_pad, int64_t p,
-                             const double* winv, double* sspart, int64_t ss_stride) {
-  if (m_pad <= 0) return 0;
-  if (ss_stride <= 0) ss_stride = m_pad;
-  if (m_pad % 128) { set_error("solve_panel_fused: m_pad must be a multiple of 128"); return GPRC_ERR_ARG; }
-  GPRC_TRY(ensure_gemm_attrs());
-  const double M = (double)m_pad;
-  ProfScope ps(s, PK_SOLVE_PANEL, M * 128.0 * 128.0 * TPP + 2.0 * M * 128.0 * 128.0 * (TPP * (TPP - 1) / 2), 8.0 * 2.0 * M * NB);
-  const size_t smem = G_SMEM_DOUBLES * sizeof(double);
-  if (sspart) hipLaunchKernelGGL(solve_panel_fused_kernel<true>, dim3((unsigned)(m_pad / 128)), dim3(256), smem, s, vt, ldv, packed, n_pad, (int)p, winv, sspart, ss_stride);
-  else hipLaunchKernelGGL(solve_panel_fused_kernel<false>, dim3((unsigned)(m_pad / 128)), dim3(256), smem, s, vt, ldv, packed, n_pad, (int)p, winv, sspart, ss_stride);
-  GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_trsm_panel(hipStream_t s, double* X, int64_t ldx, int64_t M, const double* winv, double* ssq) {
-  if (M <= 0) return 0;
-  if (M % 128) { set_error("trsm_panel: M must be a multiple of 128"); return GPRC_ERR_ARG; }
-  GPRC_TRY(ensure_gemm_attrs());
-  ProfScope ps(s, PK_TRSM_PANEL, 1.0 * M * 128 * 128, 8.0 * 2 * M * 128);
-  if (ssq) hipLaunchKernelGGL(trsm_panel_kernel<true>, dim3((unsigned)(M / 128)), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, X, ldx, winv, ssq);
-  else hipLaunchKernelGGL(trsm_panel_kernel<false>, dim3((unsigned)(M / 128)), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, X, ldx, winv, ssq);
-  GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_gemm_nt(hipStream_t s, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
-                   int64_t M, int64_t N, int64_t K, int lower, int kind) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  // (K: the tile loop runs two k-tiles of 16 per iteration and needs at least four: every caller's K is a multiple of 128)
-  if (M % 128 || N % 128 || K % (2 * G_KB) || K < 4 * G_KB || (lda & 1) || (ldb & 1)) { set_error("gemm_nt: bad shape"); return GPRC_ERR_ARG; }
-  GPRC_TRY(ensure_gemm_attrs());
-  const int64_t tiles = (M / 128) * (N / 128);
-  if (tiles > 0x7fffffff) { set_error("gemm_nt: too many tiles"); return GPRC_ERR_ARG; }
-  if (kind == PK_INV_GEMM && !(lower && M == N && K == M)) { set_error("gemm_nt: the triangular inverse product is square and lower"); return GPRC_ERR_ARG; }
-  const double useful = kind == PK_INV_GEMM ? 1.0 / 6.0 : lower ? 0.5 : 1.0;  // algorithmic: the lower triangle only (inverse product: from the diagonal on)
-  ProfScope ps(s, kind, 2.0 * M * N * K * useful, 8.0 * (2.0 * M * N * (lower ? 0.5 : 1.0) + (M + N) * (double)K));
-  constexpr int pg = 0;   // (a persistent grid of N workgroups striding over the tile list measured 4 % slower: DESIGN.md 3)
-  const dim3 grid((unsigned)((pg > 0 && tiles > pg) ? pg : tiles)), block(256);
-  const size_t smem = G_SMEM_DOUBLES * sizeof(double);
-  const int tm = (int)(M / 128), tn = (int)(N / 128);
-  constexpr int group = 8;  // 8 x 8 concurrent tiles per XCD share 16 strips; 4..32 measured within 0.5 %
-  if (kind == PK_SOLVE_UPDATE) hipLaunchKernelGGL((gemm_nt_kernel<PK_SOLVE_UPDATE>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
-  else if (kind == PK_COV_SYRK) hipLaunchKernelGGL((gemm_nt_kernel<PK_COV_SYRK>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
-  else if (kind == PK_INV_GEMM) hipLaunchKernelGGL((gemm_nt_kernel<PK_INV_GEMM>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
-  else hipLaunchKernelGGL((gemm_nt_kernel<PK_GEMM_INNER>), grid, block, smem, s, C, ldc, A, lda, B, ldb, tm, tn, (int)K, lower, group);
-  GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-// part: 0 all tiles; 1 only the lower tiles of the first target's diagonal block; 2 everything but those
-int launch_trailing_update(hipStream_t s, double* packed, int64_t n_pad, int64_t p, int64_t q_begin, int64_t q_end,
-                           int64_t q_stride) {
-  const int64_t P = n_pad / NB;
-  if (q_begin <= p || q_stride <= 0) { set_error("trailing_update: bad panel range"); return GPRC_ERR_ARG; }
-  if (q_end > P) q_end = P;
-  int64_t tiles = 0, nt = 0;
-  for (int64_t q = q_begin; q < q_end; q += q_stride) { tiles += (int64_t)TPP * TPP * (P - q) - TPP * (TPP - 1) / 2; ++nt; }
-  if (tiles <= 0) return 0;
-  GPRC_TRY(ensure_gemm_attrs());
-  double fl = 0.0, by = 0.0;  // algorithmic: lower triangle of the 512-wide diagonal block + everything below it
-  for (int64_t q = q_begin; q < q_end; q += q_stride) {
-    const double rows = (double)(n_pad - q * NB);
-    const double elems = rows * NB - 0.5 * NB * (double)(NB - 1);
-    fl += 2.0 * elems * NB;
-    by += 8.0 * (2.0 * elems + rows * NB);
-  }
-  ProfScope ps(s, PK_TRAILING, fl, by);
-
-  constexpr int pg = 0;
-  const unsigned grid = (unsigned)((pg > 0 && tiles > pg) ? pg : tiles);
-  hipLaunchKernelGGL(trailing_kernel, dim3(grid), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad, (int)p,
-                     (int)q_begin, (int)q_stride, (int)nt, (int)tiles);
-  GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-// target panels q_begin, q_begin + q_stride, ... < q_end updated with the source panels [p_begin, p_end) in one pass
-int launch_trailing_range(hipStream_t s, double* packed, int64_t n_pad, int64_t p_begin, int64_t p_end, int64_t q_begin, int64_t q_end,
-                          int64_t q_stride) {
-  const int64_t P = n_pad / NB;
-  if (q_end > P) q_end = P;
-  if (p_begin < 0 || p_end <= p_begin || q_stride <= 0) return 0;
-  if (q_begin < p_end) { set_error("trailing_range: a target panel is not behind the source range"); return GPRC_ERR_ARG; }
-  if (q_begin >= q_end) return 0;
-  GPRC_TRY(ensure_gemm_attrs());
-  int64_t tiles = 0, nt = 0;
-  double fl = 0.0, by = 0.0;
-  const double K = (double)(p_end - p_begin) * NB;
-  for (int64_t q = q_begin; q < q_end; q += q_stride) {
-    tiles += (int64_t)TPP * TPP * (P - q) - TPP * (TPP - 1) / 2;
-    ++nt;
-    const double rows = (double)(n_pad - q * NB);
-    const double elems = rows * NB - 0.5 * NB * (double)(NB - 1);
-    fl += 2.0 * elems * K;
-    by += 8.0 * (2.0 * elems + rows * K);
-  }
-  ProfScope ps(s, PK_TRAILING_LEFT, fl, by);
-  hipLaunchKernelGGL(trailing_range_kernel, dim3((unsigned)tiles), dim3(256), G_SMEM_DOUBLES * sizeof(double), s, packed, n_pad,
-                     (int)p_begin, (int)p_end, (int)q_begin, (int)q_stride, (int)nt, (int)tiles);
-  GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-// left-looking update of target panels [q_begin, q_end) with every panel before q_begin (GPRC_KCHUNK: in K-chunks, see solve_left)
-int launch_trailing_left(hipStream_t s, double* packed, int64_t n_pad, int64_t q_begin, int64_t q_end) {
-  static const int64_t kchunk = [] { const char* e = std::getenv("GPRC_KCHUNK"); return e ? std::atoll(e) : 0; }();
-  if (kchunk <= 0) return launch_trailing_range(s, packed, n_pad, 0, q_begin, q_begin, q_end, 1);
-  for (int64_t p0 = 0; p0 < q_begin; p0 += kchunk)
-    GPRC_TRY(launch_trailing_range(s, packed, n_pad, p0, std::min(q_begin, p0 + kchunk), q_begin, q_end, 1));
   return 0;
 }
 
 }  // namespace gprc
+
+// include/gprc_native.h: the raw records of the timed-out waits, see wait_diag; clears them
+extern "C" __attribute__((visibility("default"))) int gprc_prof_wait_timeout(int* out, int ints) {   // out[0]: records written; 8 ints per record from out[8]
+  if (!out || ints < 8) return -1;
+  const size_t bytes = sizeof(int) * (size_t)std::min(ints, 8 * (gprc::WAIT_DIAG_RECORDS + 1));
+  std::lock_guard<std::mutex> lock(gprc::g_wait_diag_host);
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gprc::g_wait_diag), bytes) != hipSuccess) return -1;
+  return hipMemcpyToSymbol(HIP_SYMBOL(gprc::g_wait_diag), gprc::g_wait_diag_zero, sizeof(gprc::g_wait_diag_zero)) == hipSuccess ? 0 : -1;
+}
+#ifdef GPRC_CHAIN_PROF
+extern "C" __attribute__((visibility("default"))) int gprc_debug_chain_prof(unsigned long long* out64) {
+  return hipMemcpyFromSymbol(out64, HIP_SYMBOL(gprc::g_chain_prof), 512) == hipSuccess ? 0 : -1;
+}
+#endif
+#ifdef GPRC_SWEEP_PROF
+extern "C" __attribute__((visibility("default"))) int gprc_debug_sweep_prof(unsigned long long* out8, int reset) {
+  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(gprc::g_sweep_prof), 64) != hipSuccess) return -1;
+  if (reset) { unsigned long long z[8] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(gprc::g_sweep_prof), z, 64) != hipSuccess) return -1; }
+  return 0;
+}
+#endif

@@ -264,61 +264,6 @@ def test_solve_in_panel_steps_is_bit_identical_at_a_large_size():
     ctx.close()
 
 
-def test_k_chunked_left_looking_passes_are_bit_identical():
-    """GPRC_KCHUNK cuts the long-K left-looking passes (predict solve and Cholesky trailing update) into several launches
-    over K ranges; same products in the same order, so the factor and the prediction must not change by a bit.  The
-    switch is read once per process: the chunked run happens in a child process and the two digests are compared.
-    n = 3100 (7 panels) with GPRC_FACTOR=1 (every panel its own left-looking group) and GPRC_SOLVE=left, so passes with
-    K up to 6 panels exist and chunks of 1 and 4 panels cut them unevenly."""
-    import hashlib
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = (
-        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-        "import hashlib, numpy as np\n"
-        "from gprc_amd import GPR, cov_func, sqrexp\n"
-        "rng = np.random.default_rng(41)\n"
-        "X = rng.uniform(-1, 1, (3, 3100)); y = rng.normal(size=3100); Xs = rng.uniform(-1, 1, (3, 900))\n"
-        "g = GPR(X, y, 0.1, cov_func(sqrexp, l=0.7))\n"
-        "h = hashlib.sha256(); [h.update(np.ascontiguousarray(a).tobytes()) for a in (g.alpha, g.L, g.predict(Xs))]\n"
-        "print('DIGEST', h.hexdigest())\n") % (os.path.dirname(here), here)
-    digests = {}
-    for kc in ("0", "1", "4"):
-        env = dict(os.environ, GPRC_KCHUNK=kc, GPRC_FACTOR="1", GPRC_SOLVE="left")
-        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        digests[kc] = [ln.split()[1] for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0]
-    assert digests["1"] == digests["0"] and digests["4"] == digests["0"], digests
-
-
-def test_256x128_macro_tile_is_bit_identical():
-    """GPRC_TILE256=1 runs the predict's left-looking passes on 256 x 128 macro-tiles (8 waves sharing one B strip) instead of
-    128 x 128 tiles: same k order per output element, so not a bit may change.  Child processes (the switch is read once);
-    ns = 1024 rows (m_pad a multiple of 256), GPRC_SOLVE=left / 2 so that left-looking passes with K up to 5 panels run."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = (
-        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-        "import hashlib, numpy as np\n"
-        "from gprc_amd import GPR, cov_func, sqrexp\n"
-        "rng = np.random.default_rng(43)\n"
-        "X = rng.uniform(-1, 1, (3, 2900)); y = rng.normal(size=2900); Xs = rng.uniform(-1, 1, (3, 1024))\n"
-        "g = GPR(X, y, 0.1, cov_func(sqrexp, l=0.7))\n"
-        "h = hashlib.sha256(); [h.update(np.ascontiguousarray(a).tobytes()) for a in (g.alpha, g.predict(Xs), g.predict(Xs[:, :512]))]\n"
-        "print('DIGEST', h.hexdigest())\n") % (os.path.dirname(here), here)
-    digests = {}
-    for t256, solve in (("0", "left"), ("1", "left"), ("1", "2")):
-        env = dict(os.environ, GPRC_TILE256=t256, GPRC_SOLVE=solve)
-        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        digests[(t256, solve)] = [ln.split()[1] for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0]
-    assert len(set(digests.values())) == 1, digests
-
-
 def test_fused_in_panel_predict_solve_is_bit_identical():
     """The predict's in-panel solve runs as one launch per panel (solve_panel_fused_kernel: a strip's four sub-steps back to
     back); GPRC_SOLVE_PANEL=steps selects the seven-launch form.  Same tiles in the same order per strip: identical bits,

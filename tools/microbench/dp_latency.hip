@@ -1,4 +1,4 @@
-// Dependent-issue latency of the double-precision instructions the 16x16 pivot sweep (diag16, kernels_chol.hip) is made of, one wave
+// Dependent-issue latency of the double-precision instructions the 16x16 pivot sweep (diag16, chol_tile.h) is made of, one wave
 // alone on its SIMD: cycles per instruction of a 256-long dependent chain (s_memtime), and of 4 independent chains interleaved.
 // Build: hipcc --offload-arch=gfx950 -O2 dp_latency.hip -o bin/dp_latency
 #include <hip/hip_runtime.h>
