@@ -52,6 +52,7 @@ def main():
             nat.check(L.gprc_kernel_matrix(ctx.handle, kid, pp, npar, A.ctypes.data, d, nA, B.ctypes.data, nB, out.ctypes.data, nA))
             report(f"kernel_matrix {name} d={d} {nA}x{nB}", out, orc.kernel_matrix(kid, par, A, B), 1e-13)
     # ---- 2. staged factorisation on device buffers ------------------------------------------------
+    # (the asserted form of this stage, on arbitrary matrices against an 80-bit reference: tests/test_gpu_blocks.py)
     dev = torch.device("cuda:0")
     for n in (300, 1000, 1500):
         d = 8
