@@ -62,6 +62,7 @@ PROTOTYPES = {
     "gprc_fit_gradient": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, _dp]),
     "gprc_gpr_logp_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.POINTER(C.c_double), _dp]),
     "gprc_gpr_predict": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp]),
+    "gprc_gpr_predict_grad": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "gprc_gpr_extend": (C.c_int, [_vp, _vp, _i64, _vp]),
     "gprc_model_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_model_get_L": (C.c_int, [_vp, _vp, _i64]),
@@ -130,6 +131,7 @@ PROTOTYPES = {
     "gprc_prof_kinds": (C.c_int, []),
     "gprc_prof_summary": (C.c_int, [C.c_int, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gprc_dev_solve_rows": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64]),
+    "gprc_dev_reverse_factor": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None
@@ -202,13 +204,18 @@ def device_count() -> int:
 INFO_WAIT_TIMEOUT = -99   # include/gprc_native.h: a device-side dependency wait ran out
 PROF_KINDS = ["fill", "potf2_inv", "trsm_panel", "gemm_inner_k128", "trailing_update", "solve_update_k512", "trsv",
               "row_reduce", "cov_syrk", "deriv_rowsum", "jacobi_sweep", "solve_left", "trailing_left", "panel_fused", "solve_panel",
-              "inverse_gemm", "grad_contract", "gpc_grad_contract"]
+              "inverse_gemm", "grad_contract", "reverse_factor", "pred_grad_contract", "gpc_grad_contract"]
+# the library's kind of each name (include/gprc_native.h).  The list above groups the regression kinds before the classifier's one;
+# the two prediction-gradient kinds were numbered after it, so position and kind differ from there on.
+PROF_KIND_ID = {name: kind for kind, name in enumerate(PROF_KINDS[:17])}
+PROF_KIND_ID.update(gpc_grad_contract=17, reverse_factor=18, pred_grad_contract=19)
 
 
 def prof_summary():
     """{kind: dict(count, ms, flops, bytes)} of the launches seen since gprc_prof_reset()."""
     out = {}
-    for kind, name in enumerate(PROF_KINDS):
+    for name in PROF_KINDS:
+        kind = PROF_KIND_ID[name]
         cnt, ms, fl, by = _i64(), C.c_double(), C.c_double(), C.c_double()
         check(lib().gprc_prof_summary(kind, C.byref(cnt), C.byref(ms), C.byref(fl), C.byref(by)))
         out[name] = dict(count=cnt.value, ms=ms.value, flops=fl.value, bytes=by.value)

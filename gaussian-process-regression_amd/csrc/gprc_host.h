@@ -55,6 +55,8 @@ struct gprc_model {
   double* f_hat = nullptr;   // GPC
   double* sw = nullptr;      // GPC sqrt(W)
   double* work = nullptr;    // trsv partials
+  double* packed_rev = nullptr;  // J L^T J in the packed layout and its diagonal-block inverses: built by the first gprc_gpr_predict_grad that
+  double* winv_rev = nullptr;    // wants the variance's gradient, owned by the model (never borrowed), gone after gprc_gpr_extend
   double logp = 0.0, noise = 0.0, logq = 0.0;
   bool borrowed = false;     // X, y, packed, winv, alpha belong to the caller
 };

@@ -73,7 +73,8 @@ int ensure_dynamic_lds(size_t bytes) {
 
 // ---- in-library event profiler (bench.py's live roofline numbers) ---------------------------------
 enum ProfKind { PK_FILL = 0, PK_POTF2 = 1, PK_TRSM_PANEL = 2, PK_GEMM_INNER = 3, PK_TRAILING = 4, PK_SOLVE_UPDATE = 5,
-                PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_INV_GEMM = 15, PK_GRAD_CONTRACT = 16, PK_GPC_GRAD_CONTRACT = 17, PK_COUNT = 18 };
+                PK_TRSV = 6, PK_ROWREDUCE = 7, PK_COV_SYRK = 8, PK_DERIV = 9, PK_JACOBI = 10, PK_SOLVE_LEFT = 11, PK_TRAILING_LEFT = 12, PK_PANEL_FUSED = 13, PK_SOLVE_PANEL = 14, PK_INV_GEMM = 15, PK_GRAD_CONTRACT = 16, PK_GPC_GRAD_CONTRACT = 17,
+                PK_REVERSE_FACTOR = 18, PK_PRED_GRAD = 19, PK_COUNT = 20 };
 bool prof_enabled();
 void prof_begin(hipStream_t s, int kind);
 void prof_end(hipStream_t s, int kind, double flops, double bytes);
@@ -135,6 +136,19 @@ int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, i
 int launch_gpc_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* a, const double* sw,
                              const double* u, const double* g, const double* W, int64_t ld, double* part);
 
+// ---- launchers (kernels_pgrad.hip) -------------------------------------------------------------
+// the prediction gradient's contraction over one chunk of m test points (rows of the chunk, m_pad = pad_up(m, 128)):
+//   pmean[(st d + c) m_pad + i] = sum over the columns j of stripe st of alpha_j h_ij (x*_ic - x_jc) t'_c
+//   pvar [(st d + c) m_pad + i] = the same with W[i, n_pad - 1 - j] in place of alpha_j   (W: the chunk (V L^-1) J, column-reversed; ld ldw)
+// with k and h recomputed from Xs and X; pvar == nullptr: the mean's sums alone (W is not read); pmean may be null when pvar is not.
+// pred_grad_stripes(n_pad) stripes of whole 64-column tiles, a function of n_pad only.  launch_pred_grad_sum adds the stripes in order,
+// applies the factors that do not depend on (i, j) (variance: times -2) and writes out[c + d i], i < m.
+int64_t pred_grad_stripes(int64_t n_pad);
+int launch_pred_grad(hipStream_t s, const KernelSpec& ks, const double* Xs, int64_t m, int64_t m_pad, const double* X, int64_t n, int64_t n_pad,
+                     int64_t d, const double* alpha, const double* W, int64_t ldw, double* pmean, double* pvar);
+int launch_pred_grad_sum(hipStream_t s, const KernelSpec& ks, const double* part, int64_t n_pad, int64_t d, int64_t m_pad, int64_t m, bool variance,
+                         double* out);
+
 // ---- launchers (kernels_gemm.hip: no flags between workgroups) ---------------------------------
 // the predict's in-panel solve of panel p in one launch (see solve_panel_fused_kernel)
 int launch_solve_panel_fused(hipStream_t s, double* vt, int64_t ldv, int64_t m_pad, const double* packed, int64_t n_pad, int64_t p,
@@ -190,6 +204,11 @@ int launch_logp(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, c
 // the solved tail rows vt (t_pad x n0, ld ldv; t valid rows = global rows n0 .. n0 + t - 1), zero below; bandwidth-bound
 int launch_extend_merge(hipStream_t s, const double* old_packed, int64_t n_pad_old, const double* vt, int64_t ldv, int64_t t_pad, int64_t t,
                         int64_t n0, int64_t n_pad_new, double* packed);
+// the reversed factor M = J L^T J (J: reversal of n_pad indices; M is lower triangular) in L's packed layout, zero above the diagonal,
+// and the matching diagonal-block inverses J winv_block(B - 1 - b)^T J: solve_rows with them computes (V J) M^-T = (V L^-1) J
+int launch_reverse_factor(hipStream_t s, const double* packed, const double* winv, int64_t n_pad, double* packed_rev, double* winv_rev);
+// vt[:, j] <-> vt[:, cols - 1 - j] in place, rows [0, rows)
+int launch_reverse_cols(hipStream_t s, double* vt, int64_t ld, int64_t rows, int64_t cols);
 // unpack the factor into a dense n x n lower matrix (upper = 0)
 int launch_unpack_L(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, double* out, int64_t ld_out);
 // out[i] = (minuend ? minuend[i] : 0) -/+ sum_{t < nparts} part[t * stride + i], summed in t order: the tail of the fused

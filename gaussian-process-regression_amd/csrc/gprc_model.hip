@@ -48,6 +48,8 @@ void free_model(gprc_model* m) {
   if (m->borrowed) m->X = m->y = m->packed = m->winv = m->alpha = nullptr;
   for (const auto& pr : model_parts(m))
     if (*pr.first) pool_release(m->ctx, *pr.first, sizeof(double) * (size_t)pr.second);
+  if (m->packed_rev) pool_release(m->ctx, m->packed_rev, sizeof(double) * (size_t)gprc_packed_size(m->n_pad));   // the model's own, borrowed or not
+  if (m->winv_rev) pool_release(m->ctx, m->winv_rev, sizeof(double) * (size_t)gprc_winv_size(m->n_pad));
   delete m;
 }
 
@@ -296,7 +298,8 @@ int gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const double* y
   if (info != 0) { *info_out = info + (int)n0; return 0; }
   GPRC_TRY(launch_inv512(s, nm->packed, n_pad1, nm->winv, inv.p, 0, p0));
   GPRC_TRY(gpr_alpha_logp(nm.get(), inv.p));
-  // success: the new buffers become the model's, the old ones leave with `nm` (free_model sizes them by the swapped n, n_pad)
+  // success: the new buffers become the model's, the old ones leave with `nm` (free_model sizes them by the swapped n, n_pad) -- the
+  // reversed factor of gprc_gpr_predict_grad among them: the factor has changed, the next gradient call builds it again
   nm->noise = m->noise;   // (context, kernel, type and d are the same in both)
   std::swap(*m, *nm);
   return 0;
@@ -476,6 +479,58 @@ int predict_entry(gprc_model* m, int type, const char* not_type, const char* bad
   return finish_sync(s, a, &b);
 }
 
+// The reversed factor of a model (kernels_vec.hip, reverse_factor_kernel), built on the first call that needs it and kept
+int ensure_reversed_factor(gprc_model* m) {
+  if (m->packed_rev && m->winv_rev) return 0;
+  gprc_ctx* ctx = m->ctx;
+  const size_t pb = sizeof(double) * (size_t)gprc_packed_size(m->n_pad), wb = sizeof(double) * (size_t)gprc_winv_size(m->n_pad);
+  void *pr = nullptr, *wr = nullptr;
+  int rc = pool_alloc(ctx, pb, &pr);
+  if (rc == 0 && (rc = pool_alloc(ctx, wb, &wr)) != 0) pool_release(ctx, pr, pb);
+  if (rc != 0) {
+    if (rc == GPRC_ERR_NOMEM)
+      set_error("predict_grad: the variance's gradient needs a second copy of the factor, " + std::to_string((pb + wb) >> 20) +
+                " MiB of device memory, which could not be allocated (the model is unchanged; mean, variance and the mean's gradient need none)");
+    return rc;
+  }
+  rc = launch_reverse_factor(ctx->stream, m->packed, m->winv, m->n_pad, (double*)pr, (double*)wr);
+  if (rc != 0) { pool_release(ctx, pr, pb); pool_release(ctx, wr, wb); return rc; }
+  m->packed_rev = (double*)pr;
+  m->winv_rev = (double*)wr;
+  return 0;
+}
+
+// One chunk of gprc_gpr_predict_grad: the stages of predict_chunk (same launches in the same order for the mean and the variance),
+// then   vt := vt J,  vt := vt M^-T = (V L^-1) J   with the reversed factor,   the contraction and its tails.
+// Null outputs switch their stages off; vt / part / kss_c are null when neither the mean nor a solve is wanted.
+int predict_grad_chunk(gprc_model* m, const double* xc, int64_t mcur, double* vt, int64_t ldv, double* part, double* kss_c, double* pmean,
+                       double* pvar, double* mean_out, double* var_out, double* dmean_out, double* dvar_out) {
+  gprc_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n, n_pad = m->n_pad, d = m->d, m_pad = pad_up(mcur, 128);
+  const bool solve = var_out || dvar_out;
+  if (mean_out || solve) {
+    const int64_t mt = fill_mean_tiles(n_pad);
+    double* mpart = part;
+    double* sspart = part + mt * m_pad;
+    GPRC_TRY(launch_fill_cross_fused(s, m->ks, xc, mcur, m->X, n, d, vt, ldv, m_pad, n_pad, mean_out ? m->alpha : nullptr, mpart, nullptr));
+    if (solve) GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, ldv, m_pad, var_out ? sspart : nullptr));
+    if (mean_out) GPRC_TRY(launch_sum_partials(s, mpart, mt, m_pad, mcur, nullptr, mean_out));
+    if (var_out) {
+      GPRC_TRY(launch_colwise(s, m->ks, xc, xc, d, mcur, kss_c));
+      GPRC_TRY(launch_sum_partials(s, sspart, n_pad / NBI, m_pad, mcur, kss_c, var_out));
+    }
+  }
+  if (dvar_out) {
+    GPRC_TRY(launch_reverse_cols(s, vt, ldv, m_pad, n_pad));
+    GPRC_TRY(solve_rows(ctx, m->packed_rev, m->winv_rev, n_pad, vt, ldv, m_pad));
+  }
+  if (pmean || pvar) GPRC_TRY(launch_pred_grad(s, m->ks, xc, mcur, m_pad, m->X, n, n_pad, d, m->alpha, dvar_out ? vt : nullptr, ldv, pmean, pvar));
+  if (dmean_out) GPRC_TRY(launch_pred_grad_sum(s, m->ks, pmean, n_pad, d, m_pad, mcur, false, dmean_out));
+  if (dvar_out) GPRC_TRY(launch_pred_grad_sum(s, m->ks, pvar, n_pad, d, m_pad, mcur, true, dvar_out));
+  return 0;
+}
+
 }  // namespace
 
 }  // namespace gprc
@@ -620,6 +675,50 @@ int gprc_gpr_predict(gprc_model* m, const double* X_star, int64_t ns, int pointw
     GPRC_HIP(hipStreamSynchronize(s));  // cov goes out of scope
     return 0;
   });
+}
+
+// mean, variance and their gradients with respect to the test points ("Prediction gradients"), chunk by chunk
+int gprc_gpr_predict_grad(gprc_model* m, const double* X_star, int64_t ns, double* mean_out, double* var_out, double* dmean_out, double* dvar_out) {
+  if (!m || m->type != MODEL_GPR) { set_error("predict_grad: not a GPR model"); return GPRC_ERR_ARG; }
+  if (m->borrowed) {
+    set_error("predict_grad: the model borrows its buffers (gprc_gpr_model_from_device / gprc_mgpu_model_rank) and cannot own a reversed factor");
+    return GPRC_ERR_ARG;
+  }
+  if (ns < 1 || !X_star) { set_error("predict_grad: bad arguments (n_star >= 1, non-null X_star)"); return GPRC_ERR_ARG; }
+  if (!mean_out && !var_out && !dmean_out && !dvar_out) { set_error("predict_grad: all four outputs are null"); return GPRC_ERR_ARG; }
+  GPRC_TRY(check_grad_kernel("predict_grad", m->ks.id));
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("predict_grad: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const int64_t d = m->d, n_pad = m->n_pad;
+  In xs;
+  Out om, ov, odm, odv;
+  GPRC_TRY(xs.set(s, X_star, d * ns));
+  if (mean_out) GPRC_TRY(om.set(mean_out, ns));
+  if (var_out) GPRC_TRY(ov.set(var_out, ns));
+  if (dmean_out) GPRC_TRY(odm.set(dmean_out, d * ns));
+  if (dvar_out) GPRC_TRY(odv.set(dvar_out, d * ns));
+  if (dvar_out) GPRC_TRY(ensure_reversed_factor(m));
+  int64_t rows = std::min<int64_t>(pad_up(ns, 128), 32768);   // the mean's gradient alone: no chunk of K* exists, only the partials
+  double *vt = nullptr, *part = nullptr, *tmp = nullptr;
+  if (mean_out || var_out || dvar_out) GPRC_TRY(chunk_workspace(ctx, n_pad, ns, true, &rows, &vt, &part, &tmp));
+  const int64_t ldv = rows + ctx->vt_pad;
+  const int64_t pcount = pred_grad_stripes(n_pad) * d * rows;
+  DevMem pmean, pvar;
+  if (dmean_out) GPRC_TRY(pmean.alloc(pcount));
+  if (dvar_out) GPRC_TRY(pvar.alloc(pcount));
+  for (int64_t s0 = 0; s0 < ns; s0 += rows) {
+    const int64_t mcur = std::min<int64_t>(rows, ns - s0);
+    GPRC_TRY(predict_grad_chunk(m, xs.dev + s0 * d, mcur, vt, ldv, part, tmp, pmean.p, pvar.p, mean_out ? om.dev + s0 : nullptr,
+                                var_out ? ov.dev + s0 : nullptr, dmean_out ? odm.dev + s0 * d : nullptr, dvar_out ? odv.dev + s0 * d : nullptr));
+  }
+  if (mean_out) GPRC_TRY(om.finish(s));
+  if (var_out) GPRC_TRY(ov.finish(s));
+  if (dmean_out) GPRC_TRY(odm.finish(s));
+  if (dvar_out) GPRC_TRY(odv.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
 }
 
 int gprc_gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const double* y_new) {

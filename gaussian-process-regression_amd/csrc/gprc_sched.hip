@@ -397,6 +397,11 @@ int gprc_dev_solve_rows(gprc_ctx* ctx, const double* packed, const double* winv,
   return solve_rows(ctx, packed, winv, n_pad, vt, ld, m_pad);
 }
 
+int gprc_dev_reverse_factor(gprc_ctx* ctx, const double* packed, const double* winv, int64_t n_pad, double* packed_rev, double* winv_rev) {
+  GPRC_TRY(use_device_unless(ctx, !packed || !winv || !packed_rev || !winv_rev || n_pad <= 0 || n_pad % NB, "dev_reverse_factor: bad arguments"));
+  return launch_reverse_factor(ctx->stream, packed, winv, n_pad, packed_rev, winv_rev);
+}
+
 int gprc_prof_panel_trace(gprc_ctx* ctx, int side, int64_t* ticks_out, int n) {
   GPRC_TRY(use_device_unless(ctx, !ticks_out || n < 1 || n > 24, "prof_panel_trace: 1..24 stamps"));
   GPRC_HIP(hipDeviceSynchronize());

@@ -554,6 +554,78 @@ __global__ __launch_bounds__(64) void gpc_class_prob_kernel(const double* fs, co
   out[i] = acc;
 }
 
+// ---- reversed factor: V L^-1 through the solve that knows only V L^-T ("Prediction gradients") ------------
+// With J the reversal of n_pad indices, M = J L^T J is lower triangular: M[i, j] = L[n_pad - 1 - j, n_pad - 1 - i], and
+// V L^-1 = ((V J) M^-T) J.  One workgroup moves one 64 x 64 tile: the tile of L that mirrors it is read down L's columns (16 bytes a
+// lane), turned in LDS (rows padded to 65 doubles) and written down M's columns (16 bytes a lane).  Panel q of M (leading dimension
+// n_pad - q NB, as L's panel q) takes its rows from the row block P - 1 - q of L, i.e. from L's panels 0 .. P - 1 - q.  Tiles on the
+// diagonal keep their lower triangle only, tiles above it (inside the NB x NB diagonal block) are written as zero: whatever L's buffer
+// holds above its diagonal never arrives.  blockIdx.y == P: the 128 x 128 inverses, block b of winv_rev = J winv_block(B - 1 - b)^T J.
+constexpr int RV_T = 64;
+__global__ __launch_bounds__(256) void reverse_factor_kernel(const double* __restrict__ packed, const double* __restrict__ winv, int64_t n_pad,
+                                                             double* __restrict__ packed_rev, double* __restrict__ winv_rev) {
+  __shared__ double S[RV_T][RV_T + 1];   // S[column of the source tile][its row]
+  const int64_t P = n_pad / NB, q = blockIdx.y, tile = blockIdx.x;
+  const int t = threadIdx.x;
+  const double* src;
+  double* dst;
+  int64_t ld_s, ld_d;
+  int kind = 0;   // 0: whole tile, 1: diagonal tile (zero above the diagonal), 2: zero
+  if (q < P) {
+    const int64_t ld = n_pad - q * NB, tiles_r = ld / RV_T;
+    if (tile >= tiles_r * (NB / RV_T)) return;
+    const int64_t tj = tile / tiles_r, ti = tile - tj * tiles_r;   // consecutive workgroups go down a column of M
+    kind = ti > tj ? 0 : (ti == tj ? 1 : 2);
+    ld_d = ld;
+    dst = packed_rev + panel_offset(n_pad, q) + ti * RV_T + tj * RV_T * ld;
+    const int64_t r0 = ld - RV_T * (tj + 1), c0 = ld - RV_T * (ti + 1);   // first GLOBAL row and column of the source tile in L (c0 <= r0)
+    const int64_t pl = c0 / NB;
+    ld_s = n_pad - pl * NB;
+    src = packed + panel_offset(n_pad, pl) + (r0 - pl * NB) + (c0 - pl * NB) * ld_s;
+  } else {
+    const int64_t B = n_pad / NBI;
+    if (tile >= 4 * B) return;
+    const int64_t b = tile >> 2, tj = (tile >> 1) & 1, ti = tile & 1;
+    ld_s = ld_d = NBI;
+    dst = winv_rev + b * NBI * NBI + ti * RV_T + tj * RV_T * NBI;
+    src = winv + (B - 1 - b) * NBI * NBI + (NBI - RV_T * (tj + 1)) + (NBI - RV_T * (ti + 1)) * NBI;
+  }
+  if (kind != 2) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int idx = t + 256 * k, rp = idx & 31, col = idx >> 5;
+      const double2 v = *reinterpret_cast<const double2*>(src + 2 * rp + col * ld_s);
+      S[col][2 * rp] = v.x;
+      S[col][2 * rp + 1] = v.y;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int idx = t + 256 * k, a = 2 * (idx & 31), b = idx >> 5;   // rows a, a + 1 and column b of the tile of M
+    double2 v = make_double2(0.0, 0.0);
+    if (kind != 2) v = make_double2(S[RV_T - 1 - a][RV_T - 1 - b], S[RV_T - 2 - a][RV_T - 1 - b]);
+    if (kind == 1) {
+      if (a < b) v.x = 0.0;
+      if (a + 1 < b) v.y = 0.0;
+    }
+    *reinterpret_cast<double2*>(dst + a + b * ld_d) = v;
+  }
+}
+
+// vt[:, j] <-> vt[:, cols - 1 - j] for the first `rows` rows (rows even), in place; a thread swaps two rows of a column pair
+__global__ __launch_bounds__(256) void reverse_cols_kernel(double* vt, int64_t ld, int64_t rows, int64_t cols) {
+  const int64_t i = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+  if (i >= rows) return;
+  for (int64_t j = blockIdx.y; j < cols / 2; j += gridDim.y) {
+    double2* lo = reinterpret_cast<double2*>(vt + i + j * ld);
+    double2* hi = reinterpret_cast<double2*>(vt + i + (cols - 1 - j) * ld);
+    const double2 a = *lo, b = *hi;
+    *lo = b;
+    *hi = a;
+  }
+}
+
 inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -648,6 +720,30 @@ int launch_sum_partials(hipStream_t s, const double* part, int64_t nparts, int64
   if (rows <= 0) return 0;
   ProfScope ps(s, PK_ROWREDUCE, (double)rows * nparts, 8.0 * rows * nparts);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(blocks(rows, 256)), dim3(256), 0, s, part, nparts, stride, rows, minuend, out);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_reverse_factor(hipStream_t s, const double* packed, const double* winv, int64_t n_pad, double* packed_rev, double* winv_rev) {
+  if (n_pad <= 0 || n_pad % NB) { set_error("reverse_factor: n_pad must be a positive multiple of the panel width"); return GPRC_ERR_ARG; }
+  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(winv) | reinterpret_cast<uintptr_t>(packed_rev) | reinterpret_cast<uintptr_t>(winv_rev)) & 15) {
+    set_error("reverse_factor: the buffers must be 16-byte aligned");
+    return GPRC_ERR_ARG;
+  }
+  const int64_t P = n_pad / NB;
+  const double bytes = 16.0 * ((double)panel_offset(n_pad, P) + (double)n_pad * NBI);   // every element read once, written once
+  ProfScope ps(s, PK_REVERSE_FACTOR, 0.0, bytes);
+  hipLaunchKernelGGL(reverse_factor_kernel, dim3((unsigned)((n_pad / RV_T) * (NB / RV_T)), (unsigned)(P + 1)), dim3(256), 0, s, packed, winv, n_pad,
+                     packed_rev, winv_rev);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_reverse_cols(hipStream_t s, double* vt, int64_t ld, int64_t rows, int64_t cols) {
+  if (rows <= 0 || cols <= 1) return 0;
+  if ((rows & 1) || (ld & 1) || (reinterpret_cast<uintptr_t>(vt) & 15)) { set_error("reverse_cols: 16-byte aligned chunk with even rows and leading dimension"); return GPRC_ERR_ARG; }
+  const int64_t pairs = cols / 2;
+  hipLaunchKernelGGL(reverse_cols_kernel, dim3(blocks(rows / 2, 256), (unsigned)(pairs < 16384 ? pairs : 16384)), dim3(256), 0, s, vt, ld, rows, cols);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

@@ -129,6 +129,29 @@ class GPR:
         nat.check(nat.lib().gprc_gpr_predict(self._model, Xs.ctypes.data, ns, 0, mean.ctypes.data, cov.ctypes.data))
         return [mean.reshape(-1, 1), cov]                                                    # :168
 
+    def predict_grad(self, X_star, variance=True):
+        """Prediction and its gradients with respect to the test points (gprc_gpr_predict_grad; no reference counterpart): returns
+        (pred, dmean, dvar) with pred the n* x 2 array cbind(mean, variance) of predict(X_star), dmean[c, i] = d mean_i / d X_star[c, i]
+        and dvar[c, i] = d variance_i / d X_star[c, i], both d x n*.  variance=False skips the second solve and the reversed factor the
+        variance's gradient keeps in the model (a second copy of the factor): dvar is None.  Kernels: sqrexp, sqrexp_ard, gammaexp,
+        rationalquadratic; gammaexp at a test point equal to a training point takes that pair's contribution as 0."""
+        d = self._X.shape[0]
+        Xs = np.asarray(X_star)
+        if Xs.dtype.kind not in "fiub" or Xs.size % d:
+            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")  # as :156
+        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
+        if Xs.shape[0] != d:
+            raise ValueError("X_star must have nrow(X) rows")
+        if self._mmodel is not None:
+            raise ValueError("predict_grad: a model fitted over several devices has no prediction gradients; refit GPR on one device")
+        ns = Xs.shape[1]
+        mean, var = np.empty(ns), np.empty(ns)
+        dmean = np.empty((d, ns), order="F")
+        dvar = np.empty((d, ns), order="F") if variance else None
+        nat.check(nat.lib().gprc_gpr_predict_grad(self._model, Xs.ctypes.data, ns, mean.ctypes.data, var.ctypes.data, dmean.ctypes.data,
+                                                  dvar.ctypes.data if variance else None))
+        return np.column_stack([mean, var]), dmean, dvar
+
     def add_data(self, X_new, y_new):
         """Append observations: the model becomes GPR$new(cbind(X, X_new), c(y, y_new), noise = $noise, k) -- same kernel,
         parameters and stored noise (a jitter the fit added is kept, never re-tried) -- without refactoring the whole matrix

@@ -94,6 +94,17 @@ covariance_matrix <- function(A, B, covariance_function) {
   private$.L <- NULL
 }
 
+# body of GPR$predict_grad after its input checks, native branch: list(mean, var, dmean, dvar) -- the prediction at the test points
+# and its gradients with respect to them, d x n* each (gprc_gpr_predict_grad); variance = FALSE: dvar is NULL and the model keeps no
+# reversed factor
+.gpr_predict_grad_native <- function(private, X_star, variance = TRUE) {
+  if (isTRUE(private$.multi)) stop("gprc: a model fitted over several GPUs has no prediction gradients; refit on one GPU")
+  storage.mode(X_star) <- "double"
+  res <- .Call(gprc_R_gpr_predict_grad, private$.handle, X_star, isTRUE(variance))
+  names(res) <- c("mean", "var", "dmean", "dvar")
+  res
+}
+
 # body of GPC$initialize (R/GPCclass.R:73-103), native branch
 .gpc_initialize_native <- function(private, X, y, k, epsilon) {
   tag <- attr(k, "gprc_kernel")

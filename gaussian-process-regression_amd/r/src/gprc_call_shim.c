@@ -134,6 +134,33 @@ SEXP gprc_R_gpr_extend(SEXP handle, SEXP X_new, SEXP y_new) {
   return res;
 }
 
+/* GPR$predict_grad(X_star, variance): list(mean n*, var n*, dmean d x n*, dvar d x n* or NULL) -- the prediction and its gradients
+ * with respect to the test points (gprc_gpr_predict_grad).  variance = FALSE: no second solve, no reversed factor, dvar = NULL. */
+SEXP gprc_R_gpr_predict_grad(SEXP handle, SEXP X_star, SEXP variance) {
+  gprc_model* m = model_of(handle);
+  int64_t n = 0, d = 0;
+  gprc_model_dims(m, &n, &d);
+  const int64_t ns = Rf_ncols(X_star);
+  const int with_var = Rf_asLogical(variance);
+  if (Rf_nrows(X_star) != d) Rf_error("gprc: X_star must have nrow(X) rows");
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+  SEXP mean = Rf_allocVector(REALSXP, (R_xlen_t)ns);
+  SET_VECTOR_ELT(res, 0, mean);
+  SEXP var = Rf_allocVector(REALSXP, (R_xlen_t)ns);
+  SET_VECTOR_ELT(res, 1, var);
+  SEXP dmean = Rf_allocMatrix(REALSXP, (int)d, (int)ns);
+  SET_VECTOR_ELT(res, 2, dmean);
+  SEXP dvar = R_NilValue;
+  if (with_var) {
+    dvar = Rf_allocMatrix(REALSXP, (int)d, (int)ns);
+    SET_VECTOR_ELT(res, 3, dvar);
+  }
+  const int rc = gprc_gpr_predict_grad(m, REAL(X_star), ns, REAL(mean), REAL(var), REAL(dmean), with_var ? REAL(dvar) : NULL);
+  UNPROTECT(1);
+  if (rc != 0) Rf_error("gprc: %s", gprc_last_error());
+  return res;
+}
+
 /* ---- multi-GPU from R's one process: options(gprc.devices = c(0, 1, ..., 7)) selects it (native.R) ------------------
  * One gprc_mgpu per distinct (devices, flags) request, ALL kept until the package is unloaded: creating the streams / RCCL
  * communicators is not free, and GPR objects fitted earlier hold gprc_mgpu_model handles into theirs -- destroying a
@@ -365,6 +392,7 @@ static const R_CallMethodDef call_methods[] = {
     {"gprc_R_gpr_fit", (DL_FUNC)&gprc_R_gpr_fit, 5},
     {"gprc_R_gpr_predict", (DL_FUNC)&gprc_R_gpr_predict, 3},
     {"gprc_R_gpr_extend", (DL_FUNC)&gprc_R_gpr_extend, 3},
+    {"gprc_R_gpr_predict_grad", (DL_FUNC)&gprc_R_gpr_predict_grad, 3},
     {"gprc_R_model_L", (DL_FUNC)&gprc_R_model_L, 1},
     {"gprc_R_gpc_fit", (DL_FUNC)&gprc_R_gpc_fit, 5},
     {"gprc_R_gpc_predict_latent", (DL_FUNC)&gprc_R_gpc_predict_latent, 2},

@@ -156,6 +156,24 @@ GPRC_API int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params,
  * pointwise == 0: mean_out[n_star], var_out = n_star x n_star K(X*,X*) - t(v) %*% v (:167-168) */
 GPRC_API int gprc_gpr_predict(gprc_model* model, const double* X_star, int64_t n_star, int pointwise, double* mean_out,
                      double* var_out);
+/* The posterior mean and pointwise variance at the test points AND their gradients with respect to the test points -- what maximising
+ * an acquisition function over x* needs (no reference counterpart).  With k*_j = k(x*, x_j), v = L^-1 k*, w = L^-T v = K_y^-1 k*:
+ *   d mu / d x*_c = sum_j alpha_j dk(x*, x_j) / d x*_c,     d sigma^2 / d x*_c = -2 sum_j w_j dk(x*, x_j) / d x*_c
+ * (d k(x*, x*) / d x* = 0: the kernels are stationary).  X_star: d x n_star.  mean_out, var_out: n_star doubles each, bit for bit what
+ * gprc_gpr_predict(pointwise = 1) returns; dmean_out, dvar_out: d x n_star column-major (X_star's layout).  Each of the four may be
+ * NULL (not all): without dvar_out the second solve is skipped, without var_out as well the first one too -- the mean's gradient alone
+ * is one pass over the pairs.  All pointers host or device, as gprc_gpr_predict.  Results do not depend on the chunking, bit for bit.
+ * Kernels: GPRC_SQREXP, GPRC_SQREXP_ARD, GPRC_GAMMAEXP, GPRC_RATQUAD.  gammaexp at a test point that EQUALS a training point (r = 0):
+ * that pair contributes 0 -- the limit for gamma > 1, a convention for gamma <= 1, where the kernel is not differentiable there.
+ * MEMORY: the variance's gradient needs W = V L^-1, which the row solve (V L^-T only) computes with the REVERSED factor J L^T J.  It is
+ * built by the first call that passes dvar_out and kept in the model: a second copy of the factor and of its block inverses,
+ * gprc_packed_size + gprc_winv_size doubles (17 GB at n = 65536).  GPRC_ERR_NOMEM, with the size in the text, when it cannot be
+ * allocated: the model stays usable for everything else.  gprc_model_free releases it, gprc_gpr_extend drops it (the next call
+ * rebuilds it); gprc_ctx_trim does NOT release it: it belongs to the model, not to the context's workspace.
+ * GPRC_ERR_ARG: a GPC model, a borrowed model (gprc_gpr_model_from_device, gprc_mgpu_model_rank), n_star < 1, all four outputs NULL,
+ * a kernel without a gradient (constant, linear, polynomial). */
+GPRC_API int gprc_gpr_predict_grad(gprc_model* model, const double* X_star, int64_t n_star, double* mean_out, double* var_out,
+                                   double* dmean_out, double* dvar_out);
 /* Append m observations (X_new: d x m, y_new: m) to a fitted GPR model in place of GPR$new on
  * cbind(X, X_new), c(y, y_new) with the model's kernel, parameters and stored $noise (jitter kept, never re-tried).
  * Only the factor's columns behind the last panel boundary n0 = floor(n / 512) 512 are recomputed: the new rows of the
@@ -307,6 +325,12 @@ GPRC_API int gprc_gpr_model_from_device(gprc_ctx* ctx, int kernel, const double*
 /* vt := vt * L^-T  (row i becomes (L^-1 k_i)^T) */
 GPRC_API int gprc_dev_solve_rows(gprc_ctx* ctx, const double* packed, const double* winv, int64_t n_pad, double* vt,
                         int64_t ld, int64_t m_pad);
+/* The reversed factor: with J the reversal of n_pad indices, M = J L^T J is lower triangular (M[i, j] = L[n_pad - 1 - j, n_pad - 1 - i]) and
+ * V L^-1 = ((V J) M^-T) J, so gprc_dev_solve_rows(packed_rev, winv_rev) on a column-reversed chunk is the backward solve.  packed_rev,
+ * winv_rev: the sizes and layout of packed, winv; the part of M's diagonal blocks above the diagonal is written as zero; block b of
+ * winv_rev = J winv_block(n_pad / 128 - 1 - b)^T J.  Pure data movement: exact.  Asynchronous, as the other gprc_dev_*. */
+GPRC_API int gprc_dev_reverse_factor(gprc_ctx* ctx, const double* packed, const double* winv, int64_t n_pad, double* packed_rev,
+                                     double* winv_rev);
 
 /* ---- multi-GPU from ONE process (SURVEY 8b "Threading", 8e): the form the R `.Call` boundary can use ------------ *
  * The reference's host is a single R process; it cannot be forked per GPU.  A gprc_mgpu drives G ranks -- one per
@@ -393,7 +417,8 @@ GPRC_API int gprc_combine_all(gprc_ctx* ctx, const double* axis_values, const in
  * 0 fill, 1 potf2_inv, 2 trsm_panel, 3 in-panel GEMM (K=128), 4 trailing update, 5 predict right
  * update (K=512), 6 trsv, 7 row reductions, 8 covariance SYRK, 9 derivative row sums, 10 Jacobi sweep, 11 predict
  * left-looking update, 12 trailing left-looking update, 13 fused panel factorisation, 14 fused in-panel solve of the predict, 15 inverse GEMM
- * (-L^-T L^-1, lower), 16 gradient contraction (gprc_gpr_logp_grad), 17 Laplace gradient contraction (gprc_gpc_logq_grad).  flops/bytes are the ALGORITHMIC
+ * (-L^-T L^-1, lower), 16 gradient contraction (gprc_gpr_logp_grad), 17 Laplace gradient contraction (gprc_gpc_logq_grad),
+ * 18 factor reversal, 19 prediction-gradient contraction (gprc_gpr_predict_grad).  flops/bytes are the ALGORITHMIC
  * figures of DESIGN.md for the launches seen, not counter readings. */
 GPRC_API int gprc_prof_enable(int on);
 /* With the environment variable GPRC_PANEL_TRACE=<p> set, the factor role of the fused panel kernel of panel p leaves
