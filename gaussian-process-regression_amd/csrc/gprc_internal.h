@@ -6,6 +6,9 @@
 //                   the gprc_dev_* building blocks
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
+// Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
+// pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip and kernels_pgrad.hip, the
+// kernel-id dispatcher and the set of kernels with an exact gradient).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -118,12 +121,12 @@ int launch_colwise(hipStream_t s, const KernelSpec& ks, const double* x, const d
 int64_t fill_mean_tiles(int64_t cols);
 int launch_fill_cross_fused(hipStream_t s, const KernelSpec& ks, const double* Xs, int64_t m, const double* X, int64_t n, int64_t d,
                             double* vt, int64_t ld, int64_t m_pad, int64_t n_pad, const double* w, double* mpart, const double* colscale);
-// S[r + n*i] = sum_c deriv_i(X[,r], X[,c]; v): row sums of the parameter derivatives of K(X,X) as cov_dict$...$deriv
-// (R/fit.R:4-31) defines them; n_deriv (1 or 2) components.  Kernels: sqrexp, gammaexp, polynomial, rationalquadratic.
-int launch_deriv_rowsum(hipStream_t s, int kernel, double v0, double v1, const double* X, int64_t d, int64_t n, double* S);
 int launch_set_identity_rows(hipStream_t s, double* vt, int64_t ld, int64_t rows, int64_t cols, int64_t row0);  // vt[i,j] = (row0+i == j)
 
 // ---- launchers (kernels_grad.hip) --------------------------------------------------------------
+// S[r + n*i] = sum_c deriv_i(X[,r], X[,c]; v): row sums of the parameter derivatives of K(X,X) as cov_dict$...$deriv
+// (R/fit.R:4-31) defines them; n_deriv (1 or 2) components.  Kernels: sqrexp, gammaexp, polynomial, rationalquadratic.
+int launch_deriv_rowsum(hipStream_t s, int kernel, double v0, double v1, const double* X, int64_t d, int64_t n, double* S);
 // the exact gradient's contraction: one pass over the stored lower triangle of W = -(K + noise I)^-1 (n_pad x n_pad, ld), K and dK/dtheta
 // recomputed from X.  part: grad_partial_rows() x (ks.n_params + 1) doubles, row g = what workgroup g summed over its tiles of
 //   sum_ij (alpha_i alpha_j + W_ij) dK_ij / dtheta_k   (ARD: times l_k, the host divides)   and, last, of sum_i (alpha_i^2 + W_ii);

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "gprc_host.h"
+#include "pair_tile.h"
 
 namespace gprc {
 
@@ -222,26 +223,42 @@ int mvn_factor_dev(gprc_ctx* ctx, const double* cov_dev, int64_t ld, int64_t m, 
   return 0;
 }
 
-// One chunk of the pointwise predict, everything fused ("Predict epilogues"):
-//   fill K*^T chunk   + per-tile partials of K*^T w            (w = alpha; GPC: g, with the stored columns scaled by sqrt(W))
+// One chunk of the test points, everything fused ("Predict epilogues"; section 7, "Prediction gradients"): THE
+// chunk pipeline of gprc_gpr_predict, gprc_gpc_predict_latent and gprc_gpr_predict_grad.
+//   fill K*^T chunk   + per-tile partials of K*^T w            (w = alpha; GPC: g, with the stored columns scaled by colscale = sqrt(W))
 //   vt := vt L^-T     + per-block sums of squares in the panel solves
 //   tail              mean = sum of the fill partials; var = k(x*,x*) - sum of the block sums     (R/GPRclass.R:161,164)
-// The chunk is written once by the fill and read/written only by the solve: the two row-reduction passes over it are gone.
-int predict_chunk(gprc_model* m, const double* xc, int64_t mcur, double* vt, int64_t ldv, double* part, double* kss_c,
-                  const double* colscale, double* mean_out, double* var_out) {
+//   gradients         vt := vt J,  vt := vt M^-T = (V L^-1) J  with the reversed factor,  the contraction and its two tails
+// The chunk is written once by the fill and read/written only by the solves: the two row-reduction passes over it are gone.
+// Null outputs switch their stages off; want_solved: the caller reads vt = V L^-1 afterwards (the full covariance), so the solve runs
+// whatever the outputs.  vt / part / kss_c are null when neither the mean nor a solve is wanted.  Mean and variance are the same
+// launches with the same arguments for every caller: their bits do not depend on which gradients are asked for.
+int predict_chunk(gprc_model* m, const double* xc, int64_t mcur, double* vt, int64_t ldv, double* part, double* kss_c, const double* colscale,
+                  bool want_solved, double* mean_out, double* var_out, double* pmean = nullptr, double* pvar = nullptr, double* dmean_out = nullptr,
+                  double* dvar_out = nullptr) {
   gprc_ctx* ctx = m->ctx;
   hipStream_t s = ctx->stream;
-  const int64_t n = m->n, n_pad = m->n_pad, d = m->d, m_pad = pad_up(mcur, 128);
-  const int64_t mt = fill_mean_tiles(n_pad);
-  double* mpart = part;
-  double* sspart = part + mt * m_pad;
-  GPRC_TRY(launch_fill_cross_fused(s, m->ks, xc, mcur, m->X, n, d, vt, ldv, m_pad, n_pad, m->alpha, mpart, colscale));  // :160-161
-  GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, ldv, m_pad, var_out ? sspart : nullptr));                       // :162
-  GPRC_TRY(launch_sum_partials(s, mpart, mt, m_pad, mcur, nullptr, mean_out));
-  if (var_out) {
-    GPRC_TRY(launch_colwise(s, m->ks, xc, xc, d, mcur, kss_c));                                                           // k(X*,X*)  :164
-    GPRC_TRY(launch_sum_partials(s, sspart, n_pad / NBI, m_pad, mcur, kss_c, var_out));
+  const int64_t n = m->n, n_pad = m->n_pad, d = m->d, m_pad = pad_up(mcur, PT_R);
+  const bool solve = want_solved || var_out || dvar_out;
+  if (mean_out || solve) {
+    const int64_t mt = fill_mean_tiles(n_pad);
+    double* mpart = part;
+    double* sspart = part + mt * m_pad;
+    GPRC_TRY(launch_fill_cross_fused(s, m->ks, xc, mcur, m->X, n, d, vt, ldv, m_pad, n_pad, mean_out ? m->alpha : nullptr, mpart, colscale));  // :160-161
+    if (solve) GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, ldv, m_pad, var_out ? sspart : nullptr));                                 // :162
+    if (mean_out) GPRC_TRY(launch_sum_partials(s, mpart, mt, m_pad, mcur, nullptr, mean_out));
+    if (var_out) {
+      GPRC_TRY(launch_colwise(s, m->ks, xc, xc, d, mcur, kss_c));                                                                                // k(X*,X*)  :164
+      GPRC_TRY(launch_sum_partials(s, sspart, n_pad / NBI, m_pad, mcur, kss_c, var_out));
+    }
   }
+  if (dvar_out) {
+    GPRC_TRY(launch_reverse_cols(s, vt, ldv, m_pad, n_pad));
+    GPRC_TRY(solve_rows(ctx, m->packed_rev, m->winv_rev, n_pad, vt, ldv, m_pad));
+  }
+  if (pmean || pvar) GPRC_TRY(launch_pred_grad(s, m->ks, xc, mcur, m_pad, m->X, n, n_pad, d, m->alpha, dvar_out ? vt : nullptr, ldv, pmean, pvar));
+  if (dmean_out) GPRC_TRY(launch_pred_grad_sum(s, m->ks, pmean, n_pad, d, m_pad, mcur, false, dmean_out));
+  if (dvar_out) GPRC_TRY(launch_pred_grad_sum(s, m->ks, pvar, n_pad, d, m_pad, mcur, true, dvar_out));
   return 0;
 }
 
@@ -388,13 +405,6 @@ int gpc_mode_search(gprc_model* m, const double* X, const double* y, double epsi
   return factor_B(final_inv ? inv.p : nullptr, "GPC: final factorisation failed");   // final L from the converged f (:99-102)
 }
 
-// Both exact gradients are defined for the kernels whose dK / dtheta kernels_grad.hip knows
-int check_grad_kernel(const char* who, int kernel) {
-  if (kernel == GPRC_SQREXP || kernel == GPRC_GAMMAEXP || kernel == GPRC_RATQUAD || kernel == GPRC_SQREXP_ARD) return 0;
-  set_error(std::string(who) + ": defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard");
-  return GPRC_ERR_ARG;
-}
-
 // W (n_pad x n_pad, ld n_pad, lower triangle) := -V^T V = -(L L^T)^-1 from the model's factor, with V^T = I L^-T (the identity through
 // the predict's solve in its triangular form, as gprc_fit_gradient; row tile r of V^T is zero left of column 128 r, so its products
 // start there), n^3 / 3 flops each.  With m == nullptr only the two workspaces are claimed (slots 0 and 3: gprc_gpc_logq_grad before
@@ -455,7 +465,7 @@ int predict_pointwise(gprc_model* m, const double* xs, int64_t ns, const double*
   const int64_t ldv = rows + ctx->vt_pad;  // one leading dimension for every chunk
   for (int64_t s0 = 0; s0 < ns; s0 += rows) {
     const int64_t mcur = (ns - s0 < rows) ? ns - s0 : rows;
-    GPRC_TRY(predict_chunk(m, xs + s0 * m->d, mcur, vt, ldv, part, tmp, colscale, mean_out + s0, var_out + s0));
+    GPRC_TRY(predict_chunk(m, xs + s0 * m->d, mcur, vt, ldv, part, tmp, colscale, true, mean_out + s0, var_out + s0));
   }
   return 0;
 }
@@ -497,37 +507,6 @@ int ensure_reversed_factor(gprc_model* m) {
   if (rc != 0) { pool_release(ctx, pr, pb); pool_release(ctx, wr, wb); return rc; }
   m->packed_rev = (double*)pr;
   m->winv_rev = (double*)wr;
-  return 0;
-}
-
-// One chunk of gprc_gpr_predict_grad: the stages of predict_chunk (same launches in the same order for the mean and the variance),
-// then   vt := vt J,  vt := vt M^-T = (V L^-1) J   with the reversed factor,   the contraction and its tails.
-// Null outputs switch their stages off; vt / part / kss_c are null when neither the mean nor a solve is wanted.
-int predict_grad_chunk(gprc_model* m, const double* xc, int64_t mcur, double* vt, int64_t ldv, double* part, double* kss_c, double* pmean,
-                       double* pvar, double* mean_out, double* var_out, double* dmean_out, double* dvar_out) {
-  gprc_ctx* ctx = m->ctx;
-  hipStream_t s = ctx->stream;
-  const int64_t n = m->n, n_pad = m->n_pad, d = m->d, m_pad = pad_up(mcur, 128);
-  const bool solve = var_out || dvar_out;
-  if (mean_out || solve) {
-    const int64_t mt = fill_mean_tiles(n_pad);
-    double* mpart = part;
-    double* sspart = part + mt * m_pad;
-    GPRC_TRY(launch_fill_cross_fused(s, m->ks, xc, mcur, m->X, n, d, vt, ldv, m_pad, n_pad, mean_out ? m->alpha : nullptr, mpart, nullptr));
-    if (solve) GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, ldv, m_pad, var_out ? sspart : nullptr));
-    if (mean_out) GPRC_TRY(launch_sum_partials(s, mpart, mt, m_pad, mcur, nullptr, mean_out));
-    if (var_out) {
-      GPRC_TRY(launch_colwise(s, m->ks, xc, xc, d, mcur, kss_c));
-      GPRC_TRY(launch_sum_partials(s, sspart, n_pad / NBI, m_pad, mcur, kss_c, var_out));
-    }
-  }
-  if (dvar_out) {
-    GPRC_TRY(launch_reverse_cols(s, vt, ldv, m_pad, n_pad));
-    GPRC_TRY(solve_rows(ctx, m->packed_rev, m->winv_rev, n_pad, vt, ldv, m_pad));
-  }
-  if (pmean || pvar) GPRC_TRY(launch_pred_grad(s, m->ks, xc, mcur, m_pad, m->X, n, n_pad, d, m->alpha, dvar_out ? vt : nullptr, ldv, pmean, pvar));
-  if (dmean_out) GPRC_TRY(launch_pred_grad_sum(s, m->ks, pmean, n_pad, d, m_pad, mcur, false, dmean_out));
-  if (dvar_out) GPRC_TRY(launch_pred_grad_sum(s, m->ks, pvar, n_pad, d, m_pad, mcur, true, dvar_out));
   return 0;
 }
 
@@ -662,13 +641,13 @@ int gprc_gpr_predict(gprc_model* m, const double* X_star, int64_t ns, int pointw
     // the full covariance needs all of v at once: no chunking to fall back on
     gprc_ctx* ctx = m->ctx;
     hipStream_t s = ctx->stream;
-    const int64_t n_pad = m->n_pad, d = m->d, m_pad = pad_up(ns, 128), ldv = m_pad + ctx->vt_pad;
+    const int64_t n_pad = m->n_pad, d = m->d, m_pad = pad_up(ns, PT_R), ldv = m_pad + ctx->vt_pad;
     double *vt = nullptr, *part = nullptr, *kss = nullptr, *cov = nullptr;
     GPRC_TRY(ws_get(ctx, 0, ldv * n_pad, &vt));
     GPRC_TRY(ws_get(ctx, 1, m_pad * predict_partials(n_pad), &part));
     GPRC_TRY(ws_get(ctx, 2, m_pad, &kss));
     GPRC_TRY(ws_get(ctx, 3, m_pad * m_pad, &cov));
-    GPRC_TRY(predict_chunk(m, xs, ns, vt, ldv, part, kss, nullptr, mean, nullptr));
+    GPRC_TRY(predict_chunk(m, xs, ns, vt, ldv, part, kss, nullptr, true, mean, nullptr));
     GPRC_TRY(launch_fill(s, m->ks, xs, ns, xs, ns, d, cov, m_pad, 0, m_pad, 0, m_pad, PAD_ZERO, 0.0));  // :167
     GPRC_TRY(launch_gemm_nt(s, cov, m_pad, vt, ldv, vt, ldv, m_pad, m_pad, n_pad, 0, PK_COV_SYRK));      // - t(v) %*% v
     GPRC_HIP(hipMemcpy2DAsync(var, sizeof(double) * ns, cov, sizeof(double) * m_pad, sizeof(double) * ns, ns, hipMemcpyDeviceToDevice, s));
@@ -700,7 +679,7 @@ int gprc_gpr_predict_grad(gprc_model* m, const double* X_star, int64_t ns, doubl
   if (dmean_out) GPRC_TRY(odm.set(dmean_out, d * ns));
   if (dvar_out) GPRC_TRY(odv.set(dvar_out, d * ns));
   if (dvar_out) GPRC_TRY(ensure_reversed_factor(m));
-  int64_t rows = std::min<int64_t>(pad_up(ns, 128), 32768);   // the mean's gradient alone: no chunk of K* exists, only the partials
+  int64_t rows = std::min<int64_t>(pad_up(ns, PT_R), 32768);   // the mean's gradient alone: no chunk of K* exists, only the partials
   double *vt = nullptr, *part = nullptr, *tmp = nullptr;
   if (mean_out || var_out || dvar_out) GPRC_TRY(chunk_workspace(ctx, n_pad, ns, true, &rows, &vt, &part, &tmp));
   const int64_t ldv = rows + ctx->vt_pad;
@@ -710,8 +689,8 @@ int gprc_gpr_predict_grad(gprc_model* m, const double* X_star, int64_t ns, doubl
   if (dvar_out) GPRC_TRY(pvar.alloc(pcount));
   for (int64_t s0 = 0; s0 < ns; s0 += rows) {
     const int64_t mcur = std::min<int64_t>(rows, ns - s0);
-    GPRC_TRY(predict_grad_chunk(m, xs.dev + s0 * d, mcur, vt, ldv, part, tmp, pmean.p, pvar.p, mean_out ? om.dev + s0 : nullptr,
-                                var_out ? ov.dev + s0 : nullptr, dmean_out ? odm.dev + s0 * d : nullptr, dvar_out ? odv.dev + s0 * d : nullptr));
+    GPRC_TRY(predict_chunk(m, xs.dev + s0 * d, mcur, vt, ldv, part, tmp, nullptr, false, mean_out ? om.dev + s0 : nullptr,
+                           var_out ? ov.dev + s0 : nullptr, pmean.p, pvar.p, dmean_out ? odm.dev + s0 * d : nullptr, dvar_out ? odv.dev + s0 * d : nullptr));
   }
   if (mean_out) GPRC_TRY(om.finish(s));
   if (var_out) GPRC_TRY(ov.finish(s));

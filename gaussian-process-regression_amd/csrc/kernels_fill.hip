@@ -3,21 +3,17 @@
 // Replaces covariance_matrix() = outer(1:nA, 1:nB, function(i,j) k(A[,i], B[,j]))
 // (reference R/GPRclass.R:355-357) together with the column-wise kernel bodies (R/GPRclass.R:382-402).
 // The reference materialises two d x (nA*nB) gathers and 4-6 temporaries of that size; here each
-// 128 x 64 output tile stages its 128 + 64 points through LDS once and the only HBM traffic is the
-// 8 B/element store (16 B per lane, 1 KiB contiguous per wave) -- the kernel is HBM-write-bound.
+// 128 x 64 output tile stages its 128 + 64 points through LDS once (pair_tile.h: the tile shape and the staging loop) and the only
+// HBM traffic is the 8 B/element store (16 B per lane, 1 KiB contiguous per wave) -- the kernel is HBM-write-bound.
 //
 // Differences from the reference arithmetic (within the 1e-10 normwise tolerance):
 // colSums() accumulates in 80-bit long double in R; here the d-term sum is an fp64 FMA chain.
 // The direct sum (x-y)^2 form is kept (no Gram trick: ||x||^2+||y||^2-2x.y cancels catastrophically).
-#include "gprc_internal.h"
+#include "pair_tile.h"
 
 namespace gprc {
 
 namespace {
-
-constexpr int FT_R = 128;  // tile rows: 2 consecutive rows per lane x 64 lanes
-constexpr int FT_C = 64;   // tile cols: 16 per wave x 4 waves
-constexpr int FD = 16;     // coordinates staged per pass
 
 struct FillArgs {
   const double* A;
@@ -35,15 +31,7 @@ struct FillArgs {
   const double* colscale;  // stored value = k(.,.) * colscale[col]   (GPC: sqrt(W) * K_star); the mean uses the unscaled value
 };
 
-// base R `^` for doubles (arithmetic.c R_POW / R_pow): x^2 is x*x, the rest is libm pow
-__device__ __forceinline__ double r_pow(double x, double y) {
-  if (y == 2.0) return x * x;
-  if (x == 1.0 || y == 0.0) return 1.0;
-  if (x == 0.0) return y > 0.0 ? 0.0 : (y < 0.0 ? __builtin_huge_val() : y);
-  return pow(x, y);
-}
-
-// per-coordinate accumulation term
+// per-coordinate accumulation term (its ARD form rounds differently from the contraction kernels' staged a * sig - b * sig: pair_tile.h)
 template <int KID>
 __device__ __forceinline__ double accum(double s, double a, double b, double sig) {
   if constexpr (KID == GPRC_LINEAR) return fma(sig * a, b, s);  // colSums(sigma * x * y)
@@ -160,29 +148,22 @@ __device__ __forceinline__ double finish(double s, const KernelSpec& ks) {
 // and may scale the stored columns (GPC).  The K*^T alpha pass over the stored matrix (one full HBM read) disappears.
 template <int KID, bool VEC2, int MODE, bool FUSE>
 __global__ __launch_bounds__(256) void fill_kernel(FillArgs a) {
-  __shared__ __attribute__((aligned(16))) double As[FD][FT_R];
-  __shared__ double Bs[FT_C][FD + 1];
-  __shared__ double Sg[FD];
+  __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];
+  __shared__ double Bs[PT_C][PT_D + 1];
+  __shared__ double Sg[PT_D];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t ti = a.row0 + (int64_t)blockIdx.x * FT_R;  // first global row of the tile
-  const int64_t tj = a.col0 + (int64_t)blockIdx.y * FT_C;
+  const int64_t ti = a.row0 + (int64_t)blockIdx.x * PT_R;  // first global row of the tile
+  const int64_t tj = a.col0 + (int64_t)blockIdx.y * PT_C;
   double s0[16], s1[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) { s0[c] = 0.0; s1[c] = 0.0; }
 
-  for (int64_t r0 = 0; r0 < a.d; r0 += FD) {
-    const int dc = (int)((a.d - r0 < FD) ? (a.d - r0) : FD);
+  for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {
+    const int dc = (int)((a.d - r0 < PT_D) ? (a.d - r0) : PT_D);
     __syncthreads();
-    for (int e = t; e < FT_R * dc; e += 256) {  // A points: point-major in memory
-      int i = e / dc, r = e - i * dc;
-      int64_t gi = ti + i;
-      As[r][i] = (gi < a.nA) ? a.A[gi * a.d + r0 + r] : 0.0;
-    }
-    for (int e = t; e < FT_C * dc; e += 256) {
-      int j = e / dc, r = e - j * dc;
-      int64_t gj = tj + j;
-      Bs[j][r] = (gj < a.nB) ? a.B[gj * a.d + r0 + r] : 0.0;
-    }
+    // unscaled: the per-coordinate factors stay in Sg
+    stage_points<false>(a.A, ti, a.nA, a.d, r0, dc, PT_R, nullptr, t, [&](int i, int r, double v) { As[r][i] = v; });
+    stage_points<false>(a.B, tj, a.nB, a.d, r0, dc, PT_C, nullptr, t, [&](int j, int r, double v) { Bs[j][r] = v; });
     if (t < dc) Sg[t] = (KID == GPRC_LINEAR) ? (a.ks.n_params == 1 ? a.ks.p[0] : a.ks.p[r0 + t]) : (KID == GPRC_SQREXP_ARD) ? a.ks.p[r0 + t] : 1.0;
     __syncthreads();
     for (int r = 0; r < dc; ++r) {
@@ -201,8 +182,8 @@ __global__ __launch_bounds__(256) void fill_kernel(FillArgs a) {
   const int64_t row_end = a.row0 + a.nrows, col_end = a.col0 + a.ncols;
   double m0 = 0.0, m1 = 0.0;  // FUSE: this lane's two rows times w over its 16 columns
   // interior tile: every row/column is a valid point, inside the output window, and (identity mode) off the diagonal
-  const bool interior = VEC2 && ti + FT_R <= a.nA && ti + FT_R <= row_end && tj + FT_C <= a.nB && tj + FT_C <= col_end &&
-                        (MODE != PAD_IDENTITY || ti + FT_R <= tj || tj + FT_C <= ti);
+  const bool interior = VEC2 && ti + PT_R <= a.nA && ti + PT_R <= row_end && tj + PT_C <= a.nB && tj + PT_C <= col_end &&
+                        (MODE != PAD_IDENTITY || ti + PT_R <= tj || tj + PT_C <= ti);
   if (interior) {
     double* dst = a.out + (gi0 - a.row0) + (tj + wave * 16 - a.col0) * a.ld;
 #pragma unroll
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(256) void fill_kernel(FillArgs a) {
       As[wave][2 * lane] = m0;
       As[wave][2 * lane + 1] = m1;
       __syncthreads();
-      if (t < FT_R) a.mpart[(int64_t)blockIdx.y * a.mpart_rows + (int64_t)blockIdx.x * FT_R + t] = ((As[0][t] + As[1][t]) + As[2][t]) + As[3][t];
+      if (t < PT_R) a.mpart[(int64_t)blockIdx.y * a.mpart_rows + (int64_t)blockIdx.x * PT_R + t] = sum4_in_order(As[0][t], As[1][t], As[2][t], As[3][t]);
     }
   }
 }
@@ -295,7 +276,7 @@ KernelSpec make_fill_spec(const KernelSpec& ks) {
 
 template <int KID, int MODE>
 int do_fill_mode(hipStream_t s, const FillArgs& a) {
-  dim3 grid((unsigned)((a.nrows + FT_R - 1) / FT_R), (unsigned)((a.ncols + FT_C - 1) / FT_C));
+  dim3 grid((unsigned)((a.nrows + PT_R - 1) / PT_R), (unsigned)((a.ncols + PT_C - 1) / PT_C));
   const bool vec2 = (a.ld % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
   if constexpr (MODE == PAD_ZERO) {
     if (a.w || a.colscale) {
@@ -319,65 +300,6 @@ int do_fill(hipStream_t s, const FillArgs& a) {
   }
 }
 
-// ---- derivative row sums for fit()'s gradient (R/fit.R:126-139) ---------------------------------------------------
-// deriv(x, y, v...) of cov_dict (R/fit.R:4-31), with v bound POSITIONALLY as the reference's do.call does:
-//   sqrexp (l)            r = |x-y| :  r^2/l^3 * exp(-r^2/(2 l^2))
-//   gammaexp (gamma, l)   r = |x-y| :  ( -exp(-(r/l)^gamma) (r/l)^gamma log(r/l) ,  exp(-(r/l)^gamma) gamma r^gamma / l^(gamma+1) )
-//   polynomial (sigma, p) s = x.y + sigma :  ( p s^(p-1) ,  s^p log(s) )
-//   rationalquadratic (alpha, l)  r = |x-y|^2, q = r/(2 l^2 alpha) + 1 :
-//                         ( q^-alpha (r - (2 l^2 alpha + r) log q) / (2 l^2 alpha + r) ,  r q^(-alpha-1) / l^3 )
-// (gammaexp's first component is 0 * -Inf = NaN at r = 0, i.e. on the diagonal: kept, it decides what optim does.)
-template <int KID>
-__device__ __forceinline__ void deriv_pair(double s, double v0, double v1, double& g0, double& g1) {
-  if constexpr (KID == GPRC_SQREXP) {
-    g0 = s / (v0 * v0 * v0) * exp(-s / ((v0 * v0) * 2.0));
-    g1 = 0.0;
-  } else if constexpr (KID == GPRC_GAMMAEXP) {
-    const double r = sqrt(s), rl = r / v1, e = exp(-r_pow(rl, v0));
-    g0 = -e * r_pow(rl, v0) * log(rl);
-    g1 = e * v0 * r_pow(r, v0) / r_pow(v1, v0 + 1.0);
-  } else if constexpr (KID == GPRC_POLYNOMIAL) {
-    const double t = s + v0;
-    g0 = v1 * r_pow(t, v1 - 1.0);
-    g1 = r_pow(t, v1) * log(t);
-  } else {  // rationalquadratic
-    const double c = 2.0 * (v1 * v1) * v0, q = s / c + 1.0;
-    g0 = (r_pow(q, -v0) * (s - (c + s) * log(q))) / (c + s);
-    g1 = (s * r_pow(q, -v0 - 1.0)) / (v1 * v1 * v1);
-  }
-}
-
-template <int KID>
-__global__ __launch_bounds__(256) void deriv_rowsum_kernel(double v0, double v1, const double* X, int64_t d, int64_t n, double* S) {
-  const int64_t r = blockIdx.x;
-  const double* xr = X + r * d;
-  double a0 = 0.0, a1 = 0.0;
-  for (int64_t c = threadIdx.x; c < n; c += 256) {
-    const double* xc = X + c * d;
-    double s = 0.0;
-    for (int64_t k = 0; k < d; ++k) {
-      if constexpr (KID == GPRC_POLYNOMIAL) s += xr[k] * xc[k];
-      else { const double t = xr[k] - xc[k]; s += t * t; }
-    }
-    double g0, g1;
-    deriv_pair<KID>(s, v0, v1, g0, g1);
-    a0 += g0;
-    a1 += g1;
-  }
-  __shared__ double red[2][4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    a0 += __shfl_down(a0, off, 64);
-    a1 += __shfl_down(a1, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a0; red[1][threadIdx.x >> 6] = a1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    S[r] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    if (KID != GPRC_SQREXP) S[n + r] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
-
 __global__ __launch_bounds__(256) void set_identity_rows_kernel(double* vt, int64_t ld, int64_t rows, int64_t cols, int64_t row0) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // row of the chunk (contiguous direction)
   if (i >= rows) return;
@@ -387,36 +309,30 @@ __global__ __launch_bounds__(256) void set_identity_rows_kernel(double* vt, int6
 }  // namespace
 
 static int fill_dispatch(hipStream_t s, const FillArgs& a) {
-  switch (a.ks.id) {
-    case GPRC_CONSTANT: return do_fill<GPRC_CONSTANT>(s, a);
-    case GPRC_LINEAR: return do_fill<GPRC_LINEAR>(s, a);
-    case GPRC_POLYNOMIAL: return do_fill<GPRC_POLYNOMIAL>(s, a);
-    case GPRC_SQREXP: return do_fill<GPRC_SQREXP>(s, a);
-    case GPRC_GAMMAEXP: return do_fill<GPRC_GAMMAEXP>(s, a);
-    case GPRC_RATQUAD: return do_fill<GPRC_RATQUAD>(s, a);
-    case GPRC_SQREXP_ARD: return do_fill<GPRC_SQREXP_ARD>(s, a);
-    default: set_error("unknown kernel id"); return GPRC_ERR_ARG;
-  }
+  int rc = 0;
+  if (with_any_kernel(a.ks.id, [&](auto kid) { rc = do_fill<decltype(kid)::value>(s, a); })) return rc;
+  set_error("unknown kernel id");
+  return GPRC_ERR_ARG;
 }
 
 int launch_fill(hipStream_t s, const KernelSpec& ks, const double* A, int64_t nA, const double* B, int64_t nB, int64_t d,
                 double* out, int64_t ld, int64_t row0, int64_t nrows, int64_t col0, int64_t ncols, PadMode mode,
                 double noise) {
   if (nrows <= 0 || ncols <= 0) return 0;
-  if ((ncols + FT_C - 1) / FT_C > 65535) { set_error("fill: too many column tiles in one launch"); return GPRC_ERR_ARG; }
+  if ((ncols + PT_C - 1) / PT_C > 65535) { set_error("fill: too many column tiles in one launch"); return GPRC_ERR_ARG; }
   FillArgs a{A, B, out, nA, nB, d, ld, row0, nrows, col0, ncols, (int)mode, noise, make_fill_spec(ks), nullptr, nullptr, 0, nullptr};
   ProfScope ps(s, PK_FILL, (double)nrows * ncols * (3.0 * d + 20.0), 8.0 * nrows * ncols);
   return fill_dispatch(s, a);
 }
 
-int64_t fill_mean_tiles(int64_t cols) { return (cols + FT_C - 1) / FT_C; }
+int64_t fill_mean_tiles(int64_t cols) { return (cols + PT_C - 1) / PT_C; }
 
 // The predict's cross-covariance chunk with its fused epilogue: vt (m_pad x n_pad, zero padded) = K(X_star chunk, X)
 // [times colscale per column]; mpart[t * m_pad + i] = partial of (K*^T w)_i over column tile t (fill_mean_tiles(n_pad) tiles).
 int launch_fill_cross_fused(hipStream_t s, const KernelSpec& ks, const double* Xs, int64_t m, const double* X, int64_t n, int64_t d,
                             double* vt, int64_t ld, int64_t m_pad, int64_t n_pad, const double* w, double* mpart, const double* colscale) {
   if (m_pad <= 0 || n_pad <= 0) return 0;
-  if (m_pad % FT_R) { set_error("fill_cross_fused: m_pad must be a multiple of 128"); return GPRC_ERR_ARG; }
+  if (m_pad % PT_R) { set_error("fill_cross_fused: m_pad must be a multiple of 128"); return GPRC_ERR_ARG; }
   if (fill_mean_tiles(n_pad) > 65535) { set_error("fill: too many column tiles in one launch"); return GPRC_ERR_ARG; }
   if (w && !mpart) { set_error("fill_cross_fused: partial buffer missing"); return GPRC_ERR_ARG; }
   FillArgs a{Xs, X, vt, m, n, d, ld, 0, m_pad, 0, n_pad, (int)PAD_ZERO, 0.0, make_fill_spec(ks), w, mpart, m_pad, colscale};
@@ -428,30 +344,9 @@ int launch_colwise(hipStream_t s, const KernelSpec& ks, const double* x, const d
   if (m <= 0) return 0;
   dim3 grid((unsigned)((m + 255) / 256));
   const KernelSpec ksd = make_fill_spec(ks);
-  switch (ks.id) {
-    case GPRC_CONSTANT: hipLaunchKernelGGL((colwise_kernel<GPRC_CONSTANT>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    case GPRC_LINEAR: hipLaunchKernelGGL((colwise_kernel<GPRC_LINEAR>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    case GPRC_POLYNOMIAL: hipLaunchKernelGGL((colwise_kernel<GPRC_POLYNOMIAL>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    case GPRC_SQREXP: hipLaunchKernelGGL((colwise_kernel<GPRC_SQREXP>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    case GPRC_GAMMAEXP: hipLaunchKernelGGL((colwise_kernel<GPRC_GAMMAEXP>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    case GPRC_RATQUAD: hipLaunchKernelGGL((colwise_kernel<GPRC_RATQUAD>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((colwise_kernel<GPRC_SQREXP_ARD>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); break;
-    default: set_error("unknown kernel id"); return GPRC_ERR_ARG;
-  }
-  GPRC_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_deriv_rowsum(hipStream_t s, int kernel, double v0, double v1, const double* X, int64_t d, int64_t n, double* S) {
-  if (n <= 0) return 0;
-  ProfScope ps(s, PK_DERIV, (double)n * n * (3.0 * d + 40.0), 8.0 * ((double)n * d + 2.0 * n));
-  const dim3 grid((unsigned)n), block(256);
-  switch (kernel) {
-    case GPRC_SQREXP: hipLaunchKernelGGL((deriv_rowsum_kernel<GPRC_SQREXP>), grid, block, 0, s, v0, v1, X, d, n, S); break;
-    case GPRC_GAMMAEXP: hipLaunchKernelGGL((deriv_rowsum_kernel<GPRC_GAMMAEXP>), grid, block, 0, s, v0, v1, X, d, n, S); break;
-    case GPRC_POLYNOMIAL: hipLaunchKernelGGL((deriv_rowsum_kernel<GPRC_POLYNOMIAL>), grid, block, 0, s, v0, v1, X, d, n, S); break;
-    case GPRC_RATQUAD: hipLaunchKernelGGL((deriv_rowsum_kernel<GPRC_RATQUAD>), grid, block, 0, s, v0, v1, X, d, n, S); break;
-    default: set_error("fit gradient: the reference defines it for sqrexp, gammaexp, polynomial, rationalquadratic only (R/fit.R:125)"); return GPRC_ERR_ARG;
+  if (!with_any_kernel(ks.id, [&](auto kid) { hipLaunchKernelGGL((colwise_kernel<decltype(kid)::value>), grid, dim3(256), 0, s, ksd, x, y, d, m, out); })) {
+    set_error("unknown kernel id");
+    return GPRC_ERR_ARG;
   }
   GPRC_LAUNCH_CHECK();
   return 0;

@@ -25,18 +25,17 @@
 // (explicit part a a^T - R, R = sw B^-1 sw, plus the rank-two form of the implicit part through the mode).  A tile stages the four
 // vectors of its 128 rows and 64 columns in LDS (6 KiB) and reads them there inside the column loop; there is no diagonal sum.
 // It is a compile-time parameter: the regression instantiations are the code they were.
-#include "gprc_internal.h"
+//
+// The tile shape, the staging and both distance loops are pair_tile.h's.  Also here: the derivative row sums of the reference's own
+// fit() gradient (gprc_fit_gradient), the other consumer of dK / dtheta.
+#include "pair_tile.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace gprc {
 
 namespace {
 
-constexpr int GT_R = 128;      // tile rows: 2 consecutive rows per lane x 64 lanes
-constexpr int GT_C = 64;       // tile cols: 16 per wave x 4 waves
-constexpr int GD = 16;         // coordinates staged per pass
 constexpr int GRAD_WGS = 1024; // workgroups of the launch = rows of the partial buffer (a constant: the order of summation does not depend on the device)
 
 struct GradArgs {
@@ -46,7 +45,7 @@ struct GradArgs {
   double* part;
   int64_t n, d, ld;
   int64_t ntiles;
-  KernelSpec ks;   // derived constants, see make_grad_spec
+  KernelSpec ks;   // derived constants, see make_deriv_spec
 };
 struct LaplaceArgs : GradArgs {   // alpha: the mode search's a = K^-1 f
   const double* sw;
@@ -54,21 +53,15 @@ struct LaplaceArgs : GradArgs {   // alpha: the mode search's a = K^-1 f
   const double* g;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // lane 0 holds the sum
-}
-
 template <int KID, bool LAPLACE>
 __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<LAPLACE, LaplaceArgs, GradArgs> a) {
-  __shared__ __attribute__((aligned(16))) double As[GD][GT_R];
-  __shared__ double Bs[GT_C][GD + 1];
-  __shared__ double Al[GT_C];
-  __shared__ double red[4][GD + 1];
+  __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];
+  __shared__ double Bs[PT_C][PT_D + 1];
+  __shared__ double Al[PT_C];
+  __shared__ double red[4][PT_D + 1];
   __shared__ double gacc[MAX_PARAMS + 1];
-  __shared__ __attribute__((aligned(16))) double Rv[LAPLACE ? 4 : 1][GT_R];   // Laplace: a, sw, u, g of the tile's rows ...
-  __shared__ double Cv[LAPLACE ? 4 : 1][GT_C];                                 // ... and of its columns
+  __shared__ __attribute__((aligned(16))) double Rv[LAPLACE ? 4 : 1][PT_R];   // Laplace: a, sw, u, g of the tile's rows ...
+  __shared__ double Cv[LAPLACE ? 4 : 1][PT_C];                                 // ... and of its columns
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int np = KID == GPRC_SQREXP_ARD ? (int)a.d : (KID == GPRC_SQREXP ? 1 : 2);
   constexpr int NZ = LAPLACE ? 0 : 1;   // regression leaves one more sum per workgroup, the diagonal's
@@ -81,24 +74,12 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
     while ((bi + 1) * (bi + 2) <= tile) ++bi;
     while (bi * (bi + 1) > tile) --bi;
     const int64_t bj = tile - bi * (bi + 1);
-    const int64_t ti = bi * GT_R, tj = bj * GT_C;
+    const int64_t ti = bi * PT_R, tj = bj * PT_C;
 
     auto stage = [&](int64_t r0, int dc) {  // coordinates r0 .. r0 + dc - 1 of the tile's points (ARD: divided by their length scale)
       __syncthreads();
-      for (int e = t; e < GT_R * dc; e += 256) {
-        const int i = e / dc, r = e - i * dc;
-        const int64_t gi = ti + i;
-        double v = (gi < a.n) ? a.X[gi * a.d + r0 + r] : 0.0;
-        if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
-        As[r][i] = v;
-      }
-      for (int e = t; e < GT_C * dc; e += 256) {
-        const int j = e / dc, r = e - j * dc;
-        const int64_t gj = tj + j;
-        double v = (gj < a.n) ? a.X[gj * a.d + r0 + r] : 0.0;
-        if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
-        Bs[j][r] = v;
-      }
+      stage_points<KID == GPRC_SQREXP_ARD>(a.X, ti, a.n, a.d, r0, dc, PT_R, a.ks.p, t, [&](int i, int r, double v) { As[r][i] = v; });
+      stage_points<KID == GPRC_SQREXP_ARD>(a.X, tj, a.n, a.d, r0, dc, PT_C, a.ks.p, t, [&](int j, int r, double v) { Bs[j][r] = v; });
       if constexpr (LAPLACE) {
         if (r0 == 0) {
           const int v = t >> 6, j = t & 63;   // 4 vectors x 64 columns; 4 x 128 rows, two per thread
@@ -108,7 +89,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
           Rv[v][j + 64] = (ti + j + 64 < a.n) ? src[ti + j + 64] : 0.0;
         }
       } else {
-        if (r0 == 0 && t < GT_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
+        if (r0 == 0 && t < PT_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
       }
       __syncthreads();
     };
@@ -116,19 +97,10 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
     double s0[16], s1[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) { s0[c] = 0.0; s1[c] = 0.0; }
-    for (int64_t r0 = 0; r0 < a.d; r0 += GD) {
-      const int dc = (int)((a.d - r0 < GD) ? (a.d - r0) : GD);
+    for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {
+      const int dc = (int)((a.d - r0 < PT_D) ? (a.d - r0) : PT_D);
       stage(r0, dc);
-      for (int r = 0; r < dc; ++r) {
-        const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          const double b = Bs[wave * 16 + c][r];
-          const double t0 = av.x - b, t1 = av.y - b;
-          s0[c] = fma(t0, t0, s0[c]);
-          s1[c] = fma(t1, t1, s1[c]);
-        }
-      }
+      accum_sqdist(As, Bs, dc, lane, wave, s0, s1);
     }
 
     const int64_t gi0 = ti + 2 * lane;
@@ -190,25 +162,16 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
     }
 
     if constexpr (KID == GPRC_SQREXP_ARD) {
-      for (int64_t r0 = 0; r0 < a.d; r0 += GD) {
-        const int dc = (int)((a.d - r0 < GD) ? (a.d - r0) : GD);
-        if (a.d > GD) stage(r0, dc);  // (d <= 16: the only chunk is still in LDS)
+      for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {
+        const int dc = (int)((a.d - r0 < PT_D) ? (a.d - r0) : PT_D);
+        if (a.d > PT_D) stage(r0, dc);  // (d <= 16: the only chunk is still in LDS)
         for (int r = 0; r < dc; ++r) {
-          const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
-          double acc = 0.0;
-#pragma unroll
-          for (int c = 0; c < 16; ++c) {
-            const double b = Bs[wave * 16 + c][r];
-            const double t0 = av.x - b, t1 = av.y - b;
-            acc = fma(s0[c], t0 * t0, acc);
-            acc = fma(s1[c], t1 * t1, acc);
-          }
-          acc = wave_sum(acc);
+          const double acc = wave_sum(weighted_sqdiff(As, Bs, r, lane, wave, s0, s1));
           if (lane == 0) red[wave][r] = acc;
         }
         __syncthreads();
-        if (t < dc) gacc[r0 + t] += (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-        if (a.d <= GD) __syncthreads();  // (otherwise the next stage() separates these reads from the next chunk's writes)
+        if (t < dc) gacc[r0 + t] += sum4_pairs(red[0][t], red[1][t], red[2][t], red[3][t]);
+        if (a.d <= PT_D) __syncthreads();  // (otherwise the next stage() separates these reads from the next chunk's writes)
       }
     }
   }
@@ -221,24 +184,93 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
   __syncthreads();
   if (t == 0) {
     if constexpr (KID != GPRC_SQREXP_ARD) {
-      gacc[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-      if (np == 2) gacc[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+      gacc[0] = sum4_pairs(red[0][0], red[1][0], red[2][0], red[3][0]);
+      if (np == 2) gacc[1] = sum4_pairs(red[0][1], red[1][1], red[2][1], red[3][1]);
     }
-    if constexpr (!LAPLACE) gacc[np] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+    if constexpr (!LAPLACE) gacc[np] = sum4_pairs(red[0][2], red[1][2], red[2][2], red[3][2]);
   }
   __syncthreads();
   for (int k = t; k < np + NZ; k += 256) a.part[(int64_t)blockIdx.x * (np + NZ) + k] = gacc[k];
 }
 
-// the spec with the constants the kernel wants (ARD: p[k] = 1 / l_k)
-KernelSpec make_grad_spec(const KernelSpec& ks) {
-  KernelSpec g = ks;
-  if (ks.id == GPRC_SQREXP) g.p[1] = 1.0 / (2.0 * (ks.p[0] * ks.p[0]));
-  if (ks.id == GPRC_GAMMAEXP) { g.p[2] = 1.0 / (ks.p[0] * ks.p[0]); g.p[3] = 0.5 * ks.p[1]; }
-  if (ks.id == GPRC_RATQUAD) g.p[2] = 1.0 / (2.0 * ks.p[1] * (ks.p[0] * ks.p[0]));
-  if (ks.id == GPRC_SQREXP_ARD)
-    for (int k = 0; k < ks.n_params; ++k) g.p[k] = 1.0 / ks.p[k];
-  return g;
+// One launcher behind both public ones: they differ in the argument struct, the width of a partial row (regression: one more sum, the
+// diagonal's), the profile kind and its flop / byte constants.  a: everything but ntiles and ks.
+template <bool LAPLACE>
+int launch_contract(hipStream_t s, const KernelSpec& ks, std::conditional_t<LAPLACE, LaplaceArgs, GradArgs> a) {
+  const std::string who = LAPLACE ? "gpc_grad_contract" : "grad_contract";
+  if (a.n <= 0) return 0;
+  if ((a.ld & 1) || (reinterpret_cast<uintptr_t>(a.W) & 15)) { set_error(who + ": the inverse must be 16-byte aligned with an even leading dimension"); return GPRC_ERR_ARG; }
+  const int64_t R = (a.n + PT_R - 1) / PT_R;
+  if (a.ld < R * PT_R) { set_error(who + ": leading dimension smaller than the padded size"); return GPRC_ERR_ARG; }
+  GPRC_TRY(check_grad_kernel(LAPLACE ? "logq_grad" : "logp_grad", ks.id));
+  a.ntiles = R * (R + 1);
+  a.ks = make_deriv_spec(ks);
+  GPRC_HIP(hipMemsetAsync(a.part, 0, sizeof(double) * (size_t)(GRAD_WGS * (ks.n_params + (LAPLACE ? 0 : 1))), s));   // rows of workgroups that are not launched
+  const dim3 grid((unsigned)std::min<int64_t>(a.ntiles, GRAD_WGS)), block(256);
+  // bytes: the stored triangle once + X and alpha (Laplace: four vectors); flops: the distance (3 d), the kernel and its derivatives
+  // (~60; Laplace: the 9 of M more), ARD's second pass (4 d)
+  const double elems = 0.5 * (double)a.n * (double)(a.n + 1), n = (double)a.n, d = (double)a.d;
+  ProfScope ps(s, LAPLACE ? PK_GPC_GRAD_CONTRACT : PK_GRAD_CONTRACT, elems * (3.0 * d + (LAPLACE ? 69.0 : 60.0) + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)),
+               8.0 * (elems + n * d + (LAPLACE ? 4.0 * n : n)));
+  with_gradient_kernel(ks.id, [&](auto kid) { hipLaunchKernelGGL((grad_contract_kernel<decltype(kid)::value, LAPLACE>), grid, block, 0, s, a); });
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- derivative row sums for fit()'s gradient (R/fit.R:126-139) ---------------------------------------------------
+// deriv(x, y, v...) of cov_dict (R/fit.R:4-31), with v bound POSITIONALLY as the reference's do.call does:
+//   sqrexp (l)            r = |x-y| :  r^2/l^3 * exp(-r^2/(2 l^2))
+//   gammaexp (gamma, l)   r = |x-y| :  ( -exp(-(r/l)^gamma) (r/l)^gamma log(r/l) ,  exp(-(r/l)^gamma) gamma r^gamma / l^(gamma+1) )
+//   polynomial (sigma, p) s = x.y + sigma :  ( p s^(p-1) ,  s^p log(s) )
+//   rationalquadratic (alpha, l)  r = |x-y|^2, q = r/(2 l^2 alpha) + 1 :
+//                         ( q^-alpha (r - (2 l^2 alpha + r) log q) / (2 l^2 alpha + r) ,  r q^(-alpha-1) / l^3 )
+// (gammaexp's first component is 0 * -Inf = NaN at r = 0, i.e. on the diagonal: kept, it decides what optim does.)
+template <int KID>
+__device__ __forceinline__ void deriv_pair(double s, double v0, double v1, double& g0, double& g1) {
+  if constexpr (KID == GPRC_SQREXP) {
+    g0 = s / (v0 * v0 * v0) * exp(-s / ((v0 * v0) * 2.0));
+    g1 = 0.0;
+  } else if constexpr (KID == GPRC_GAMMAEXP) {
+    const double r = sqrt(s), rl = r / v1, e = exp(-r_pow(rl, v0));
+    g0 = -e * r_pow(rl, v0) * log(rl);
+    g1 = e * v0 * r_pow(r, v0) / r_pow(v1, v0 + 1.0);
+  } else if constexpr (KID == GPRC_POLYNOMIAL) {
+    const double t = s + v0;
+    g0 = v1 * r_pow(t, v1 - 1.0);
+    g1 = r_pow(t, v1) * log(t);
+  } else {  // rationalquadratic
+    const double c = 2.0 * (v1 * v1) * v0, q = s / c + 1.0;
+    g0 = (r_pow(q, -v0) * (s - (c + s) * log(q))) / (c + s);
+    g1 = (s * r_pow(q, -v0 - 1.0)) / (v1 * v1 * v1);
+  }
+}
+
+template <int KID>
+__global__ __launch_bounds__(256) void deriv_rowsum_kernel(double v0, double v1, const double* X, int64_t d, int64_t n, double* S) {
+  const int64_t r = blockIdx.x;
+  const double* xr = X + r * d;
+  double a0 = 0.0, a1 = 0.0;
+  for (int64_t c = threadIdx.x; c < n; c += 256) {
+    const double* xc = X + c * d;
+    double s = 0.0;
+    for (int64_t k = 0; k < d; ++k) {
+      if constexpr (KID == GPRC_POLYNOMIAL) s += xr[k] * xc[k];
+      else { const double t = xr[k] - xc[k]; s += t * t; }
+    }
+    double g0, g1;
+    deriv_pair<KID>(s, v0, v1, g0, g1);
+    a0 += g0;
+    a1 += g1;
+  }
+  __shared__ double red[2][4];
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a0; red[1][threadIdx.x >> 6] = a1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    S[r] = sum4_pairs(red[0][0], red[0][1], red[0][2], red[0][3]);
+    if (KID != GPRC_SQREXP) S[n + r] = sum4_pairs(red[1][0], red[1][1], red[1][2], red[1][3]);
+  }
 }
 
 }  // namespace
@@ -247,47 +279,22 @@ int64_t grad_partial_rows() { return GRAD_WGS; }
 
 int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* alpha, const double* W,
                          int64_t ld, double* part) {
-  if (n <= 0) return 0;
-  if ((ld & 1) || (reinterpret_cast<uintptr_t>(W) & 15)) { set_error("grad_contract: the inverse must be 16-byte aligned with an even leading dimension"); return GPRC_ERR_ARG; }
-  const int64_t R = (n + GT_R - 1) / GT_R;
-  if (ld < R * GT_R) { set_error("grad_contract: leading dimension smaller than the padded size"); return GPRC_ERR_ARG; }
-  const int np = ks.n_params;
-  GradArgs a{X, alpha, W, part, n, d, ld, R * (R + 1), make_grad_spec(ks)};
-  GPRC_HIP(hipMemsetAsync(part, 0, sizeof(double) * (size_t)(GRAD_WGS * (np + 1)), s));   // rows of workgroups that are not launched
-  const dim3 grid((unsigned)std::min<int64_t>(a.ntiles, GRAD_WGS)), block(256);
-  // bytes: the stored triangle once + X and alpha; flops: the distance (3 d), the kernel and its derivatives (~60), ARD's second pass (4 d)
-  const double elems = 0.5 * (double)n * (double)(n + 1);
-  ProfScope ps(s, PK_GRAD_CONTRACT, elems * (3.0 * d + 60.0 + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)), 8.0 * (elems + (double)n * d + n));
-  switch (ks.id) {
-    case GPRC_SQREXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP, false>), grid, block, 0, s, a); break;
-    case GPRC_GAMMAEXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_GAMMAEXP, false>), grid, block, 0, s, a); break;
-    case GPRC_RATQUAD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_RATQUAD, false>), grid, block, 0, s, a); break;
-    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP_ARD, false>), grid, block, 0, s, a); break;
-    default: set_error("logp_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
-  }
-  GPRC_LAUNCH_CHECK();
-  return 0;
+  return launch_contract<false>(s, ks, GradArgs{X, alpha, W, part, n, d, ld, 0, {}});
 }
 
 int launch_gpc_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* a_vec, const double* sw,
                              const double* u, const double* g, const double* W, int64_t ld, double* part) {
+  return launch_contract<true>(s, ks, LaplaceArgs{{X, a_vec, W, part, n, d, ld, 0, {}}, sw, u, g});
+}
+
+int launch_deriv_rowsum(hipStream_t s, int kernel, double v0, double v1, const double* X, int64_t d, int64_t n, double* S) {
   if (n <= 0) return 0;
-  if ((ld & 1) || (reinterpret_cast<uintptr_t>(W) & 15)) { set_error("gpc_grad_contract: the inverse must be 16-byte aligned with an even leading dimension"); return GPRC_ERR_ARG; }
-  const int64_t R = (n + GT_R - 1) / GT_R;
-  if (ld < R * GT_R) { set_error("gpc_grad_contract: leading dimension smaller than the padded size"); return GPRC_ERR_ARG; }
-  const int np = ks.n_params;
-  LaplaceArgs a{{X, a_vec, W, part, n, d, ld, R * (R + 1), make_grad_spec(ks)}, sw, u, g};
-  GPRC_HIP(hipMemsetAsync(part, 0, sizeof(double) * (size_t)(GRAD_WGS * np), s));   // rows of workgroups that are not launched
-  const dim3 grid((unsigned)std::min<int64_t>(a.ntiles, GRAD_WGS)), block(256);
-  // as launch_grad_contract, plus the four vectors and the 9 flops of M
-  const double elems = 0.5 * (double)n * (double)(n + 1);
-  ProfScope ps(s, PK_GPC_GRAD_CONTRACT, elems * (3.0 * d + 69.0 + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)), 8.0 * (elems + (double)n * d + 4.0 * n));
-  switch (ks.id) {
-    case GPRC_SQREXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP, true>), grid, block, 0, s, a); break;
-    case GPRC_GAMMAEXP: hipLaunchKernelGGL((grad_contract_kernel<GPRC_GAMMAEXP, true>), grid, block, 0, s, a); break;
-    case GPRC_RATQUAD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_RATQUAD, true>), grid, block, 0, s, a); break;
-    case GPRC_SQREXP_ARD: hipLaunchKernelGGL((grad_contract_kernel<GPRC_SQREXP_ARD, true>), grid, block, 0, s, a); break;
-    default: set_error("logq_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
+  ProfScope ps(s, PK_DERIV, (double)n * n * (3.0 * d + 40.0), 8.0 * ((double)n * d + 2.0 * n));
+  if (!with_kernel_id<GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_POLYNOMIAL, GPRC_RATQUAD>(kernel, [&](auto kid) {
+        hipLaunchKernelGGL((deriv_rowsum_kernel<decltype(kid)::value>), dim3((unsigned)n), dim3(256), 0, s, v0, v1, X, d, n, S);
+      })) {
+    set_error("fit gradient: the reference defines it for sqrexp, gammaexp, polynomial, rationalquadratic only (R/fit.R:125)");
+    return GPRC_ERR_ARG;
   }
   GPRC_LAUNCH_CHECK();
   return 0;

@@ -23,7 +23,9 @@
 // Order of summation is fixed: a lane's columns ascending, tile after tile of the stripe, the four waves in wave order; one partial
 // per (stripe, coordinate, row); the stripes are added in order by pred_grad_sum_kernel.  No atomics.  The stripe is a function of
 // n_pad alone, so a row's result does not depend on how the test points are chunked, bit for bit.
-#include "gprc_internal.h"
+//
+// The tile shape, the staging and the distance loop are pair_tile.h's.
+#include "pair_tile.h"
 
 #include <algorithm>
 
@@ -31,9 +33,6 @@ namespace gprc {
 
 namespace {
 
-constexpr int PG_R = 128;   // tile rows: 2 consecutive rows per lane x 64 lanes
-constexpr int PG_C = 64;    // tile cols: 16 per wave x 4 waves
-constexpr int PG_D = 16;    // coordinates staged per pass of the distance
 constexpr int PG_Z = 8;     // coordinates whose sums one workgroup forms
 constexpr int PG_MAX_STRIPES = 32;
 
@@ -46,7 +45,7 @@ struct PgradArgs {
   double* pvar;          // stripes x d x m_pad (WITH_VAR only)
   int64_t m, n, d, ldw, m_pad, n_pad;
   int64_t stripe_tiles, ntiles;
-  KernelSpec ks;         // derived constants, see make_pgrad_spec
+  KernelSpec ks;         // derived constants, see make_deriv_spec
 };
 
 // h without the factor the tail applies
@@ -66,19 +65,20 @@ __device__ __forceinline__ double pair_weight(double s, const KernelSpec& ks) {
 
 template <int KID, bool WITH_VAR>
 __global__ __launch_bounds__(256) void pred_grad_kernel(PgradArgs a) {
-  __shared__ __attribute__((aligned(16))) double As[PG_D][PG_R];
-  __shared__ double Bs[PG_C][PG_D + 1];
-  __shared__ double Bz[PG_C][PG_Z + 1];   // the workgroup's own coordinates of the tile's training points
-  __shared__ double Al[PG_C];
-  __shared__ __attribute__((aligned(16))) double Red[4][PG_Z][PG_R];
+  __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];
+  __shared__ double Bs[PT_C][PT_D + 1];
+  __shared__ double Bz[PT_C][PG_Z + 1];   // the workgroup's own coordinates of the tile's training points
+  __shared__ double Al[PT_C];
+  __shared__ __attribute__((aligned(16))) double Red[4][PG_Z][PT_R];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t ti = (int64_t)blockIdx.x * PG_R;
+  const int64_t ti = (int64_t)blockIdx.x * PT_R;
   const int64_t stripe = blockIdx.y;
   const int64_t z0 = (int64_t)blockIdx.z * PG_Z;
   const int dz = (int)((a.d - z0 < PG_Z) ? (a.d - z0) : PG_Z);
   const int64_t tile0 = stripe * a.stripe_tiles;
   const int64_t tile1 = (tile0 + a.stripe_tiles < a.ntiles) ? tile0 + a.stripe_tiles : a.ntiles;
   const int64_t gi0 = ti + 2 * lane;
+  constexpr bool ARD = KID == GPRC_SQREXP_ARD;   // coordinates staged divided by their length scale
 
   double xs0[PG_Z], xs1[PG_Z], gm0[PG_Z], gm1[PG_Z], gv0[PG_Z], gv1[PG_Z];
 #pragma unroll
@@ -90,50 +90,23 @@ __global__ __launch_bounds__(256) void pred_grad_kernel(PgradArgs a) {
   }
 
   for (int64_t tile = tile0; tile < tile1; ++tile) {
-    const int64_t tj = tile * PG_C;
+    const int64_t tj = tile * PT_C;
     double s0[16], s1[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) { s0[c] = 0.0; s1[c] = 0.0; }
-    for (int64_t r0 = 0; r0 < a.d; r0 += PG_D) {
-      const int dc = (int)((a.d - r0 < PG_D) ? (a.d - r0) : PG_D);
+    for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {
+      const int dc = (int)((a.d - r0 < PT_D) ? (a.d - r0) : PT_D);
       __syncthreads();
-      if (a.d > PG_D || tile == tile0) {   // (d <= 16: the test points' only chunk stays in LDS for the whole stripe)
-        for (int e = t; e < PG_R * dc; e += 256) {
-          const int i = e / dc, r = e - i * dc;
-          const int64_t gi = ti + i;
-          double v = (gi < a.m) ? a.Xs[gi * a.d + r0 + r] : 0.0;
-          if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
-          As[r][i] = v;
-        }
+      if (a.d > PT_D || tile == tile0) {   // (d <= 16: the test points' only chunk stays in LDS for the whole stripe)
+        stage_points<ARD>(a.Xs, ti, a.m, a.d, r0, dc, PT_R, a.ks.p, t, [&](int i, int r, double v) { As[r][i] = v; });
       }
-      for (int e = t; e < PG_C * dc; e += 256) {
-        const int j = e / dc, r = e - j * dc;
-        const int64_t gj = tj + j;
-        double v = (gj < a.n) ? a.X[gj * a.d + r0 + r] : 0.0;
-        if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[r0 + r];
-        Bs[j][r] = v;
-      }
+      stage_points<ARD>(a.X, tj, a.n, a.d, r0, dc, PT_C, a.ks.p, t, [&](int j, int r, double v) { Bs[j][r] = v; });
       if (r0 == 0) {
-        if (t < PG_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
-        for (int e = t; e < PG_C * dz; e += 256) {
-          const int j = e / dz, r = e - j * dz;
-          const int64_t gj = tj + j;
-          double v = (gj < a.n) ? a.X[gj * a.d + z0 + r] : 0.0;
-          if constexpr (KID == GPRC_SQREXP_ARD) v *= a.ks.p[z0 + r];
-          Bz[j][r] = v;
-        }
+        if (t < PT_C) Al[t] = (tj + t < a.n) ? a.alpha[tj + t] : 0.0;
+        stage_points<ARD>(a.X, tj, a.n, a.d, z0, dz, PT_C, a.ks.p, t, [&](int j, int r, double v) { Bz[j][r] = v; });
       }
       __syncthreads();
-      for (int r = 0; r < dc; ++r) {
-        const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          const double b = Bs[wave * 16 + c][r];
-          const double t0 = av.x - b, t1 = av.y - b;
-          s0[c] = fma(t0, t0, s0[c]);
-          s1[c] = fma(t1, t1, s1[c]);
-        }
-      }
+      accum_sqdist(As, Bs, dc, lane, wave, s0, s1);
     }
 
     // rows gi0, gi0 + 1 < m_pad and columns n_pad - 1 - (tj + 63) .. n_pad - 1 - tj inside [0, n_pad): every load is inside the chunk
@@ -167,26 +140,18 @@ __global__ __launch_bounds__(256) void pred_grad_kernel(PgradArgs a) {
   }
 
   // the four waves' sums in wave order, one partial per (stripe, coordinate, row)
-  if (a.pmean) {
+  auto write_partials = [&](const double (&g0)[PG_Z], const double (&g1)[PG_Z], double* out) {
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < PG_Z; ++r) *reinterpret_cast<double2*>(&Red[wave][r][2 * lane]) = make_double2(gm0[r], gm1[r]);
+    for (int r = 0; r < PG_Z; ++r) *reinterpret_cast<double2*>(&Red[wave][r][2 * lane]) = make_double2(g0[r], g1[r]);
     __syncthreads();
-    for (int e = t; e < dz * PG_R; e += 256) {
-      const int r = e / PG_R, i = e - r * PG_R;
-      a.pmean[(stripe * a.d + z0 + r) * a.m_pad + ti + i] = ((Red[0][r][i] + Red[1][r][i]) + Red[2][r][i]) + Red[3][r][i];
+    for (int e = t; e < dz * PT_R; e += 256) {
+      const int r = e / PT_R, i = e - r * PT_R;
+      out[(stripe * a.d + z0 + r) * a.m_pad + ti + i] = sum4_in_order(Red[0][r][i], Red[1][r][i], Red[2][r][i], Red[3][r][i]);
     }
-  }
-  if constexpr (WITH_VAR) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < PG_Z; ++r) *reinterpret_cast<double2*>(&Red[wave][r][2 * lane]) = make_double2(gv0[r], gv1[r]);
-    __syncthreads();
-    for (int e = t; e < dz * PG_R; e += 256) {
-      const int r = e / PG_R, i = e - r * PG_R;
-      a.pvar[(stripe * a.d + z0 + r) * a.m_pad + ti + i] = ((Red[0][r][i] + Red[1][r][i]) + Red[2][r][i]) + Red[3][r][i];
-    }
-  }
+  };
+  if (a.pmean) write_partials(gm0, gm1, a.pmean);
+  if constexpr (WITH_VAR) write_partials(gv0, gv1, a.pvar);
 }
 
 // out[c + d i] = f_c * sum over the stripes, in order, of part[(st d + c) m_pad + i];  f_c = sign * (ard ? ks.p[c] : iso)
@@ -200,56 +165,37 @@ __global__ __launch_bounds__(256) void pred_grad_sum_kernel(const double* part, 
   out[c + d * i] = (sign * (ard ? ks.p[c] : iso)) * s;
 }
 
-// the spec with the constants the kernel wants (ARD: p[k] = 1 / l_k)
-KernelSpec make_pgrad_spec(const KernelSpec& ks) {
-  KernelSpec g = ks;
-  if (ks.id == GPRC_SQREXP) g.p[1] = 1.0 / (2.0 * (ks.p[0] * ks.p[0]));
-  if (ks.id == GPRC_GAMMAEXP) { g.p[2] = 1.0 / (ks.p[0] * ks.p[0]); g.p[3] = 0.5 * ks.p[1]; }
-  if (ks.id == GPRC_RATQUAD) g.p[2] = 1.0 / (2.0 * ks.p[1] * (ks.p[0] * ks.p[0]));
-  if (ks.id == GPRC_SQREXP_ARD)
-    for (int k = 0; k < ks.n_params; ++k) g.p[k] = 1.0 / ks.p[k];
-  return g;
-}
-
 // column tiles per stripe: at most PG_MAX_STRIPES stripes (n_pad = 65536: 2048 columns each)
-int64_t stripe_tiles_of(int64_t n_pad) { return (n_pad / PG_C + PG_MAX_STRIPES - 1) / PG_MAX_STRIPES; }
-
-template <int KID>
-void launch_kid(hipStream_t s, const dim3& grid, const PgradArgs& a) {
-  if (a.pvar) hipLaunchKernelGGL((pred_grad_kernel<KID, true>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((pred_grad_kernel<KID, false>), grid, dim3(256), 0, s, a);
-}
+int64_t stripe_tiles_of(int64_t n_pad) { return (n_pad / PT_C + PG_MAX_STRIPES - 1) / PG_MAX_STRIPES; }
 
 }  // namespace
 
 int64_t pred_grad_stripes(int64_t n_pad) {
   const int64_t st = stripe_tiles_of(n_pad);
-  return (n_pad / PG_C + st - 1) / st;
+  return (n_pad / PT_C + st - 1) / st;
 }
 
 int launch_pred_grad(hipStream_t s, const KernelSpec& ks, const double* Xs, int64_t m, int64_t m_pad, const double* X, int64_t n, int64_t n_pad,
                      int64_t d, const double* alpha, const double* W, int64_t ldw, double* pmean, double* pvar) {
   if (m <= 0) return 0;
+  GPRC_TRY(check_grad_kernel("predict_grad", ks.id));
   if (!pmean && !pvar) { set_error("pred_grad: no output"); return GPRC_ERR_ARG; }
-  if (m_pad % PG_R || m_pad < m || n_pad % PG_C || n_pad < n || d < 1) { set_error("pred_grad: bad padding"); return GPRC_ERR_ARG; }
+  if (m_pad % PT_R || m_pad < m || n_pad % PT_C || n_pad < n || d < 1) { set_error("pred_grad: bad padding"); return GPRC_ERR_ARG; }
   if (pvar && (!W || ldw < m_pad || (ldw & 1) || (reinterpret_cast<uintptr_t>(W) & 15))) {
     set_error("pred_grad: the solved chunk must be 16-byte aligned with an even leading dimension >= m_pad");
     return GPRC_ERR_ARG;
   }
   const int64_t zgroups = (d + PG_Z - 1) / PG_Z;
   if (zgroups > 65535) { set_error("pred_grad: too many coordinates"); return GPRC_ERR_ARG; }
-  PgradArgs a{Xs, X, alpha, W, pmean, pvar, m, n, d, ldw, m_pad, n_pad, stripe_tiles_of(n_pad), n_pad / PG_C, make_pgrad_spec(ks)};
-  const dim3 grid((unsigned)(m_pad / PG_R), (unsigned)pred_grad_stripes(n_pad), (unsigned)zgroups);
+  PgradArgs a{Xs, X, alpha, W, pmean, pvar, m, n, d, ldw, m_pad, n_pad, stripe_tiles_of(n_pad), n_pad / PT_C, make_deriv_spec(ks)};
+  const dim3 grid((unsigned)(m_pad / PT_R), (unsigned)pred_grad_stripes(n_pad), (unsigned)zgroups);
   // per element and coordinate group: the distance (3 d), h (~40), the sums (3 or 5 per coordinate); bytes: the solved chunk once
   const double elems = (double)m_pad * (double)n_pad * (double)zgroups;
   ProfScope ps(s, PK_PRED_GRAD, elems * (3.0 * d + 40.0 + (pvar ? 5.0 : 3.0) * PG_Z), 8.0 * ((pvar ? (double)m_pad * n_pad : 0.0) + (double)(m + n) * d + n));
-  switch (ks.id) {
-    case GPRC_SQREXP: launch_kid<GPRC_SQREXP>(s, grid, a); break;
-    case GPRC_GAMMAEXP: launch_kid<GPRC_GAMMAEXP>(s, grid, a); break;
-    case GPRC_RATQUAD: launch_kid<GPRC_RATQUAD>(s, grid, a); break;
-    case GPRC_SQREXP_ARD: launch_kid<GPRC_SQREXP_ARD>(s, grid, a); break;
-    default: set_error("predict_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
-  }
+  with_gradient_kernel(ks.id, [&](auto kid) {
+    if (a.pvar) hipLaunchKernelGGL((pred_grad_kernel<decltype(kid)::value, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((pred_grad_kernel<decltype(kid)::value, false>), grid, dim3(256), 0, s, a);
+  });
   GPRC_LAUNCH_CHECK();
   return 0;
 }
@@ -257,16 +203,12 @@ int launch_pred_grad(hipStream_t s, const KernelSpec& ks, const double* Xs, int6
 int launch_pred_grad_sum(hipStream_t s, const KernelSpec& ks, const double* part, int64_t n_pad, int64_t d, int64_t m_pad, int64_t m, bool variance,
                          double* out) {
   if (m <= 0) return 0;
-  double iso = 1.0;
-  switch (ks.id) {
-    case GPRC_SQREXP: case GPRC_RATQUAD: iso = 1.0 / (ks.p[0] * ks.p[0]); break;
-    case GPRC_GAMMAEXP: iso = ks.p[1]; break;
-    case GPRC_SQREXP_ARD: break;
-    default: set_error("predict_grad: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard"); return GPRC_ERR_ARG;
-  }
+  GPRC_TRY(check_grad_kernel("predict_grad", ks.id));
+  // the factor the tail applies (ARD: 1 / l_c per coordinate, from the spec)
+  const double iso = ks.id == GPRC_GAMMAEXP ? ks.p[1] : (ks.id == GPRC_SQREXP_ARD ? 1.0 : 1.0 / (ks.p[0] * ks.p[0]));
   // dk / dx* = -h (x* - x) t: the mean's gradient carries -1, the variance's -2 * -1
   hipLaunchKernelGGL(pred_grad_sum_kernel, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, s, part, pred_grad_stripes(n_pad), d, m_pad, m,
-                     variance ? 2.0 : -1.0, iso, ks.id == GPRC_SQREXP_ARD ? 1 : 0, make_pgrad_spec(ks), out);
+                     variance ? 2.0 : -1.0, iso, ks.id == GPRC_SQREXP_ARD ? 1 : 0, make_deriv_spec(ks), out);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

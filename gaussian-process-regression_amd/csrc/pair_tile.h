@@ -1,0 +1,134 @@
+// pair_tile.h -- the pairwise-tile core of the covariance side for gfx950 (MI355X), shared by kernels_fill.hip (the fills),
+// kernels_grad.hip (the contractions of both exact evidence gradients) and kernels_pgrad.hip (the prediction gradients' contraction).
+//
+// One tile of point pairs: PT_R x PT_C = 128 x 64 per 256-thread workgroup, two consecutive rows x 16 columns per lane.  Both point
+// sets go through LDS PT_D = 16 coordinates at a time (As[r][i] coordinate-major for the 16-byte row reads, Bs[j][r] padded by one for
+// the column broadcasts); the squared distance of a lane's 32 pairs accumulates in s0[16] / s1[16]; a per-kernel epilogue follows.
+// What is here: the tile shape, the staging loop, the distance loop of the contraction kernels, the wave and four-wave sums, R's `^`,
+// and for the host the derived constants of the contraction kernels, the set of kernels with an exact gradient and the dispatcher
+// from a run-time kernel id to a template instantiation.
+//
+// What is deliberately NOT shared:
+//   * the fill's accum<KID> (kernels_fill.hip).  Its ARD term is (a - b) * sig, the contraction kernels stage a * sig and b * sig and
+//     subtract: the two round differently, the fill is tied to the oracle at 1e-13 and the gradients to their own references, and
+//     both stay as they are.
+//   * the kernel value and its intermediates per kernel (u, log for gammaexp; x, q, log1p for ratquad).  kernels_grad.hip forms
+//     (m * exp(-u)) * u and m * exp(-alpha log1p x), kernels_pgrad.hip exp(-u) * u / s and exp(-alpha log1p x) / (1 + x), the fill
+//     its measured fast paths (finish<KID>): a shared function would fix one order of multiplications for all three.
+#pragma once
+#include <string>
+#include <type_traits>
+#include <utility>
+
+#include "gprc_internal.h"
+
+namespace gprc {
+
+constexpr int PT_R = 128;  // tile rows: 2 consecutive rows per lane x 64 lanes
+constexpr int PT_C = 64;   // tile cols: 16 per wave x 4 waves
+constexpr int PT_D = 16;   // coordinates staged per pass
+
+// ---- host: kernel ids -> instantiations ----------------------------------------------------------------------------------------
+// f(std::integral_constant<int, ID>{}) for the ID among Ids that equals id; false when none does
+template <int... Ids, class F>
+inline bool with_kernel_id(int id, F&& f) {
+  return ((id == Ids ? (f(std::integral_constant<int, Ids>{}), true) : false) || ...);
+}
+template <class F>
+inline bool with_any_kernel(int id, F&& f) {
+  return with_kernel_id<GPRC_CONSTANT, GPRC_LINEAR, GPRC_POLYNOMIAL, GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD>(id, std::forward<F>(f));
+}
+// the kernels whose dK / dtheta and dk / dx* the contraction kernels know: THE statement of that set
+template <class F>
+inline bool with_gradient_kernel(int id, F&& f) {
+  return with_kernel_id<GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD>(id, std::forward<F>(f));
+}
+inline bool has_exact_gradient(int kernel_id) { return with_gradient_kernel(kernel_id, [](auto) {}); }
+inline int check_grad_kernel(const char* who, int kernel_id) {
+  if (has_exact_gradient(kernel_id)) return 0;
+  set_error(std::string(who) + ": defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard");
+  return GPRC_ERR_ARG;
+}
+
+// the spec with the constants the contraction kernels want:
+//   sqrexp p[1] = 1 / (2 l^2);  gammaexp p[2] = 1 / l^2, p[3] = gamma / 2;  ratquad p[2] = 1 / (2 alpha l^2);  ARD p[k] = 1 / l_k
+inline KernelSpec make_deriv_spec(const KernelSpec& ks) {
+  KernelSpec g = ks;
+  if (ks.id == GPRC_SQREXP) g.p[1] = 1.0 / (2.0 * (ks.p[0] * ks.p[0]));
+  if (ks.id == GPRC_GAMMAEXP) { g.p[2] = 1.0 / (ks.p[0] * ks.p[0]); g.p[3] = 0.5 * ks.p[1]; }
+  if (ks.id == GPRC_RATQUAD) g.p[2] = 1.0 / (2.0 * ks.p[1] * (ks.p[0] * ks.p[0]));
+  if (ks.id == GPRC_SQREXP_ARD)
+    for (int k = 0; k < ks.n_params; ++k) g.p[k] = 1.0 / ks.p[k];
+  return g;
+}
+
+// ---- device --------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// base R `^` for doubles (arithmetic.c R_POW / R_pow): x^2 is x*x, the rest is libm pow
+__device__ __forceinline__ double r_pow(double x, double y) {
+  if (y == 2.0) return x * x;
+  if (x == 1.0 || y == 0.0) return 1.0;
+  if (x == 0.0) return y > 0.0 ? 0.0 : (y < 0.0 ? __builtin_huge_val() : y);
+  return pow(x, y);
+}
+
+// Coordinates r0 .. r0 + dc - 1 of the points g0 .. g0 + count - 1 of P (point-major, d coordinates each; zero from point npts on),
+// by the 256 threads of the workgroup (t: the thread): store(i, r, value) for point i of the tile and coordinate r of the pass.
+// SCALED: times scale[r0 + r] (ARD in the contraction kernels: the coordinates divided by their length scale).
+template <bool SCALED, class Store>
+__device__ __forceinline__ void stage_points(const double* P, int64_t g0, int64_t npts, int64_t d, int64_t r0, int dc, int count,
+                                             const double* scale, int t, Store store) {
+  for (int e = t; e < count * dc; e += 256) {
+    const int i = e / dc, r = e - i * dc;
+    const int64_t g = g0 + i;
+    double v = (g < npts) ? P[g * d + r0 + r] : 0.0;
+    if constexpr (SCALED) v *= scale[r0 + r];
+    store(i, r, v);
+  }
+}
+
+// s0[c] / s1[c] += (a - b)^2 over the dc staged coordinates, for the lane's two rows and its wave's 16 columns
+__device__ __forceinline__ void accum_sqdist(const double (&As)[PT_D][PT_R], const double (&Bs)[PT_C][PT_D + 1], int dc, int lane, int wave,
+                                             double (&s0)[16], double (&s1)[16]) {
+  for (int r = 0; r < dc; ++r) {
+    const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const double b = Bs[wave * 16 + c][r];
+      const double t0 = av.x - b, t1 = av.y - b;
+      s0[c] = fma(t0, t0, s0[c]);
+      s1[c] = fma(t1, t1, s1[c]);
+    }
+  }
+}
+
+// its sibling, ARD's second pass: sum over the lane's 32 pairs of w * (a - b)^2 for the ONE staged coordinate r, columns ascending
+__device__ __forceinline__ double weighted_sqdiff(const double (&As)[PT_D][PT_R], const double (&Bs)[PT_C][PT_D + 1], int r, int lane, int wave,
+                                                  const double (&w0)[16], const double (&w1)[16]) {
+  const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
+  double acc = 0.0;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    const double b = Bs[wave * 16 + c][r];
+    const double t0 = av.x - b, t1 = av.y - b;
+    acc = fma(w0[c], t0 * t0, acc);
+    acc = fma(w1[c], t1 * t1, acc);
+  }
+  return acc;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;  // lane 0 holds the sum
+}
+
+// the four waves' partials in a fixed order, the two forms in use: pairwise (the scalar sums of the gradients) and in wave order
+// (the fused predict epilogues, whose partials are also summed tile after tile in order)
+__device__ __forceinline__ double sum4_pairs(double w0, double w1, double w2, double w3) { return (w0 + w1) + (w2 + w3); }
+__device__ __forceinline__ double sum4_in_order(double w0, double w1, double w2, double w3) { return ((w0 + w1) + w2) + w3; }
+
+}  // namespace
+
+}  // namespace gprc
