@@ -8,15 +8,16 @@ CPU fallback: without the built library / an MI355X the compute calls raise.
 from . import _native
 from ._native import GprcError, NotPositiveDefinite, Context, default_context, device_count
 from .covfunc import (cov_func, covariance_matrix, constant, linear, polynomial, sqrexp, gammaexp,
-                      rationalquadratic, sqrexp_ard, CovFunc)
+                      rationalquadratic, sqrexp_ard, matern32, matern52, matern32_ard, matern52_ard, CovFunc)
 from .gpr import (GPR, GPR_constant, GPR_linear, GPR_polynomial, GPR_sqrexp, GPR_gammaexp,
-                  GPR_rationalquadratic, GPR_sqrexp_ard)
+                  GPR_rationalquadratic, GPR_sqrexp_ard, GPR_matern32, GPR_matern52, GPR_matern32_ard, GPR_matern52_ard)
 from .gpc import GPC
 from .fit import fit, dens, dens_deriv, logp_grad, optimize, logq_grad, optimize_gpc
 from .sampling import multivariate_normal, expand_range, mvn_factor, sym_eigen
 from .simulation import combine_all, iid_noise, simulate_regression, simulate_regression_gp, simulate_classification
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "logq_grad", "optimize_gpc", "sqrexp_ard", "GPR_sqrexp_ard", "multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "combine_all", "iid_noise",
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "logq_grad", "optimize_gpc", "sqrexp_ard", "GPR_sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard",
+           "GPR_matern32", "GPR_matern52", "GPR_matern32_ard", "GPR_matern52_ard", "multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "combine_all", "iid_noise",
            "simulate_regression", "simulate_regression_gp", "simulate_classification", "GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp",
            "GPR_rationalquadratic", "GPC", "cov_func", "covariance_matrix", "constant", "linear", "polynomial",
            "sqrexp", "gammaexp", "rationalquadratic", "CovFunc", "GprcError", "NotPositiveDefinite", "Context",

@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgprc_native" + os.environ.get("GPRC_LIB_SUFFIX", "") + ".so")
 
 # kernel ids (include/gprc_native.h gprc_kernel_id)
-CONSTANT, LINEAR, POLYNOMIAL, SQREXP, GAMMAEXP, RATQUAD, SQREXP_ARD = range(7)
+CONSTANT, LINEAR, POLYNOMIAL, SQREXP, GAMMAEXP, RATQUAD, SQREXP_ARD, MATERN32, MATERN52, MATERN32_ARD, MATERN52_ARD = range(11)
+ARD_KERNELS = (SQREXP_ARD, MATERN32_ARD, MATERN52_ARD)   # one length scale per input dimension
 
 OK = 0
 GPC_REFERENCE_STOP = 1

@@ -1,7 +1,8 @@
 """Covariance-function layer: the reference's operator API (R/GPRclass.R:353-357, 378-403, 424-427).
 
 `cov_func(func, ...)` fixes the parameters of one of the six kernel generics (or of `sqrexp_ard`, the squared
-exponential with one length scale per input dimension, which the reference does not have) and returns a callable
+exponential with one length scale per input dimension, or of the Matern kernels `matern32`, `matern52`, `matern32_ard`,
+`matern52_ard`, none of which the reference has) and returns a callable
 `k(x, y)` obeying the reference's closure contract (two d x m matrices -> the m kernel values of their
 columns).  The returned closure carries `gprc_kernel = (id, params)`, which is what routes
 `covariance_matrix`, `GPR` and `GPC` to the fused HIP fill kernel.  Arbitrary user closures are part of
@@ -15,7 +16,7 @@ import numpy as np
 from . import _native as nat
 
 __all__ = ["cov_func", "covariance_matrix", "constant", "linear", "polynomial", "sqrexp", "gammaexp",
-           "rationalquadratic", "sqrexp_ard", "CovFunc", "KernelGeneric", "as_points"]
+           "rationalquadratic", "sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard", "CovFunc", "KernelGeneric", "as_points"]
 
 
 def as_points(X, d=None, what="X"):
@@ -83,6 +84,12 @@ gammaexp = KernelGeneric("gammaexp", nat.GAMMAEXP, ("l", "gamma"))
 rationalquadratic = KernelGeneric("rationalquadratic", nat.RATQUAD, ("l", "alpha"))
 # automatic relevance determination: exp(-1/2 sum_k ((x_k - y_k) / l_k)^2), l of length nrow(X) (no reference counterpart)
 sqrexp_ard = KernelGeneric("sqrexp_ard", nat.SQREXP_ARD, ("l",))
+# Matern: (1 + a) exp(-a), a = sqrt(3) r / l, and (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r / l; ARD: r / l -> sqrt(sum_k ((x_k - y_k) / l_k)^2)
+# (no reference counterpart; nu = 1/2 is gammaexp(l, gamma = 1))
+matern32 = KernelGeneric("matern32", nat.MATERN32, ("l",))
+matern52 = KernelGeneric("matern52", nat.MATERN52, ("l",))
+matern32_ard = KernelGeneric("matern32_ard", nat.MATERN32_ARD, ("l",))
+matern52_ard = KernelGeneric("matern52_ard", nat.MATERN52_ARD, ("l",))
 
 
 class CovFunc:
@@ -92,15 +99,17 @@ class CovFunc:
         self.func = func
         self.values = dict(values)
         self.params = func.param_vector(values)
-        if func.kernel_id == nat.SQREXP_ARD and not (self.params.size >= 1 and np.all(np.isfinite(self.params)) and np.all(self.params > 0)):
+        if func.kernel_id in nat.ARD_KERNELS and not (self.params.size >= 1 and np.all(np.isfinite(self.params)) and np.all(self.params > 0)):
             raise ValueError("all(is.finite(l)), all(l > 0) are not all TRUE")
+        if func.kernel_id in (nat.MATERN32, nat.MATERN52) and not (self.params.size == 1 and np.isfinite(self.params[0]) and self.params[0] > 0):
+            raise ValueError("length(l) == 1, is.finite(l), l > 0 are not all TRUE")
         self.gprc_kernel = (func.kernel_id, self.params)
 
     def native_params(self, d):
-        """Parameter vector checked against the input dimension (linear: sigma of length 1 or d; sqrexp_ard: l of length d)."""
+        """Parameter vector checked against the input dimension (linear: sigma of length 1 or d; the ARD kernels: l of length d)."""
         if self.func.kernel_id == nat.LINEAR and self.params.size not in (1, d):
             raise ValueError("length(sigma) == nrow(X) is not TRUE")
-        if self.func.kernel_id == nat.SQREXP_ARD and self.params.size != d:
+        if self.func.kernel_id in nat.ARD_KERNELS and self.params.size != d:
             raise ValueError("length(l) == nrow(X) is not TRUE")
         return self.params
 
@@ -131,7 +140,7 @@ def cov_func(func, *args, **kwargs):
     """cov_func(func, ...) (R/GPRclass.R:424-427): a covariance function with fixed parameters."""
     if not isinstance(func, KernelGeneric):
         raise TypeError("cov_func: `func` must be one of constant, linear, polynomial, sqrexp, gammaexp, "
-                        "rationalquadratic, sqrexp_ard on the MI355X path (arbitrary R closures stay on the reference's R path)")
+                        "rationalquadratic, sqrexp_ard, matern32, matern52, matern32_ard, matern52_ard on the MI355X path (arbitrary R closures stay on the reference's R path)")
     return CovFunc(func, func.bind(args, kwargs))
 
 

@@ -130,7 +130,7 @@ int launch_deriv_rowsum(hipStream_t s, int kernel, double v0, double v1, const d
 // the exact gradient's contraction: one pass over the stored lower triangle of W = -(K + noise I)^-1 (n_pad x n_pad, ld), K and dK/dtheta
 // recomputed from X.  part: grad_partial_rows() x (ks.n_params + 1) doubles, row g = what workgroup g summed over its tiles of
 //   sum_ij (alpha_i alpha_j + W_ij) dK_ij / dtheta_k   (ARD: times l_k, the host divides)   and, last, of sum_i (alpha_i^2 + W_ii);
-// the caller sums the rows in order and halves.  Kernels: sqrexp, gammaexp, rationalquadratic, sqrexp_ard.
+// the caller sums the rows in order and halves.  Kernels: sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52, matern32_ard, matern52_ard.
 int64_t grad_partial_rows();
 int launch_grad_contract(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* alpha, const double* W,
                          int64_t ld, double* part);

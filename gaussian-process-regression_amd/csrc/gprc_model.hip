@@ -21,12 +21,17 @@ int make_spec(int kernel, const double* params, int n_params, int64_t d, KernelS
     case GPRC_LINEAR: ok = n_params == 1 || n_params == d; break;
     case GPRC_POLYNOMIAL: case GPRC_GAMMAEXP: case GPRC_RATQUAD: ok = n_params == 2; break;
     case GPRC_SQREXP: ok = n_params == 1; break;
-    case GPRC_SQREXP_ARD:
-      if (n_params != d) { set_error("sqrexp_ard: one length scale per input dimension (n_params == d <= 256)"); return GPRC_ERR_ARG; }
+    case GPRC_SQREXP_ARD: case GPRC_MATERN32_ARD: case GPRC_MATERN52_ARD: case GPRC_MATERN32: case GPRC_MATERN52: {
+      const std::string name = kernel == GPRC_SQREXP_ARD ? "sqrexp_ard" : kernel == GPRC_MATERN32_ARD ? "matern32_ard" : kernel == GPRC_MATERN52_ARD ? "matern52_ard"
+                               : kernel == GPRC_MATERN32 ? "matern32" : "matern52";
+      if (kernel == GPRC_MATERN32 || kernel == GPRC_MATERN52) {
+        if (n_params != 1) { set_error(name + ": one length scale (n_params == 1)"); return GPRC_ERR_ARG; }
+      } else if (n_params != d) { set_error(name + ": one length scale per input dimension (n_params == d <= 256)"); return GPRC_ERR_ARG; }
       for (int i = 0; i < n_params; ++i)
-        if (!(params[i] > 0.0) || !std::isfinite(params[i])) { set_error("sqrexp_ard: every length scale must be finite and > 0"); return GPRC_ERR_ARG; }
+        if (!(params[i] > 0.0) || !std::isfinite(params[i])) { set_error(name + ": every length scale must be finite and > 0"); return GPRC_ERR_ARG; }
       ok = true;
       break;
+    }
     default: set_error("unknown kernel id"); return GPRC_ERR_ARG;
   }
   if (!ok) { set_error("wrong number of kernel parameters for this kernel"); return GPRC_ERR_ARG; }
@@ -449,6 +454,14 @@ int grad_from_partials(hipStream_t s, const double* part, int64_t cols, int kern
       break;
     case GPRC_RATQUAD: grad_out[1] = (double)(0.5L * acc[1]);   // and the length scale as sqrexp's:
     case GPRC_SQREXP: grad_out[0] = (double)(0.5L * acc[0] / ((long double)p0 * p0 * p0)); break;
+    case GPRC_MATERN32: grad_out[0] = (double)(acc[0] / (2.0L * (long double)p0)); break;
+    case GPRC_MATERN52: grad_out[0] = (double)(acc[0] / (6.0L * (long double)p0)); break;
+    case GPRC_MATERN32_ARD:
+      for (int k = 0; k < n_params; ++k) grad_out[k] = (double)(3.0L * acc[(size_t)k] / (2.0L * (long double)params[k]));
+      break;
+    case GPRC_MATERN52_ARD:
+      for (int k = 0; k < n_params; ++k) grad_out[k] = (double)(5.0L * acc[(size_t)k] / (6.0L * (long double)params[k]));
+      break;
     default:
       for (int k = 0; k < n_params; ++k) grad_out[k] = (double)(0.5L * acc[(size_t)k] / (long double)params[k]);
   }

@@ -37,7 +37,7 @@ __device__ __forceinline__ double accum(double s, double a, double b, double sig
   if constexpr (KID == GPRC_LINEAR) return fma(sig * a, b, s);  // colSums(sigma * x * y)
   else if constexpr (KID == GPRC_POLYNOMIAL) return fma(a, b, s);  // colSums(x * y)
   else if constexpr (KID == GPRC_CONSTANT) return s;
-  else if constexpr (KID == GPRC_SQREXP_ARD) {
+  else if constexpr (is_ard(KID)) {
     double t = (a - b) * sig;  // colSums(((x - y) / l)^2): sig = 1 / l_k (make_fill_spec)
     return fma(t, t, s);
   }
@@ -79,6 +79,22 @@ __device__ __forceinline__ double finish(double s, const KernelSpec& ks) {
     return exp(-q);
   }
   else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);  // s is already the scaled distance: sqrexp with l = 1
+  else if constexpr (is_matern(KID)) {
+    // (1 + a) exp(-a) and (1 + a + a^2 / 3) exp(-a), a = sqrt(u), u = 3 s / l^2 or 5 s / l^2: one correctly rounded square root, one exp, at most
+    // four multiply-adds; no division, no pow.  The quotient by the launch constant l^2 / 3 (l^2 / 5) as for sqexp: reciprocal + one fma correction.
+    // ARD: s is already the scaled distance, u = 3 s (5 s).  a^2 / 3 is taken from u, which the root has not rounded yet.  s = 0: a = 0, exp = 1, the
+    // polynomial 1, the value exactly 1.
+    double u;
+    if constexpr (is_ard(KID)) u = (is_matern32(KID) ? 3.0 : 5.0) * s;
+    else {
+      const double c = ks.p[1], rc = ks.p[2];  // l^2 / 3 (l^2 / 5) and its reciprocal (make_fill_spec)
+      u = s * rc;
+      u = fma(fma(-u, c, s), rc, u);
+    }
+    const double a = sqrt(u), e = exp(-a);
+    if constexpr (is_matern32(KID)) return fma(a, e, e);
+    else return fma(u, 1.0 / 3.0, 1.0 + a) * e;
+  }
   else if constexpr (KID == GPRC_GAMMAEXP) {
     // exp(-(sqrt(s) / l)^gamma).  gamma == 2 is R's x^2 = x * x (R_pow); any other gamma > 0 went through libm pow -- a special-case ladder and
     // an extended-precision log / exp, ~3x the work of a plain log and exp: the gamma-exponential fill ran at 0.8 TB/s against 3.5 for sqexp.
@@ -164,7 +180,7 @@ __global__ __launch_bounds__(256) void fill_kernel(FillArgs a) {
     // unscaled: the per-coordinate factors stay in Sg
     stage_points<false>(a.A, ti, a.nA, a.d, r0, dc, PT_R, nullptr, t, [&](int i, int r, double v) { As[r][i] = v; });
     stage_points<false>(a.B, tj, a.nB, a.d, r0, dc, PT_C, nullptr, t, [&](int j, int r, double v) { Bs[j][r] = v; });
-    if (t < dc) Sg[t] = (KID == GPRC_LINEAR) ? (a.ks.n_params == 1 ? a.ks.p[0] : a.ks.p[r0 + t]) : (KID == GPRC_SQREXP_ARD) ? a.ks.p[r0 + t] : 1.0;
+    if (t < dc) Sg[t] = (KID == GPRC_LINEAR) ? (a.ks.n_params == 1 ? a.ks.p[0] : a.ks.p[r0 + t]) : is_ard(KID) ? a.ks.p[r0 + t] : 1.0;
     __syncthreads();
     for (int r = 0; r < dc; ++r) {
       const double2 av = *reinterpret_cast<const double2*>(&As[r][2 * lane]);
@@ -243,17 +259,22 @@ __global__ __launch_bounds__(256) void colwise_kernel(KernelSpec ks, const doubl
   if (c >= m) return;
   double s = 0.0;
   for (int64_t r = 0; r < d; ++r) {
-    double sg = (KID == GPRC_LINEAR) ? (ks.n_params == 1 ? ks.p[0] : ks.p[r]) : (KID == GPRC_SQREXP_ARD) ? ks.p[r] : 1.0;
+    double sg = (KID == GPRC_LINEAR) ? (ks.n_params == 1 ? ks.p[0] : ks.p[r]) : is_ard(KID) ? ks.p[r] : 1.0;
     s = accum<KID>(s, x[c * d + r], y[c * d + r], sg);
   }
   out[c] = finish<KID>(s, ks);
 }
 
-// device-side copy of the spec with derived constants (sqexp: p[1] = 2 l^2, p[2] = 1 / (2 l^2); ARD: p[k] = 1 / l_k)
+// device-side copy of the spec with derived constants (sqexp: p[1] = 2 l^2, p[2] = 1 / (2 l^2); ARD: p[k] = 1 / l_k;
+// matern32 / matern52: p[1] = l^2 / 3 or l^2 / 5, p[2] = 1 / p[1])
 KernelSpec make_fill_spec(const KernelSpec& ks) {
   KernelSpec d = ks;
-  if (ks.id == GPRC_SQREXP_ARD)
+  if (is_ard(ks.id))
     for (int k = 0; k < ks.n_params; ++k) d.p[k] = 1.0 / ks.p[k];
+  if (ks.id == GPRC_MATERN32 || ks.id == GPRC_MATERN52) {
+    d.p[1] = (ks.p[0] * ks.p[0]) / (ks.id == GPRC_MATERN32 ? 3.0 : 5.0);
+    d.p[2] = 1.0 / d.p[1];
+  }
   if (ks.id == GPRC_SQREXP) {
     d.p[1] = 2.0 * (ks.p[0] * ks.p[0]);
     d.p[2] = 1.0 / d.p[1];

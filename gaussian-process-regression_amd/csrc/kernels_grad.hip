@@ -13,6 +13,11 @@
 //   gammaexp      sum M K u, sum M K u L        (x gamma / l, x -1/2)        u = (s / l^2)^(gamma / 2), L = log(s / l^2); 0 at s = 0
 //   ratquad       sum M K s / q, sum M K (x / q - log q)   (x 1 / l^3, x 1)  x = s / (2 alpha l^2), q = 1 + x
 //   sqrexp_ard    sum M K t_k^2  per k          (x 1 / l_k)                  t_k = (x_k - y_k) / l_k
+//   matern32      sum M e^-a u                  (x 1 / l)                    u = 3 s / l^2, a = sqrt(u)         (dK / dl = 3 e^-a s / l^3)
+//   matern52      sum M (1 + a) e^-a u          (x 1 / (3 l))                u = 5 s / l^2, a = sqrt(u)         (dK / dl = 5/3 (1 + a) e^-a s / l^3)
+//   matern32_ard  sum M e^-a t_k^2  per k       (x 3 / l_k)                  a = sqrt(3 sum_k t_k^2)
+//   matern52_ard  sum M (1 + a) e^-a t_k^2      (x 5 / (3 l_k))              a = sqrt(5 sum_k t_k^2)
+// (no 1 / r anywhere in the Matern derivatives: s = 0 needs no convention.)
 // For ARD a lane keeps M K of its 32 elements in registers and passes over the coordinates a second time, 16 at a time: the d sums
 // never live in registers at once (d <= 256), and nothing of size n x d is formed.
 //
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
   __shared__ __attribute__((aligned(16))) double Rv[LAPLACE ? 4 : 1][PT_R];   // Laplace: a, sw, u, g of the tile's rows ...
   __shared__ double Cv[LAPLACE ? 4 : 1][PT_C];                                 // ... and of its columns
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int np = KID == GPRC_SQREXP_ARD ? (int)a.d : (KID == GPRC_SQREXP ? 1 : 2);
+  const int np = is_ard(KID) ? (int)a.d : ((KID == GPRC_SQREXP || is_matern(KID)) ? 1 : 2);
   constexpr int NZ = LAPLACE ? 0 : 1;   // regression leaves one more sum per workgroup, the diagonal's
   for (int k = t; k <= np; k += 256) gacc[k] = 0.0;
   double a0 = 0.0, a1 = 0.0, nz = 0.0;  // isotropic kernels: this lane's sums over all its tiles; nz: the diagonal's M_ii
@@ -78,8 +83,8 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
 
     auto stage = [&](int64_t r0, int dc) {  // coordinates r0 .. r0 + dc - 1 of the tile's points (ARD: divided by their length scale)
       __syncthreads();
-      stage_points<KID == GPRC_SQREXP_ARD>(a.X, ti, a.n, a.d, r0, dc, PT_R, a.ks.p, t, [&](int i, int r, double v) { As[r][i] = v; });
-      stage_points<KID == GPRC_SQREXP_ARD>(a.X, tj, a.n, a.d, r0, dc, PT_C, a.ks.p, t, [&](int j, int r, double v) { Bs[j][r] = v; });
+      stage_points<is_ard(KID)>(a.X, ti, a.n, a.d, r0, dc, PT_R, a.ks.p, t, [&](int i, int r, double v) { As[r][i] = v; });
+      stage_points<is_ard(KID)>(a.X, tj, a.n, a.d, r0, dc, PT_C, a.ks.p, t, [&](int j, int r, double v) { Bs[j][r] = v; });
       if constexpr (LAPLACE) {
         if (r0 == 0) {
           const int v = t >> 6, j = t & 63;   // 4 vectors x 64 columns; 4 x 128 rows, two per thread
@@ -134,6 +139,16 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
       } else if constexpr (KID == GPRC_SQREXP_ARD) {
         s0[c] = m0 * exp(-0.5 * s0[c]);  // M K, kept for the second pass
         s1[c] = m1 * exp(-0.5 * s1[c]);
+      } else if constexpr (KID == GPRC_MATERN32 || KID == GPRC_MATERN52) {
+        const double h = a.ks.p[1];  // 3 / l^2, 5 / l^2
+        const double u0 = s0[c] * h, u1 = s1[c] * h, q0 = sqrt(u0), q1 = sqrt(u1), e0 = exp(-q0), e1 = exp(-q1);
+        a0 = fma(m0 * (KID == GPRC_MATERN32 ? e0 : fma(q0, e0, e0)), u0, a0);
+        a0 = fma(m1 * (KID == GPRC_MATERN32 ? e1 : fma(q1, e1, e1)), u1, a0);
+      } else if constexpr (is_matern(KID)) {  // ARD: M g~ kept for the second pass; s is the scaled distance
+        constexpr double nu2 = is_matern32(KID) ? 3.0 : 5.0;
+        const double q0 = sqrt(nu2 * s0[c]), q1 = sqrt(nu2 * s1[c]), e0 = exp(-q0), e1 = exp(-q1);
+        s0[c] = m0 * (is_matern32(KID) ? e0 : fma(q0, e0, e0));
+        s1[c] = m1 * (is_matern32(KID) ? e1 : fma(q1, e1, e1));
       } else if constexpr (KID == GPRC_GAMMAEXP) {
         const double rl2 = a.ks.p[2], hg = a.ks.p[3];  // 1 / l^2, gamma / 2
         if (s0[c] > 0.0) {
@@ -161,7 +176,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
       }
     }
 
-    if constexpr (KID == GPRC_SQREXP_ARD) {
+    if constexpr (is_ard(KID)) {
       for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {
         const int dc = (int)((a.d - r0 < PT_D) ? (a.d - r0) : PT_D);
         if (a.d > PT_D) stage(r0, dc);  // (d <= 16: the only chunk is still in LDS)
@@ -183,7 +198,7 @@ __global__ __launch_bounds__(256) void grad_contract_kernel(std::conditional_t<L
   if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; red[wave][2] = nz; }
   __syncthreads();
   if (t == 0) {
-    if constexpr (KID != GPRC_SQREXP_ARD) {
+    if constexpr (!is_ard(KID)) {
       gacc[0] = sum4_pairs(red[0][0], red[1][0], red[2][0], red[3][0]);
       if (np == 2) gacc[1] = sum4_pairs(red[0][1], red[1][1], red[2][1], red[3][1]);
     }
@@ -210,7 +225,7 @@ int launch_contract(hipStream_t s, const KernelSpec& ks, std::conditional_t<LAPL
   // bytes: the stored triangle once + X and alpha (Laplace: four vectors); flops: the distance (3 d), the kernel and its derivatives
   // (~60; Laplace: the 9 of M more), ARD's second pass (4 d)
   const double elems = 0.5 * (double)a.n * (double)(a.n + 1), n = (double)a.n, d = (double)a.d;
-  ProfScope ps(s, LAPLACE ? PK_GPC_GRAD_CONTRACT : PK_GRAD_CONTRACT, elems * (3.0 * d + (LAPLACE ? 69.0 : 60.0) + (ks.id == GPRC_SQREXP_ARD ? 4.0 * d : 0.0)),
+  ProfScope ps(s, LAPLACE ? PK_GPC_GRAD_CONTRACT : PK_GRAD_CONTRACT, elems * (3.0 * d + (LAPLACE ? 69.0 : 60.0) + (is_ard(ks.id) ? 4.0 * d : 0.0)),
                8.0 * (elems + n * d + (LAPLACE ? 4.0 * n : n)));
   with_gradient_kernel(ks.id, [&](auto kid) { hipLaunchKernelGGL((grad_contract_kernel<decltype(kid)::value, LAPLACE>), grid, block, 0, s, a); });
   GPRC_LAUNCH_CHECK();

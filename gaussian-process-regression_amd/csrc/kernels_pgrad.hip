@@ -8,6 +8,10 @@
 //   sqrexp_ard    h = k, t_c = 1 / l_c^2            coordinates staged divided by l_c: k (x*_c - x_jc) / l_c,        by 1 / l_c
 //   gammaexp      h = k gamma u / s, u = (s / l^2)^(gamma / 2); 0 at s = 0       k u / s (x*_c - x_jc),              by gamma
 //   ratquad       h = k / (q l^2), q = 1 + s / (2 alpha l^2)                     k / q (x*_c - x_jc),                by 1 / l^2
+//   matern32      h = 3 e^-a / l^2, a = sqrt(3 s) / l                            e^-a (x*_c - x_jc),                 by 3 / l^2
+//   matern52      h = 5/3 (1 + a) e^-a / l^2, a = sqrt(5 s) / l                  (1 + a) e^-a (x*_c - x_jc),         by 5 / (3 l^2)
+//   matern32_ard, matern52_ard    the same with l = 1 on coordinates staged divided by l_c, t_c = 1 / l_c^2;         by 3 / l_c, 5 / (3 l_c)
+// (h is finite at s = 0 for the Matern kernels and the difference is 0: that pair contributes an exact 0.)
 // The difference is formed directly (x* sum p - sum p x cancels for points far from the origin).
 //
 // A workgroup owns one row tile of the chunk (128 test points, two per lane), one STRIPE of column tiles (64 training points each,
@@ -53,7 +57,11 @@ template <int KID>
 __device__ __forceinline__ double pair_weight(double s, const KernelSpec& ks) {
   if constexpr (KID == GPRC_SQREXP) return exp(-s * ks.p[1]);        // p[1] = 1 / (2 l^2)
   else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);   // s is the scaled distance
-  else if constexpr (KID == GPRC_GAMMAEXP) {
+  else if constexpr (is_matern(KID)) {                               // p[1] = 3 / l^2 or 5 / l^2; ARD: s is the scaled distance
+    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
+    if constexpr (is_matern32(KID)) return e;
+    else return fma(a, e, e);
+  } else if constexpr (KID == GPRC_GAMMAEXP) {
     if (!(s > 0.0)) return 0.0;                                      // the limit for gamma > 1, the convention for gamma <= 1
     const double u = exp(ks.p[3] * log(s * ks.p[2]));                // p[2] = 1 / l^2, p[3] = gamma / 2
     return exp(-u) * u / s;
@@ -78,12 +86,12 @@ __global__ __launch_bounds__(256) void pred_grad_kernel(PgradArgs a) {
   const int64_t tile0 = stripe * a.stripe_tiles;
   const int64_t tile1 = (tile0 + a.stripe_tiles < a.ntiles) ? tile0 + a.stripe_tiles : a.ntiles;
   const int64_t gi0 = ti + 2 * lane;
-  constexpr bool ARD = KID == GPRC_SQREXP_ARD;   // coordinates staged divided by their length scale
+  constexpr bool ARD = is_ard(KID);   // coordinates staged divided by their length scale
 
   double xs0[PG_Z], xs1[PG_Z], gm0[PG_Z], gm1[PG_Z], gv0[PG_Z], gv1[PG_Z];
 #pragma unroll
   for (int r = 0; r < PG_Z; ++r) {
-    const double sc = (KID == GPRC_SQREXP_ARD && r < dz) ? a.ks.p[z0 + r] : 1.0;
+    const double sc = (ARD && r < dz) ? a.ks.p[z0 + r] : 1.0;
     xs0[r] = (r < dz && gi0 < a.m) ? a.Xs[gi0 * a.d + z0 + r] * sc : 0.0;
     xs1[r] = (r < dz && gi0 + 1 < a.m) ? a.Xs[(gi0 + 1) * a.d + z0 + r] * sc : 0.0;
     gm0[r] = gm1[r] = gv0[r] = gv1[r] = 0.0;
@@ -154,7 +162,7 @@ __global__ __launch_bounds__(256) void pred_grad_kernel(PgradArgs a) {
   if constexpr (WITH_VAR) write_partials(gv0, gv1, a.pvar);
 }
 
-// out[c + d i] = f_c * sum over the stripes, in order, of part[(st d + c) m_pad + i];  f_c = sign * (ard ? ks.p[c] : iso)
+// out[c + d i] = f_c * sum over the stripes, in order, of part[(st d + c) m_pad + i];  f_c = sign * (ard ? iso * ks.p[c] : iso)
 __global__ __launch_bounds__(256) void pred_grad_sum_kernel(const double* part, int64_t stripes, int64_t d, int64_t m_pad, int64_t m, double sign,
                                                             double iso, int ard, KernelSpec ks, double* out) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;   // rows fastest: the partials are read contiguously
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(256) void pred_grad_sum_kernel(const double* part, 
   const int64_t c = idx / m, i = idx - c * m;
   double s = 0.0;
   for (int64_t st = 0; st < stripes; ++st) s += part[(st * d + c) * m_pad + i];
-  out[c + d * i] = (sign * (ard ? ks.p[c] : iso)) * s;
+  out[c + d * i] = (sign * (ard ? iso * ks.p[c] : iso)) * s;
 }
 
 // column tiles per stripe: at most PG_MAX_STRIPES stripes (n_pad = 65536: 2048 columns each)
@@ -204,11 +212,21 @@ int launch_pred_grad_sum(hipStream_t s, const KernelSpec& ks, const double* part
                          double* out) {
   if (m <= 0) return 0;
   GPRC_TRY(check_grad_kernel("predict_grad", ks.id));
-  // the factor the tail applies (ARD: 1 / l_c per coordinate, from the spec)
-  const double iso = ks.id == GPRC_GAMMAEXP ? ks.p[1] : (ks.id == GPRC_SQREXP_ARD ? 1.0 : 1.0 / (ks.p[0] * ks.p[0]));
+  // the factor the tail applies (ARD: its constant times 1 / l_c per coordinate, from the spec; sqrexp_ard's 1.0 * p[c] is p[c] exactly)
+  const double il2 = 1.0 / (ks.p[0] * ks.p[0]);
+  double iso = il2;
+  switch (ks.id) {
+    case GPRC_GAMMAEXP: iso = ks.p[1]; break;
+    case GPRC_SQREXP_ARD: iso = 1.0; break;
+    case GPRC_MATERN32: iso = 3.0 * il2; break;
+    case GPRC_MATERN52: iso = 5.0 / 3.0 * il2; break;
+    case GPRC_MATERN32_ARD: iso = 3.0; break;
+    case GPRC_MATERN52_ARD: iso = 5.0 / 3.0; break;
+    default: break;
+  }
   // dk / dx* = -h (x* - x) t: the mean's gradient carries -1, the variance's -2 * -1
   hipLaunchKernelGGL(pred_grad_sum_kernel, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, s, part, pred_grad_stripes(n_pad), d, m_pad, m,
-                     variance ? 2.0 : -1.0, iso, ks.id == GPRC_SQREXP_ARD ? 1 : 0, make_deriv_spec(ks), out);
+                     variance ? 2.0 : -1.0, iso, is_ard(ks.id) ? 1 : 0, make_deriv_spec(ks), out);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

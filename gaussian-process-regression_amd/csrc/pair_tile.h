@@ -36,28 +36,38 @@ inline bool with_kernel_id(int id, F&& f) {
 }
 template <class F>
 inline bool with_any_kernel(int id, F&& f) {
-  return with_kernel_id<GPRC_CONSTANT, GPRC_LINEAR, GPRC_POLYNOMIAL, GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD>(id, std::forward<F>(f));
+  return with_kernel_id<GPRC_CONSTANT, GPRC_LINEAR, GPRC_POLYNOMIAL, GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD, GPRC_MATERN32, GPRC_MATERN52,
+                        GPRC_MATERN32_ARD, GPRC_MATERN52_ARD>(id, std::forward<F>(f));
 }
+// the families the per-kernel bodies branch on: one length scale per coordinate; Matern of either order, ARD or not
+constexpr bool is_ard(int id) { return id == GPRC_SQREXP_ARD || id == GPRC_MATERN32_ARD || id == GPRC_MATERN52_ARD; }
+constexpr bool is_matern32(int id) { return id == GPRC_MATERN32 || id == GPRC_MATERN32_ARD; }
+constexpr bool is_matern52(int id) { return id == GPRC_MATERN52 || id == GPRC_MATERN52_ARD; }
+constexpr bool is_matern(int id) { return is_matern32(id) || is_matern52(id); }
 // the kernels whose dK / dtheta and dk / dx* the contraction kernels know: THE statement of that set
 template <class F>
 inline bool with_gradient_kernel(int id, F&& f) {
-  return with_kernel_id<GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD>(id, std::forward<F>(f));
+  return with_kernel_id<GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD, GPRC_MATERN32, GPRC_MATERN52, GPRC_MATERN32_ARD, GPRC_MATERN52_ARD>(
+      id, std::forward<F>(f));
 }
 inline bool has_exact_gradient(int kernel_id) { return with_gradient_kernel(kernel_id, [](auto) {}); }
 inline int check_grad_kernel(const char* who, int kernel_id) {
   if (has_exact_gradient(kernel_id)) return 0;
-  set_error(std::string(who) + ": defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard");
+  set_error(std::string(who) + ": defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard, matern32, matern52, matern32_ard and matern52_ard");
   return GPRC_ERR_ARG;
 }
 
 // the spec with the constants the contraction kernels want:
-//   sqrexp p[1] = 1 / (2 l^2);  gammaexp p[2] = 1 / l^2, p[3] = gamma / 2;  ratquad p[2] = 1 / (2 alpha l^2);  ARD p[k] = 1 / l_k
+//   sqrexp p[1] = 1 / (2 l^2);  gammaexp p[2] = 1 / l^2, p[3] = gamma / 2;  ratquad p[2] = 1 / (2 alpha l^2);  ARD p[k] = 1 / l_k;
+//   matern32 p[1] = 3 / l^2;  matern52 p[1] = 5 / l^2
 inline KernelSpec make_deriv_spec(const KernelSpec& ks) {
   KernelSpec g = ks;
   if (ks.id == GPRC_SQREXP) g.p[1] = 1.0 / (2.0 * (ks.p[0] * ks.p[0]));
   if (ks.id == GPRC_GAMMAEXP) { g.p[2] = 1.0 / (ks.p[0] * ks.p[0]); g.p[3] = 0.5 * ks.p[1]; }
   if (ks.id == GPRC_RATQUAD) g.p[2] = 1.0 / (2.0 * ks.p[1] * (ks.p[0] * ks.p[0]));
-  if (ks.id == GPRC_SQREXP_ARD)
+  if (ks.id == GPRC_MATERN32) g.p[1] = 3.0 / (ks.p[0] * ks.p[0]);
+  if (ks.id == GPRC_MATERN52) g.p[1] = 5.0 / (ks.p[0] * ks.p[0]);
+  if (is_ard(ks.id))
     for (int k = 0; k < ks.n_params; ++k) g.p[k] = 1.0 / ks.p[k];
   return g;
 }

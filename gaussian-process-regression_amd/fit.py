@@ -20,7 +20,7 @@ What runs where
 Beside the reference-faithful fit() stands an EXACT path (no reference counterpart): `logp_grad` is the log marginal
 likelihood and its true gradient in one native call (gprc_gpr_logp_grad: the noisy K_y = K + noise I, a trace, every
 parameter and the noise), and `optimize` maximises it over log(theta) (and log(noise)) with the same vmmin.  It is what
-makes gammaexp / rationalquadratic searches move and what the d length scales of `sqrexp_ard` need.
+makes gammaexp / rationalquadratic searches move and what the d length scales of `sqrexp_ard`, `matern32_ard` and `matern52_ard` need.
 Classification has the same pair: `logq_grad` is the Laplace log evidence of GPC and its exact gradient (gprc_gpc_logq_grad: the
 mode search of GPC$new, then one contraction), `optimize_gpc` maximises it over log(theta).
 Parity status: unpinned (the reference holds no numeric expectations for fit(); tests/testthat/test-fit.R:12-17 only
@@ -36,7 +36,8 @@ import sys
 import numpy as np
 
 from . import _native as nat
-from .covfunc import CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard
+from .covfunc import (CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
+                      matern32_ard, matern52_ard)
 
 __all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "logq_grad", "optimize_gpc", "cov_dict", "brent_fmin", "vmmin"]
 
@@ -55,8 +56,9 @@ SENTINEL = -10000.0  # R/fit.R:50
 def dens(X, y, noise, name, v, ctx=None):
     """dens(v) of R/fit.R:117-124 for kernel `name` with parameter vector v (in the generic's argument order).
     Raises nat.NotPositiveDefinite when K + noise*I is not positive definite (the reference's stopifnot / chol error).
-    `name` may also be "sqrexp_ard" (v = one length scale per row of X), which is not in cov_dict."""
-    func = cov_dict[name][0] if name in cov_dict else grad_dict[name]
+    `name` may also be a kernel of grad_dict that is not in cov_dict: "sqrexp_ard", "matern32_ard", "matern52_ard" (v = one length
+    scale per row of X), "matern32", "matern52" (v = the length scale)."""
+    func = _kernel_by_name(name)
     Xm = as_points(X)
     y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
     d, n = Xm.shape
@@ -84,7 +86,29 @@ def dens_deriv(X, y, name, v, ctx=None):
 
 
 # kernels of the exact gradient: name -> generic (parameter vectors in the ABI's order: {l}, {l, gamma}, {l, alpha}, {l_1..l_d})
-grad_dict = {"sqrexp": sqrexp, "gammaexp": gammaexp, "rationalquadratic": rationalquadratic, "sqrexp_ard": sqrexp_ard}
+grad_dict = {"sqrexp": sqrexp, "gammaexp": gammaexp, "rationalquadratic": rationalquadratic, "sqrexp_ard": sqrexp_ard,
+             "matern32": matern32, "matern52": matern52, "matern32_ard": matern32_ard, "matern52_ard": matern52_ard}
+
+
+def _kernel_by_name(name):
+    """The generic of a kernel name: one of cov_dict's six or one of grad_dict's."""
+    return cov_dict[name][0] if name in cov_dict else grad_dict[name]
+
+
+def _is_ard(name):
+    return grad_dict[name].kernel_id in nat.ARD_KERNELS
+
+
+def _default_start(name, d):
+    """cov_dict's start values; the kernels outside it: every length scale 1."""
+    if name in cov_dict:
+        return cov_dict[name][2]
+    return np.ones(d if _is_ard(name) else 1)
+
+
+def _func_of(name, par):
+    func = grad_dict[name]
+    return CovFunc(func, {"l": np.array(par)} if _is_ard(name) else func.bind(par, {}))
 
 
 def logp_grad(X, y, noise, name, v, ctx=None):
@@ -153,10 +177,10 @@ def _maximise_over_log(z0, value_and_grad_theta, maxit):
 
 
 def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, value_and_grad=None, ctx=None):
-    """Maximise the log marginal likelihood of kernel `name` ("sqrexp", "gammaexp", "rationalquadratic", "sqrexp_ard")
-    over its parameters, and over the noise when `optimize_noise` and noise > 0, with vmmin on z = log(theta): every
+    """Maximise the log marginal likelihood of kernel `name` (a key of grad_dict: "sqrexp", "gammaexp", "rationalquadratic", "sqrexp_ard",
+    "matern32", "matern52", "matern32_ard", "matern52_ard") over its parameters, and over the noise when `optimize_noise` and noise > 0, with vmmin on z = log(theta): every
     parameter stays positive, and d / dz = theta * d / dtheta.  start: parameter vector (default: cov_dict's start values;
-    ones(d) for sqrexp_ard).  value_and_grad(theta, noise) -> (logp, grad) replaces the native objective (grad: len(theta) + 1,
+    1 for the Matern kernels, ones(d) for the ARD kernels).  value_and_grad(theta, noise) -> (logp, grad) replaces the native objective (grad: len(theta) + 1,
     noise last).  An evaluation that fails (not positive definite, a parameter over- or underflowing) counts as the sentinel
     -10000, as in optim_until_error.  Returns dict(par, noise, value, counts, convergence, func): GPR(X, y, r["noise"],
     r["func"]) is the fitted model; convergence 0: converged, 1: maxit reached (optim's codes)."""
@@ -164,7 +188,7 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
     Xm = as_points(X)
     d = Xm.shape[0]
     if start is None:
-        start = np.ones(d) if name == "sqrexp_ard" else cov_dict[name][2]
+        start = _default_start(name, d)
     theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
     npar = theta0.size
     with_noise = bool(optimize_noise) and noise > 0
@@ -184,13 +208,13 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
     t = np.exp(z)
     par = tuple(float(v) for v in t[:npar])
     return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
-            "convergence": fail, "func": CovFunc(func, {"l": np.array(par)} if name == "sqrexp_ard" else func.bind(par, {}))}
+            "convergence": fail, "func": _func_of(name, par)}
 
 
 def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_grad=None, ctx=None):
     """Maximise the Laplace log evidence of GP classification (y in {-1, +1}) over the parameters of kernel `name` ("sqrexp",
-    "gammaexp", "rationalquadratic", "sqrexp_ard") with vmmin on z = log(theta), exactly as `optimize` does for regression.
-    start: parameter vector (default: cov_dict's start values; ones(d) for sqrexp_ard).  value_and_grad(theta) -> (logq, grad)
+    "gammaexp", "rationalquadratic", "sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard") with vmmin on z = log(theta), exactly as `optimize` does for regression.
+    start: parameter vector (default: cov_dict's start values; 1 for the Matern kernels, ones(d) for the ARD kernels).  value_and_grad(theta) -> (logq, grad)
     replaces the native objective `logq_grad`.  An evaluation that fails (a mode search that does not converge, a parameter
     over- or underflowing) counts as the sentinel -10000.  Returns dict(par, value, counts, convergence, func):
     GPC(X, y, r["func"], reference_stop=False) is the fitted classifier; convergence 0: converged, 1: maxit reached."""
@@ -198,7 +222,7 @@ def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_
     Xm = as_points(X)
     d = Xm.shape[0]
     if start is None:
-        start = np.ones(d) if name == "sqrexp_ard" else cov_dict[name][2]
+        start = _default_start(name, d)
     theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
     if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
         raise ValueError("optimize_gpc: start values must be finite and > 0")
@@ -216,7 +240,7 @@ def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_
     z, fmin, fncount, grcount, fail = _maximise_over_log(np.log(theta0), lambda t: value_and_grad(t.copy()), maxit)
     par = tuple(float(v) for v in np.exp(z))
     return {"par": par, "value": -fmin, "counts": (fncount, grcount), "convergence": fail,
-            "func": CovFunc(func, {"l": np.array(par)} if name == "sqrexp_ard" else func.bind(par, {}))}
+            "func": _func_of(name, par)}
 
 
 def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):

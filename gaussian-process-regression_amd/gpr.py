@@ -13,10 +13,10 @@ import numpy as np
 
 from . import _native as nat
 from .covfunc import (as_points, cov_func, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic,
-                      sqrexp_ard, require_tagged)
+                      sqrexp_ard, matern32, matern52, matern32_ard, matern52_ard, require_tagged)
 
 __all__ = ["GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp", "GPR_rationalquadratic",
-           "GPR_sqrexp_ard"]
+           "GPR_sqrexp_ard", "GPR_matern32", "GPR_matern52", "GPR_matern32_ard", "GPR_matern52_ard"]
 
 
 def _r_num(x) -> str:
@@ -134,7 +134,8 @@ class GPR:
         (pred, dmean, dvar) with pred the n* x 2 array cbind(mean, variance) of predict(X_star), dmean[c, i] = d mean_i / d X_star[c, i]
         and dvar[c, i] = d variance_i / d X_star[c, i], both d x n*.  variance=False skips the second solve and the reversed factor the
         variance's gradient keeps in the model (a second copy of the factor): dvar is None.  Kernels: sqrexp, sqrexp_ard, gammaexp,
-        rationalquadratic; gammaexp at a test point equal to a training point takes that pair's contribution as 0."""
+        rationalquadratic, matern32, matern52, matern32_ard, matern52_ard; gammaexp at a test point equal to a training point takes that
+        pair's contribution as 0 (the Matern kernels need no such convention: that pair's term is an exact 0)."""
         d = self._X.shape[0]
         Xs = np.asarray(X_star)
         if Xs.dtype.kind not in "fiub" or Xs.size % d:
@@ -374,6 +375,42 @@ class GPR_sqrexp_ard(GPR):
         super().__init__(X, y, noise, cov_func(sqrexp_ard, l=l), **kw)
 
 
+class _GPR_matern(GPR):
+    """Shared constructor of the four Matern classes: `generic` is the kernel; l = None: every length scale 1."""
+    generic = None
+
+    def __init__(self, X, y, noise, l=None, **kw):
+        d = as_points(np.asarray(X)).shape[0] if self.generic.kernel_id in nat.ARD_KERNELS else 1
+        if l is None:
+            l = np.ones(d)
+        if _len(l) != d:
+            raise ValueError("length(l) == nrow(X) is not TRUE" if self.generic.kernel_id in nat.ARD_KERNELS else "length(l) == 1 is not TRUE")
+        super().__init__(X, y, noise, cov_func(self.generic, l=l), **kw)
+
+
+class GPR_matern32(_GPR_matern):
+    """GPR with the Matern 3/2 kernel (1 + a) exp(-a), a = sqrt(3) |x - y| / l; l = None: 1
+    (fit.optimize(X, y, noise, "matern32") learns it).  No reference counterpart."""
+    generic = matern32
+
+
+class GPR_matern52(_GPR_matern):
+    """GPR with the Matern 5/2 kernel (1 + a + a^2 / 3) exp(-a), a = sqrt(5) |x - y| / l; l = None: 1.  No reference counterpart."""
+    generic = matern52
+
+
+class GPR_matern32_ard(_GPR_matern):
+    """GPR with the ARD Matern 3/2 kernel: a = sqrt(3 sum_k ((x_k - y_k) / l_k)^2); l = None: every length scale 1
+    (fit.optimize(X, y, noise, "matern32_ard") learns them).  No reference counterpart."""
+    generic = matern32_ard
+
+
+class GPR_matern52_ard(_GPR_matern):
+    """GPR with the ARD Matern 5/2 kernel: a = sqrt(5 sum_k ((x_k - y_k) / l_k)^2); l = None: every length scale 1
+    (the standard prior of Bayesian optimisation; fit.optimize(X, y, noise, "matern52_ard") learns them).  No reference counterpart."""
+    generic = matern52_ard
+
+
 # `GPR.sqrexp$new(...)` reads `GPR.sqrexp.new(...)` here
 GPR.constant = GPR_constant
 GPR.linear = GPR_linear
@@ -382,3 +419,7 @@ GPR.sqrexp = GPR_sqrexp
 GPR.gammaexp = GPR_gammaexp
 GPR.rationalquadratic = GPR_rationalquadratic
 GPR.sqrexp_ard = GPR_sqrexp_ard
+GPR.matern32 = GPR_matern32
+GPR.matern52 = GPR_matern52
+GPR.matern32_ard = GPR_matern32_ard
+GPR.matern52_ard = GPR_matern52_ard

@@ -54,7 +54,14 @@ extern "C" {
  *   GPRC_SQREXP       params = {l}               R/GPRclass.R:394
  *   GPRC_GAMMAEXP     params = {l, gamma}        R/GPRclass.R:398
  *   GPRC_RATQUAD      params = {l, alpha}        R/GPRclass.R:402
- *   GPRC_SQREXP_ARD   params = l[d], every l_k > 0: exp(-1/2 sum_k ((x_k - y_k) / l_k)^2)   (no reference counterpart; d <= 256) */
+ *   GPRC_SQREXP_ARD   params = l[d], every l_k > 0: exp(-1/2 sum_k ((x_k - y_k) / l_k)^2)   (no reference counterpart; d <= 256)
+ * Matern kernels (no reference counterpart either).  With r = |x - y| and a = sqrt(3) r / l (3/2) or sqrt(5) r / l (5/2); the ARD forms
+ * take r / l -> sqrt(sum_k ((x_k - y_k) / l_k)^2).  Every length scale finite and > 0; ARD: n_params == d <= 256.
+ *   GPRC_MATERN32     params = {l}               (1 + a) exp(-a)
+ *   GPRC_MATERN52     params = {l}               (1 + a + a^2 / 3) exp(-a)
+ *   GPRC_MATERN32_ARD params = l[d]              as GPRC_MATERN32
+ *   GPRC_MATERN52_ARD params = l[d]              as GPRC_MATERN52
+ * nu = 1/2 has no id of its own: it is GPRC_GAMMAEXP {l, 1}, exp(-r / l), which the fill forms from one square root and one exp. */
 typedef enum {
   GPRC_CONSTANT = 0,
   GPRC_LINEAR = 1,
@@ -62,7 +69,11 @@ typedef enum {
   GPRC_SQREXP = 3,
   GPRC_GAMMAEXP = 4,
   GPRC_RATQUAD = 5,
-  GPRC_SQREXP_ARD = 6
+  GPRC_SQREXP_ARD = 6,
+  GPRC_MATERN32 = 7,
+  GPRC_MATERN52 = 8,
+  GPRC_MATERN32_ARD = 9,
+  GPRC_MATERN52_ARD = 10
 } gprc_kernel_id;
 
 typedef enum {
@@ -142,7 +153,8 @@ GPRC_API int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, 
  *   d logp / d theta = 1/2 sum_ij (alpha_i alpha_j - (K_y^-1)_ij) dK_y,ij / d theta,   K_y = K + noise * I,  alpha = K_y^-1 y
  * (no reference counterpart: R/fit.R:126-139 and gprc_fit_gradient above keep the reference's form).
  * grad_out: n_params + 1 doubles in HOST memory: d logp / d params[i] in the ABI's parameter order
- * (GPRC_SQREXP {l}; GPRC_GAMMAEXP {l, gamma}; GPRC_RATQUAD {l, alpha}; GPRC_SQREXP_ARD {l_1..l_d}),
+ * (GPRC_SQREXP {l}; GPRC_GAMMAEXP {l, gamma}; GPRC_RATQUAD {l, alpha}; GPRC_SQREXP_ARD {l_1..l_d}; GPRC_MATERN32, GPRC_MATERN52 {l};
+ * GPRC_MATERN32_ARD, GPRC_MATERN52_ARD {l_1..l_d}),
  * then d logp / d noise (noise enters as K + noise * I, un-squared, R/GPRclass.R:139).
  * gammaexp's d/d gamma takes u log(r / l) = 0 at r = 0 (the limit, not the reference's NaN).
  * The whole of L^-1 and of K_y^-1 is held on the device: 2 * gprc_pad(n)^2 doubles of the context's workspace
@@ -163,7 +175,8 @@ GPRC_API int gprc_gpr_predict(gprc_model* model, const double* X_star, int64_t n
  * gprc_gpr_predict(pointwise = 1) returns; dmean_out, dvar_out: d x n_star column-major (X_star's layout).  Each of the four may be
  * NULL (not all): without dvar_out the second solve is skipped, without var_out as well the first one too -- the mean's gradient alone
  * is one pass over the pairs.  All pointers host or device, as gprc_gpr_predict.  Results do not depend on the chunking, bit for bit.
- * Kernels: GPRC_SQREXP, GPRC_SQREXP_ARD, GPRC_GAMMAEXP, GPRC_RATQUAD.  gammaexp at a test point that EQUALS a training point (r = 0):
+ * Kernels: GPRC_SQREXP, GPRC_SQREXP_ARD, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_MATERN32, GPRC_MATERN52, GPRC_MATERN32_ARD, GPRC_MATERN52_ARD
+ * (the Matern derivatives hold no 1 / r: a test point on a training point contributes an exact 0 without a convention).  gammaexp at a test point that EQUALS a training point (r = 0):
  * that pair contributes 0 -- the limit for gamma > 1, a convention for gamma <= 1, where the kernel is not differentiable there.
  * MEMORY: the variance's gradient needs W = V L^-1, which the row solve (V L^-T only) computes with the REVERSED factor J L^T J.  It is
  * built by the first call that passes dvar_out and kept in the model: a second copy of the factor and of its block inverses,
@@ -224,7 +237,8 @@ GPRC_API int gprc_gpc_get_logq(gprc_model* model, double* logq_out);
  * reference's sum(diag(L)) (R/GPCclass.R:103) and is no objective.  For a model fitted with the same epsilon and flags = 0:
  *   *logq_out = gprc_gpc_get_logq + sum_i L_ii - sum_i log L_ii.
  * grad_out: n_params doubles in HOST memory, d log q / d params[i] in the ABI's parameter order (GPRC_SQREXP {l}; GPRC_GAMMAEXP
- * {l, gamma}; GPRC_RATQUAD {l, alpha}; GPRC_SQREXP_ARD {l_1..l_d}); explicit and implicit (through f_hat) parts together.  The
+ * {l, gamma}; GPRC_RATQUAD {l, alpha}; GPRC_SQREXP_ARD {l_1..l_d}; GPRC_MATERN32, GPRC_MATERN52 {l}; GPRC_MATERN32_ARD,
+ * GPRC_MATERN52_ARD {l_1..l_d}); explicit and implicit (through f_hat) parts together.  The
  * gradient is that of the converged mode: epsilon = 1e-10 is what the 1e-10 accuracy of the gradient needs (with GPC$new's default
  * 1e-5 the mode can be one Newton step short: 2.6e-9 at n = 3000).  X, y: host or device pointers.
  * The dense K, the factor, L^-1 and B^-1 are held whole on the device: about 3.5 * gprc_pad(n)^2 doubles (GPRC_ERR_NOMEM when that

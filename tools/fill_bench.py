@@ -16,7 +16,9 @@ g = Geometry(n)
 K = torch.zeros(g.packed_size, dtype=torch.float64, device="cuda")
 torch.cuda.synchronize()
 for name, kid, params in (("sqrexp l=1", 3, [1.0]), ("rationalquadratic l=1 alpha=1.5 (rsqrt form)", 5, [1.0, 1.5]), ("rationalquadratic l=1 alpha=1.7 (exp/log form)", 5, [1.0, 1.7]),
-                          ("gammaexp l=1 gamma=1.5", 4, [1.0, 1.5]), ("polynomial sigma=0.5 p=3", 2, [0.5, 3.0]), ("linear sigma=0.7", 1, [0.7])):
+                          ("gammaexp l=1 gamma=1.5", 4, [1.0, 1.5]), ("gammaexp l=1 gamma=1 (sqrt form)", 4, [1.0, 1.0]), ("polynomial sigma=0.5 p=3", 2, [0.5, 3.0]),
+                          ("linear sigma=0.7", 1, [0.7]), ("matern32 l=1", nat.MATERN32, [1.0]), ("matern52 l=1", nat.MATERN52, [1.0]),
+                          ("matern32_ard l_k=1+k/16", nat.MATERN32_ARD, 1.0 + np.arange(d) / 16.0), ("matern52_ard l_k=1+k/16", nat.MATERN52_ARD, 1.0 + np.arange(d) / 16.0)):
     par, pp, npar = nat.params_array(params)
     best = 1e9
     for rep in range(3):
@@ -31,7 +33,9 @@ Xs = torch.from_numpy(np.ascontiguousarray(rng.uniform(-1, 1, (m, d)))).cuda()
 ld = m + 128
 vt = torch.empty(ld * g.n_pad, dtype=torch.float64, device="cuda")
 torch.cuda.synchronize()
-for name, kid, params in (("sqrexp l=1", 3, [1.0]), ("rationalquadratic alpha=1.5", 5, [1.0, 1.5]), ("rationalquadratic alpha=1.7", 5, [1.0, 1.7])):
+for name, kid, params in (("sqrexp l=1", 3, [1.0]), ("rationalquadratic alpha=1.5", 5, [1.0, 1.5]), ("rationalquadratic alpha=1.7", 5, [1.0, 1.7]),
+                          ("gammaexp l=1 gamma=1", 4, [1.0, 1.0]), ("matern32 l=1", nat.MATERN32, [1.0]), ("matern52 l=1", nat.MATERN52, [1.0]),
+                          ("matern32_ard l_k=1+k/16", nat.MATERN32_ARD, 1.0 + np.arange(d) / 16.0), ("matern52_ard l_k=1+k/16", nat.MATERN52_ARD, 1.0 + np.arange(d) / 16.0)):
     par, pp, npar = nat.params_array(params)
     best = 1e9
     for rep in range(3):

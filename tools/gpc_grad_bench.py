@@ -1,7 +1,7 @@
 """gprc_gpc_logq_grad (Laplace log evidence + exact gradient, one call) against the cost of the mode search alone, gprc_gpc_fit
 (flags 0, the same epsilon): the only other way to the gradient is central differences, 2 p mode searches for p parameters.
 d = 8, epsilon 1e-10, X ~ U[-1, 1], y = sign(x_0 - 0.5 x_7 + 0.3 N(0, 1)) (Philox seed 20261016), resident in device memory;
-kernels: sqrexp (l = 1) and sqrexp_ard (l_k = 1 + k / 16).
+kernels: sqrexp (l = 1), sqrexp_ard and matern52_ard (l_k = 1 + k / 16).
     python tools/gpc_grad_bench.py                                   # n = 4096 8192 16384, writes profiles/gpc_logq_grad_bench.txt
     python tools/gpc_grad_bench.py 8192 --parent-lib PATH --out FILE  # gprc_gpc_fit also timed on another build of the library
     python tools/gpc_grad_bench.py --check-gpr FILE                   # dump of gprc_gpr_logp_grad on six fixed cases, nothing else
@@ -97,7 +97,8 @@ def main():
     parent = bind(parent_path) if parent_path else None
     d = 8
     dev = torch.device("cuda:0")
-    kernels = [("sqrexp", nat.SQREXP, np.array([1.0])), ("sqrexp_ard", nat.SQREXP_ARD, 1.0 + np.arange(d) / 16.0)]
+    kernels = [("sqrexp", nat.SQREXP, np.array([1.0])), ("sqrexp_ard", nat.SQREXP_ARD, 1.0 + np.arange(d) / 16.0),
+               ("matern52_ard", nat.MATERN52_ARD, 1.0 + np.arange(d) / 16.0)]
     log = open(out_path, "a")
 
     def emit(rec):

@@ -1,6 +1,7 @@
 """gprc_gpr_logp_grad (value + exact gradient in one call) against the only other way to the same gradient, central differences of
 gprc_gpr_log_marginal: 2 (p + 1) calls for p parameters and the noise.  d = 8, noise 0.1, bench.py's C4 inputs (X ~ U[-1, 1],
-y = 0.1 sum(x^3) + N(0, 0.1^2), Philox seed 20261004), resident in device memory; kernels: sqrexp_ard (l_k = 1 + k / 16) and sqrexp (l = 1).
+y = 0.1 sum(x^3) + N(0, 0.1^2), Philox seed 20261004), resident in device memory; kernels: sqrexp_ard and matern52_ard
+(l_k = 1 + k / 16), sqrexp and matern52 (l = 1).
     python tools/grad_bench.py                         # n = 4096 8192 16384 32768
     python tools/grad_bench.py 16384 --once            # one logp_grad call per kernel, nothing else (the run to put under rocprofv3)
 Per (n, kernel) one JSON line: logp_grad_ms = median of 5 calls after a warm-up (host clock around the synchronous C-ABI call);
@@ -50,7 +51,8 @@ def main():
     ctx = nat.default_context().handle
     d, noise = 8, 0.1
     dev = torch.device("cuda:0")
-    kernels = [("sqrexp_ard", nat.SQREXP_ARD, 1.0 + np.arange(d) / 16.0), ("sqrexp", nat.SQREXP, np.array([1.0]))]
+    kernels = [("sqrexp_ard", nat.SQREXP_ARD, 1.0 + np.arange(d) / 16.0), ("sqrexp", nat.SQREXP, np.array([1.0])),
+               ("matern52_ard", nat.MATERN52_ARD, 1.0 + np.arange(d) / 16.0), ("matern52", nat.MATERN52, np.array([1.0]))]
     for n in sizes:
         Xh, yh = synth(n, d)
         X, y = torch.from_numpy(Xh).to(dev), torch.from_numpy(yh).to(dev)

@@ -1,7 +1,7 @@
 """gprc_gpr_predict_grad (mean, variance and both gradients with respect to the test points) against gprc_gpr_predict(pointwise = 1),
 the call it extends: by flop count two m n^2 solves instead of one plus three bandwidth-bound passes.  d = 8, noise 0.1, n* = n,
 bench.py's C4 inputs (X ~ U[-1, 1], y = 0.1 sum(x^3) + N(0, 0.1^2), Philox seed 20261004), everything resident in device memory;
-kernels: sqrexp (l = 1) and sqrexp_ard (l_k = 1 + k / 16).
+kernels: sqrexp (l = 1), sqrexp_ard and matern52_ard (l_k = 1 + k / 16).
     python tools/predict_grad_bench.py                              # n = 4096 16384
     python tools/predict_grad_bench.py 16384 --parent-lib PATH      # gprc_gpr_predict also timed on another build of the library
     python tools/predict_grad_bench.py 4096 --out FILE              # where the JSON lines are appended (default profiles/predict_grad_bench.txt)
@@ -69,7 +69,8 @@ def main():
     parent = bind(parent_path) if parent_path else None
     d, noise = 8, 0.1
     dev = torch.device("cuda:0")
-    kernels = [("sqrexp", nat.SQREXP, np.array([1.0])), ("sqrexp_ard", nat.SQREXP_ARD, 1.0 + np.arange(d) / 16.0)]
+    kernels = [("sqrexp", nat.SQREXP, np.array([1.0])), ("sqrexp_ard", nat.SQREXP_ARD, 1.0 + np.arange(d) / 16.0),
+               ("matern52_ard", nat.MATERN52_ARD, 1.0 + np.arange(d) / 16.0)]
     log = open(out_path, "a")
 
     def emit(rec):
