@@ -229,6 +229,15 @@ int launch_gpc_class_prob(hipStream_t s, const double* fs, const double* vf, dou
 // negBinv = -B^-1 (n_pad x n_pad, ld) and d3_i = W_i (2 pi_i - 1); zero in the padding.  W_i cancels: 1/2 (1 + negBinv_ii) (2 pi_i - 1)
 int launch_gpc_s2(hipStream_t s, const double* f, const double* negBinv, int64_t ld, int64_t n, double* s2);
 int launch_diag_log_sum(hipStream_t s, const double* packed, int64_t n_pad, int64_t n, double* out);              // sum(log(diag(L)))
+// leave-one-out cross-validation (gprc_gpr_loo, gprc_gpr_loo_grad).  launch_loo_point: per point i < n the LOO mean, variance and log
+// density from alpha and p_i = (K_y^-1)_ii (pdiag, or the diagonal of negKinv = -K_y^-1 with leading dimension ld: exactly one of the
+// two); null outputs are skipped; w, sc, mask (all three or none, n_pad entries, zero in the padding): alpha_i / p_i, sqrt(c_i), 1
+int launch_loo_point(hipStream_t s, const double* alpha, const double* y, const double* pdiag, const double* negKinv, int64_t ld, int64_t n,
+                     int64_t n_pad, double* mean, double* var, double* ell, double* w, double* sc, double* mask);
+// Q = P diag(sc), the full n_pad x n_pad matrix (ld n_pad), from the lower 128-tiles of negP = -P (ld n_pad); bandwidth-bound
+int launch_loo_q(hipStream_t s, const double* negP, const double* sc, int64_t n_pad, double* Q);
+// out[i] = u_i alpha_i + 1/2 S_ii, i < n: the terms of d LOO / d noise
+int launch_loo_noise_terms(hipStream_t s, const double* u, const double* alpha, const double* S, int64_t ld, int64_t n, double* out);
 // sampling support (kernels_eig.hip)
 int launch_pack_dense(hipStream_t s, const double* A, int64_t lda, int64_t m, int64_t n_pad, double* packed);
 int launch_sym_copy(hipStream_t s, const double* A, int64_t lda, int64_t m, double* W, double* V);

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "gprc_host.h"
+#include "host_sums.h"
 #include "pair_tile.h"
 
 namespace gprc {
@@ -502,6 +503,29 @@ int predict_entry(gprc_model* m, int type, const char* not_type, const char* bad
   return finish_sync(s, a, &b);
 }
 
+// diag((L L^T)^-1) of a factored model, kinv_i = sum_k (L^-1)_ki^2 for i < n (kinv: n_pad doubles; entries past n may be written): the
+// rows of the identity go through the predict's solve in its triangular form, chunk by chunk (n^3 / 3 over all chunks; GPRC_FITGRAD_DENSE=1:
+// the dense n^3 form), the panel solves leave the per-block sums of squares and launch_sum_partials adds them in block order.  No n^2
+// buffer beyond the chunk; a row's arithmetic depends on columns only, so the result does not depend on the chunking, bit for bit.
+// Shared by gprc_fit_gradient and gprc_gpr_loo.
+int inverse_diagonal(gprc_model* m, double* kinv) {
+  gprc_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n, n_pad = m->n_pad;
+  int64_t rows = 0;
+  double *vt = nullptr, *red = nullptr, *unused = nullptr;
+  GPRC_TRY(chunk_workspace(ctx, n_pad, n, false, &rows, &vt, &red, &unused));
+  for (int64_t s0 = 0; s0 < n; s0 += rows) {
+    const int64_t mcur = std::min<int64_t>(rows, n - s0), m_pad = pad_up(mcur, 128);
+    GPRC_TRY(launch_set_identity_rows(s, vt, m_pad, m_pad, n_pad, s0));
+    const bool dense = identity_solve_dense();
+    if (!dense) GPRC_HIP(hipMemsetAsync(red, 0, sizeof(double) * (size_t)(m_pad * (n_pad / NBI)), s));
+    GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, m_pad, m_pad, red, dense ? -1 : s0));
+    GPRC_TRY(launch_sum_partials(s, red, n_pad / NBI, m_pad, m_pad, nullptr, kinv + s0));  // writes m_pad entries: kinv has n_pad
+  }
+  return 0;
+}
+
 // The reversed factor of a model (kernels_vec.hip, reverse_factor_kernel), built on the first call that needs it and kept
 int ensure_reversed_factor(gprc_model* m) {
   if (m->packed_rev && m->winv_rev) return 0;
@@ -572,19 +596,7 @@ int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, int n_par
   DevMem kinv, S;
   GPRC_TRY(kinv.alloc(n_pad));
   GPRC_TRY(S.alloc(2 * n));
-  // diag(K^-1): rows of L^-T, chunk by chunk
-  int64_t rows = 0;
-  double *vt = nullptr, *red = nullptr, *unused = nullptr;
-  GPRC_TRY(chunk_workspace(ctx, n_pad, n, false, &rows, &vt, &red, &unused));
-  for (int64_t s0 = 0; s0 < n; s0 += rows) {
-    const int64_t mcur = std::min<int64_t>(rows, n - s0), m_pad = pad_up(mcur, 128);
-    GPRC_TRY(launch_set_identity_rows(s, vt, m_pad, m_pad, n_pad, s0));
-    // rows s0.. of the identity: the triangular form of the solve (n^3 / 3 over all chunks; GPRC_FITGRAD_DENSE=1: the dense n^3 form)
-    const bool dense = identity_solve_dense();
-    if (!dense) GPRC_HIP(hipMemsetAsync(red, 0, sizeof(double) * (size_t)(m_pad * (n_pad / NBI)), s));
-    GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, m_pad, m_pad, red, dense ? -1 : s0));
-    GPRC_TRY(launch_sum_partials(s, red, n_pad / NBI, m_pad, m_pad, nullptr, kinv.p + s0));  // writes m_pad entries: kinv has n_pad
-  }
+  GPRC_TRY(inverse_diagonal(m.get(), kinv.p));
   GPRC_TRY(launch_deriv_rowsum(s, kernel, params[0], n_params > 1 ? params[1] : 0.0, m->X, d, n, S.p));
   std::vector<double> ha(n), hk(n), hs(2 * n);
   GPRC_HIP(hipMemcpyAsync(ha.data(), m->alpha, sizeof(double) * n, hipMemcpyDeviceToHost, s));
@@ -622,6 +634,83 @@ int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params, int n_pa
   GPRC_TRY(launch_grad_contract(s, m->ks, m->X, d, n, m->alpha, W, n_pad, part.p));
   GPRC_TRY(grad_from_partials(s, part.p, n_params + 1, kernel, params, n_params, grad_out));   // the last column: the noise variance
   *logp_out = m->logp;
+  return 0;
+}
+
+// Leave-one-out predictions of a fitted model ("Leave-one-out cross-validation"): p = diag(K_y^-1) as
+// gprc_fit_gradient computes it (inverse_diagonal: n^3 / 3, no n^2 buffer), then one elementwise pass; the call only reads the model
+int gprc_gpr_loo(gprc_model* m, double* mean_out, double* var_out, double* logdens_out, double* loo_out) {
+  if (!m || m->type != MODEL_GPR) { set_error("loo: not a GPR model"); return GPRC_ERR_ARG; }
+  if (!mean_out && !var_out && !logdens_out && !loo_out) { set_error("loo: all four outputs are null"); return GPRC_ERR_ARG; }
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("loo: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n, n_pad = m->n_pad;
+  Out om, ov, ol;
+  if (mean_out) GPRC_TRY(om.set(mean_out, n));
+  if (var_out) GPRC_TRY(ov.set(var_out, n));
+  if (logdens_out) GPRC_TRY(ol.set(logdens_out, n));
+  DevMem kinv, ell;
+  GPRC_TRY(kinv.alloc(n_pad));
+  if (loo_out && !logdens_out) GPRC_TRY(ell.alloc(n));
+  double* ell_dev = logdens_out ? ol.dev : ell.p;
+  GPRC_TRY(inverse_diagonal(m, kinv.p));
+  GPRC_TRY(launch_loo_point(s, m->alpha, m->y, kinv.p, nullptr, 0, n, n_pad, om.dev, ov.dev, ell_dev, nullptr, nullptr, nullptr));
+  std::vector<double> hl(loo_out ? (size_t)n : 0);
+  if (loo_out) GPRC_HIP(hipMemcpyAsync(hl.data(), ell_dev, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  if (mean_out) GPRC_TRY(om.finish(s));
+  if (var_out) GPRC_TRY(ov.finish(s));
+  if (logdens_out) GPRC_TRY(ol.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  if (loo_out) *loo_out = sum_in_order(hl.data(), n);
+  return 0;
+}
+
+// The LOO log score and its exact gradient ("Leave-one-out cross-validation"):
+//   fit                    L, alpha                                           as gprc_gpr_log_marginal                    n^3 / 3
+//   W = -P = -K_y^-1       neg_inverse_from_factor (lower, slot 3; slot 0 is free afterwards)                          2 x n^3 / 3
+//   vectors                p = -diag(W): ell, w = alpha / p, sqrt(c); u = P w by the two vector solves with L
+//   Q = P diag(sqrt c)     the full matrix, mirrored through LDS into slot 0 (zero columns in the padding)
+//   S = -Q Q^T             W := 0, then the lower triangle of C -= A B^T on the MFMA tile core                            n^3
+//   contraction            M = u alpha^T + alpha u^T + S is the Laplace form with a = 0, sw = 1, g = alpha, W = S (0 * 0 + (1 * 1) S_ij is exact)
+//   noise                  1/2 sum_i M_ii = sum_i (u_i alpha_i + 1/2 S_ii), summed on the host in index order
+int gprc_gpr_loo_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                      const double* y, double noise, double* loo_out, double* grad_out) {
+  if (!loo_out || !grad_out) { set_error("loo_grad: null output"); return GPRC_ERR_ARG; }
+  GPRC_TRY(check_grad_kernel("loo_grad", kernel));
+  ModelPtr m;
+  GPRC_TRY(gpr_fit_once(ctx, kernel, params, n_params, X, d, n, y, noise, m));
+  hipStream_t s = ctx->stream;
+  const int64_t n_pad = m->n_pad;
+  double *W = nullptr, *Q = nullptr;
+  const auto nomem = [&] {
+    return "loo_grad: (K + noise I)^-1 and its column-scaled full copy are held whole, 2 x " + std::to_string(n_pad) + "^2 doubles (" +
+           std::to_string((2 * n_pad * n_pad * (int64_t)sizeof(double)) >> 20) + " MiB) of device memory, which could not be allocated";
+  };
+  GPRC_TRY(neg_inverse_from_factor(ctx, n_pad, m.get(), nomem, &W));
+  GPRC_TRY(ws_get(ctx, 0, n_pad * n_pad, &Q));   // L^-T has been consumed
+  DevMem vec, inv, part;
+  GPRC_TRY(vec.alloc(5 * n_pad));
+  GPRC_TRY(inv.alloc(gprc_solve_inv_size(n_pad)));
+  GPRC_TRY(part.alloc(grad_partial_rows() * n_params));
+  double *u = vec.p, *sc = vec.p + n_pad, *one = vec.p + 2 * n_pad, *zero = vec.p + 3 * n_pad, *terms = vec.p + 4 * n_pad;
+  GPRC_HIP(hipMemsetAsync(zero, 0, sizeof(double) * (size_t)(2 * n_pad), s));   // and the terms' tail
+  GPRC_TRY(launch_loo_point(s, m->alpha, m->y, nullptr, W, n_pad, n, n_pad, nullptr, nullptr, terms, u, sc, one));   // terms: ell for now
+  std::vector<double> he((size_t)n), ht((size_t)n);
+  GPRC_HIP(hipMemcpyAsync(he.data(), terms, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  GPRC_TRY(launch_inv512(s, m->packed, n_pad, m->winv, inv.p, 0, n_pad / NB));
+  GPRC_TRY(launch_trsv(s, m->packed, inv.p, n_pad, u, 0, m->work));   // u = L^-T L^-1 w
+  GPRC_TRY(launch_trsv(s, m->packed, inv.p, n_pad, u, 1, m->work));
+  GPRC_TRY(launch_loo_q(s, W, sc, n_pad, Q));
+  GPRC_HIP(hipMemsetAsync(W, 0, sizeof(double) * (size_t)(n_pad * n_pad), s));
+  GPRC_TRY(launch_gemm_nt(s, W, n_pad, Q, n_pad, Q, n_pad, n_pad, n_pad, n_pad, 1, PK_COV_SYRK));   // S = -Q Q^T (lower)
+  GPRC_TRY(launch_loo_noise_terms(s, u, m->alpha, W, n_pad, n, terms));
+  GPRC_HIP(hipMemcpyAsync(ht.data(), terms, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  GPRC_TRY(launch_gpc_grad_contract(s, m->ks, m->X, d, n, zero, one, u, m->alpha, W, n_pad, part.p));
+  GPRC_TRY(grad_from_partials(s, part.p, n_params, kernel, params, n_params, grad_out));   // synchronises: he and ht have arrived
+  grad_out[n_params] = sum_in_order(ht.data(), n);
+  *loo_out = sum_in_order(he.data(), n);
   return 0;
 }
 

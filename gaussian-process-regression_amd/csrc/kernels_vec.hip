@@ -626,6 +626,71 @@ __global__ __launch_bounds__(256) void reverse_cols_kernel(double* vt, int64_t l
   }
 }
 
+// ---- leave-one-out cross-validation ("Leave-one-out cross-validation") ------------------------------------
+// Point i of a fitted GPR from alpha = K_y^-1 y and p_i = (K_y^-1)_ii (pdiag[i], or -negKinv[i + i ld] when pdiag is null):
+//   mean_i = y_i - alpha_i / p_i,   var_i = 1 / p_i,   ell_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log 2 pi       (i < n only)
+// and what the gradient goes on with, n_pad entries each, zero in the padding: w_i = alpha_i / p_i, sc_i = sqrt(c_i) =
+// sqrt(p_i + alpha_i^2) / p_i, mask_i = 1.  Null outputs are not written; nothing but w, sc and mask is written for i >= n.
+__global__ __launch_bounds__(256) void loo_point_kernel(const double* alpha, const double* y, const double* pdiag, const double* negKinv, int64_t ld,
+                                                        int64_t n, int64_t n_pad, double* mean, double* var, double* ell, double* w, double* sc,
+                                                        double* mask) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pad) return;
+  if (i >= n) {
+    if (w) { w[i] = 0.0; sc[i] = 0.0; mask[i] = 0.0; }
+    return;
+  }
+  const double p = pdiag ? pdiag[i] : -negKinv[i + i * ld], a = alpha[i], r = a / p;
+  if (mean) mean[i] = y[i] - r;
+  if (var) var[i] = 1.0 / p;
+  if (ell) ell[i] = 0.5 * log(p) - 0.5 * (a * r) - 0.9189385332046727;   // 1/2 log(2 pi)
+  if (w) { w[i] = r; sc[i] = sqrt(p + a * a) / p; mask[i] = 1.0; }
+}
+
+// Q[i, k] = P[max(i, k), min(i, k)] sc_k with P = -negP, of which only the lower 128 x 128 tiles (the diagonal ones whole) are valid:
+// the full n_pad x n_pad matrix P diag(sc), one 64 x 64 tile per workgroup.  A tile of the lower part is copied down its columns; a tile
+// above it takes the mirror tile of negP, read down ITS columns (16 bytes a lane), turned in LDS (rows padded to 65 doubles) and
+// written down Q's columns (16 bytes a lane), as reverse_factor_kernel.  Consecutive workgroups go down a column of tiles.
+__global__ __launch_bounds__(256) void loo_q_kernel(const double* __restrict__ negP, const double* __restrict__ sc, int64_t n_pad,
+                                                    double* __restrict__ Q) {
+  __shared__ double S[RV_T][RV_T + 1];   // S[column of the source tile][its row]
+  const int64_t i0 = (int64_t)blockIdx.x * RV_T, k0 = (int64_t)blockIdx.y * RV_T;
+  const int t = threadIdx.x;
+  double* dst = Q + i0 + k0 * n_pad;
+  if ((i0 >> 7) >= (k0 >> 7)) {
+    const double* src = negP + i0 + k0 * n_pad;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int idx = t + 256 * k, a = 2 * (idx & 31), b = idx >> 5;
+      const double2 v = *reinterpret_cast<const double2*>(src + a + b * n_pad);
+      const double f = -sc[k0 + b];
+      *reinterpret_cast<double2*>(dst + a + b * n_pad) = make_double2(v.x * f, v.y * f);
+    }
+    return;
+  }
+  const double* src = negP + k0 + i0 * n_pad;   // rows k0.., columns i0.. of the lower part
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int idx = t + 256 * k, rp = idx & 31, col = idx >> 5;
+    const double2 v = *reinterpret_cast<const double2*>(src + 2 * rp + col * n_pad);
+    S[col][2 * rp] = v.x;
+    S[col][2 * rp + 1] = v.y;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int idx = t + 256 * k, a = 2 * (idx & 31), b = idx >> 5;   // rows a, a + 1 and column b of the tile of Q
+    const double f = -sc[k0 + b];
+    *reinterpret_cast<double2*>(dst + a + b * n_pad) = make_double2(S[a][b] * f, S[a + 1][b] * f);
+  }
+}
+
+// the terms of d LOO / d noise = sum_i (u_i alpha_i + 1/2 S_ii), i < n; the host sums them in index order
+__global__ __launch_bounds__(256) void loo_noise_terms_kernel(const double* u, const double* alpha, const double* S, int64_t ld, int64_t n, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = fma(u[i], alpha[i], 0.5 * S[i + i * ld]);
+}
+
 inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -800,6 +865,29 @@ int launch_gpc_grad(hipStream_t s, const double* f, const double* y, int64_t n, 
 int launch_gpc_s2(hipStream_t s, const double* f, const double* negBinv, int64_t ld, int64_t n, double* s2) {
   const int64_t n_pad = pad_up(n, NB);
   hipLaunchKernelGGL(gpc_s2_kernel, dim3(blocks(n_pad, 256)), dim3(256), 0, s, f, negBinv, ld, n, n_pad, s2);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+int launch_loo_point(hipStream_t s, const double* alpha, const double* y, const double* pdiag, const double* negKinv, int64_t ld, int64_t n,
+                     int64_t n_pad, double* mean, double* var, double* ell, double* w, double* sc, double* mask) {
+  if (!pdiag == !negKinv || !w != !sc || !w != !mask) { set_error("loo_point: one source of the diagonal; w, sc and mask together"); return GPRC_ERR_ARG; }
+  hipLaunchKernelGGL(loo_point_kernel, dim3(blocks(n_pad, 256)), dim3(256), 0, s, alpha, y, pdiag, negKinv, ld, n, n_pad, mean, var, ell, w, sc, mask);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+int launch_loo_q(hipStream_t s, const double* negP, const double* sc, int64_t n_pad, double* Q) {
+  if (n_pad <= 0 || n_pad % NBI || n_pad / RV_T > 65535) { set_error("loo_q: n_pad must be a positive multiple of 128 below 2^22"); return GPRC_ERR_ARG; }
+  if ((reinterpret_cast<uintptr_t>(negP) | reinterpret_cast<uintptr_t>(Q)) & 15) { set_error("loo_q: the matrices must be 16-byte aligned"); return GPRC_ERR_ARG; }
+  // n_pad^2 elements read (the lower tiles twice, as themselves and as their mirror), n_pad^2 written, one multiplication each; accounted
+  // with the other n^2-sized turn through LDS, the reversed factor (no profiling kind of its own)
+  const double np = (double)n_pad;
+  ProfScope ps(s, PK_REVERSE_FACTOR, np * np, 8.0 * (2.0 * np * np + np));
+  hipLaunchKernelGGL(loo_q_kernel, dim3((unsigned)(n_pad / RV_T), (unsigned)(n_pad / RV_T)), dim3(256), 0, s, negP, sc, n_pad, Q);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+int launch_loo_noise_terms(hipStream_t s, const double* u, const double* alpha, const double* S, int64_t ld, int64_t n, double* out) {
+  hipLaunchKernelGGL(loo_noise_terms_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, u, alpha, S, ld, n, out);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

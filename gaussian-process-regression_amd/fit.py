@@ -39,7 +39,7 @@ from . import _native as nat
 from .covfunc import (CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
                       matern32_ard, matern52_ard)
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "optimize", "logq_grad", "optimize_gpc", "cov_dict", "brent_fmin", "vmmin"]
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "loo_grad", "optimize", "logq_grad", "optimize_gpc", "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
 cov_dict = {
@@ -128,6 +128,24 @@ def logp_grad(X, y, noise, name, v, ctx=None):
     return out.value, g
 
 
+def loo_grad(X, y, noise, name, v, ctx=None):
+    """(loo, grad) of GPR(X, y, noise, name(v)): the leave-one-out log predictive probability (Rasmussen & Williams 5.4.2), what
+    GPR(...).loo_score returns, and its exact gradient, one native call (gprc_gpr_loo_grad).  The twin of `logp_grad`: `v` in the order
+    `dens` takes it; grad has len(v) + 1 entries, d loo / d noise last.  Raises nat.NotPositiveDefinite when K + noise * I is not
+    positive definite."""
+    func = grad_dict[name]
+    Xm = as_points(X)
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    d, n = Xm.shape
+    ctx = ctx or nat.default_context()
+    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    g = np.empty(p.size + 1)
+    out = C.c_double()
+    nat.check(nat.lib().gprc_gpr_loo_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
+                                          C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.value, g
+
+
 def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):
     """(logq, grad) of GP classification with kernel name(v) on (X, y), y in {-1, +1}: the Laplace approximation of the log
     evidence and its exact gradient (explicit part and the part through the mode), one native call (gprc_gpc_logq_grad).
@@ -176,14 +194,19 @@ def _maximise_over_log(z0, value_and_grad_theta, maxit):
     return vmmin(z0, fn, lambda z: -evaluate(z)[1], maxit=maxit)
 
 
-def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, value_and_grad=None, ctx=None):
+def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, value_and_grad=None, ctx=None, objective="logp"):
     """Maximise the log marginal likelihood of kernel `name` (a key of grad_dict: "sqrexp", "gammaexp", "rationalquadratic", "sqrexp_ard",
     "matern32", "matern52", "matern32_ard", "matern52_ard") over its parameters, and over the noise when `optimize_noise` and noise > 0, with vmmin on z = log(theta): every
     parameter stays positive, and d / dz = theta * d / dtheta.  start: parameter vector (default: cov_dict's start values;
     1 for the Matern kernels, ones(d) for the ARD kernels).  value_and_grad(theta, noise) -> (logp, grad) replaces the native objective (grad: len(theta) + 1,
     noise last).  An evaluation that fails (not positive definite, a parameter over- or underflowing) counts as the sentinel
     -10000, as in optim_until_error.  Returns dict(par, noise, value, counts, convergence, func): GPR(X, y, r["noise"],
-    r["func"]) is the fitted model; convergence 0: converged, 1: maxit reached (optim's codes)."""
+    r["func"]) is the fitted model; convergence 0: converged, 1: maxit reached (optim's codes).
+    objective: "logp" (the default) maximises the log marginal likelihood (`logp_grad`), "loo" the leave-one-out log predictive
+    probability (`loo_grad`), the usual choice when the kernel family may be misspecified; anything else raises ValueError.  A
+    `value_and_grad` hook replaces either."""
+    if objective not in ("logp", "loo"):
+        raise ValueError('optimize: objective must be "logp" or "loo"')
     func = grad_dict[name]
     Xm = as_points(X)
     d = Xm.shape[0]
@@ -196,7 +219,8 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
         raise ValueError("optimize: start values must be finite and > 0")
     if value_and_grad is None:
         ctx = ctx or nat.default_context()
-        value_and_grad = lambda theta, nz: logp_grad(Xm, y, nz, name, theta, ctx)   # noqa: E731
+        native = loo_grad if objective == "loo" else logp_grad
+        value_and_grad = lambda theta, nz: native(Xm, y, nz, name, theta, ctx)   # noqa: E731
     z0 = np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0)
 
     def vg(t):

@@ -153,6 +153,21 @@ class GPR:
                                                   dvar.ctypes.data if variance else None))
         return np.column_stack([mean, var]), dmean, dvar
 
+    def loo(self):
+        """Leave-one-out cross-validation in closed form (gprc_gpr_loo; no reference counterpart): the n x 3 array cbind(mean, variance,
+        log density) of the prediction of every y_i from the other n - 1 observations -- predict's convention plus one column.  The
+        variance is that of the NOISY observation (it contains $noise), so (y - mean) / sqrt(variance) are the standardised residuals.
+        Costs about one more fit; works for a model fitted over several devices (rank 0's replica)."""
+        n = self._X.shape[1]
+        mean, var, dens = np.empty(n), np.empty(n), np.empty(n)
+        nat.check(nat.lib().gprc_gpr_loo(self._model, mean.ctypes.data, var.ctypes.data, dens.ctypes.data, None))
+        return np.column_stack([mean, var, dens])
+
+    def _loo_score(self):
+        score = C.c_double()
+        nat.check(nat.lib().gprc_gpr_loo(self._model, None, None, None, C.byref(score)))
+        return score.value
+
     def add_data(self, X_new, y_new):
         """Append observations: the model becomes GPR$new(cbind(X, X_new), c(y, y_new), noise = $noise, k) -- same kernel,
         parameters and stored noise (a jitter the fit added is kept, never re-tried) -- without refactoring the whole matrix
@@ -225,6 +240,7 @@ class GPR:
     L = _ReadOnly("L", _get_L)
     alpha = _ReadOnly("alpha", lambda s: s._alpha)
     logp = _ReadOnly("logp", lambda s: s._logp)
+    loo_score = _ReadOnly("loo_score", _loo_score)   # the LOO log predictive probability, sum(loo()[:, 2]); computed when read
 
     def close(self):
         if getattr(self, "_mmodel", None):

@@ -163,6 +163,29 @@ GPRC_API int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, 
  * Other kernel ids: GPRC_ERR_ARG. */
 GPRC_API int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,
                                 int64_t n, const double* y, double noise, double* logp_out, double* grad_out);
+/* Leave-one-out cross-validation of a fitted GPR model in closed form (Rasmussen & Williams 5.4.2; no reference counterpart).  With
+ * K_y = K + noise * I, P = K_y^-1, alpha = P y and p_i = P_ii, the prediction of y_i from the other n - 1 observations is
+ *   mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i,     logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log(2 pi),
+ * and *loo_out = sum_i logdens_i, the LOO log predictive probability.  var_i is the variance of the NOISY observation y_i: it contains
+ * `noise` (gprc_gpr_predict's variance on the other n - 1 points is var_i - noise).  mean_out, var_out, logdens_out: n doubles each,
+ * host or device pointers as gprc_gpr_predict's; loo_out: one double in HOST memory, the sum taken in index order in long double (two
+ * calls give the same bits).  Each of the four may be NULL (not all).  p_i = sum_k (L^-1)_ki^2 comes from the rows of L^-T, chunk by
+ * chunk as gprc_fit_gradient: n^3 / 3 flop, MEMORY: the context's predict chunk, no n^2 buffer -- the call works at every n a fit
+ * works at -- and the results do not depend on the chunking, bit for bit.  The model is only read: every GPR model is accepted, the
+ * borrowed ones (gprc_gpr_model_from_device, gprc_mgpu_model_rank) included, with every kernel id.
+ * GPRC_ERR_ARG: a GPC model, all four outputs NULL. */
+GPRC_API int gprc_gpr_loo(gprc_model* model, double* mean_out, double* var_out, double* logdens_out, double* loo_out);
+/* The LOO log predictive probability of GPR(X, y, noise, kernel(params)), *loo_out as gprc_gpr_loo's, and its exact gradient: with
+ * w_i = alpha_i / p_i, c_i = (p_i + alpha_i^2) / p_i^2, u = P w,
+ *   d LOO / d theta = 1/2 sum_ij M_ij dK_ij / d theta,   M = u alpha^T + alpha u^T - P diag(c) P,     d LOO / d noise = 1/2 sum_i M_ii.
+ * The contract is gprc_gpr_logp_grad's: grad_out: n_params + 1 doubles in HOST memory, d LOO / d params[i] in the ABI's parameter
+ * order, then d LOO / d noise; kernels GPRC_SQREXP, GPRC_GAMMAEXP, GPRC_RATQUAD, GPRC_SQREXP_ARD, GPRC_MATERN32, GPRC_MATERN52,
+ * GPRC_MATERN32_ARD, GPRC_MATERN52_ARD (other ids: GPRC_ERR_ARG); gammaexp's d/d gamma takes u log(r / l) = 0 at r = 0.
+ * MEMORY: P and its column-scaled full copy P diag(sqrt c) are held whole, 2 * gprc_pad(n)^2 doubles of the context's workspace
+ * (GPRC_ERR_NOMEM when that does not fit; gprc_ctx_trim releases it).  About 2 n^3 flop: the fit, the inverse and one n^3 product.
+ * No jitter retry: returns info > 0 (leading minor) when K + noise * I is not positive definite. */
+GPRC_API int gprc_gpr_loo_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,
+                               int64_t n, const double* y, double noise, double* loo_out, double* grad_out);
 /* GPR$predict (R/GPRclass.R:155-170).  X_star is d x n_star.
  * pointwise != 0: mean_out[n_star], var_out[n_star] = k(x*,x*) - colSums(v*v)      (:164-165)
  * pointwise == 0: mean_out[n_star], var_out = n_star x n_star K(X*,X*) - t(v) %*% v (:167-168) */
@@ -432,7 +455,8 @@ GPRC_API int gprc_combine_all(gprc_ctx* ctx, const double* axis_values, const in
  * update (K=512), 6 trsv, 7 row reductions, 8 covariance SYRK, 9 derivative row sums, 10 Jacobi sweep, 11 predict
  * left-looking update, 12 trailing left-looking update, 13 fused panel factorisation, 14 fused in-panel solve of the predict, 15 inverse GEMM
  * (-L^-T L^-1, lower), 16 gradient contraction (gprc_gpr_logp_grad), 17 Laplace gradient contraction (gprc_gpc_logq_grad),
- * 18 factor reversal, 19 prediction-gradient contraction (gprc_gpr_predict_grad).  flops/bytes are the ALGORITHMIC
+ * 18 factor reversal, 19 prediction-gradient contraction (gprc_gpr_predict_grad).  gprc_gpr_loo_grad adds no kind: its n^3 product is
+ * counted under 8, its contraction under 17 and the builder of its scaled full inverse under 18.  flops/bytes are the ALGORITHMIC
  * figures of DESIGN.md for the launches seen, not counter readings. */
 GPRC_API int gprc_prof_enable(int on);
 /* With the environment variable GPRC_PANEL_TRACE=<p> set, the factor role of the fused panel kernel of panel p leaves
