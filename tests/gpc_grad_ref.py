@@ -14,12 +14,12 @@ At the mode f of the Newton iteration, with pi = sigmoid(f), W = pi (1 - pi), sw
 This is the book's per-parameter form on purpose: it shares no algebra with the rank-two form the device contracts
 (`gradient_rank_two` below restates that one, for the CPU test that pins the two against each other).
 The mode search is the device's: from f = 0, stop when |delta objective| < epsilon (absolute), so iteration counts compare.
-Kernels and their derivatives come from tests/ard_grad_ref.py.  Parameter vectors are in the C ABI's order; X is d x n.
+Kernels and their derivatives come from tests/kernel_ref.py.  Parameter vectors are in the C ABI's order; X is d x n.
 """
 import numpy as np
 from scipy.linalg import cholesky, solve_triangular
 
-from ard_grad_ref import kernel, kernel_derivs
+from kernel_ref import kernel, kernel_derivs
 
 
 def sigmoid(x):

@@ -8,39 +8,18 @@ tests/test_gpu_loo.py, written from the formulas below (Rasmussen & Williams 5.4
     M = u alpha^T + alpha u^T - P diag(c) P        dLOO / dtheta = 1/2 sum_ij M_ij dK_ij / dtheta        dLOO / dnoise = 1/2 tr M
 
 Three forms: the closed form in float64 (LAPACK), the same in longdouble (pred_grad_ref's column Cholesky and substitutions), and
-`loo_brute`, which really removes point i and solves the (n - 1)-point problem.  K and dK / dtheta come from the sibling references
-(ard_grad_ref: sqrexp, sqrexp_ard, gammaexp, rationalquadratic; matern_ref: the four Matern kernels); `linear` (values only) is
-sum_k sigma_k x_k y_k.  Parameter vectors are in the C ABI's order; X is d x n (one point per column).
+`loo_brute`, which really removes point i and solves the (n - 1)-point problem.  K and dK / dtheta come from tests/kernel_ref.py (its eight
+gradient kernels; `linear`, values only).  Parameter vectors are in the C ABI's order; X is d x n (one point per column).
 """
 import math
 
 import numpy as np
 
-import ard_grad_ref
-import matern_ref
+from kernel_ref import kernel, kernel_derivs
 from pred_grad_ref import chol, solve_lower
 
 LD = np.longdouble
-GRAD_NAMES = ("sqrexp", "gammaexp", "rationalquadratic", "sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard")
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
-
-
-def kernel(name, theta, X):
-    X = np.asarray(X, dtype=float)
-    if name in matern_ref.NAMES:
-        return matern_ref.kernel(name, theta, X)
-    if name == "linear":
-        sig = np.atleast_1d(np.asarray(theta, dtype=float))
-        sig = np.full(X.shape[0], sig[0]) if sig.size == 1 else sig
-        return (X * sig[:, None]).T @ X
-    return ard_grad_ref.kernel(name, theta, X)
-
-
-def kernel_derivs(name, theta, X, K):
-    X = np.asarray(X, dtype=float)
-    if name in matern_ref.NAMES:
-        return matern_ref.kernel_derivs(name, theta, X, K)
-    return ard_grad_ref.kernel_derivs(name, theta, X, K)
 
 
 def _inverse(Ky):

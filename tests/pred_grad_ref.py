@@ -4,69 +4,16 @@ pointwise variance and their gradients with respect to the test points, written 
     K_y = K + noise I = L L^T,  alpha = K_y^-1 y,  k*_j = k(x*, x_j),  v = L^-1 k*,  w = L^-T v
     mu = k* . alpha                      d mu / d x*_c      =      sum_j alpha_j dk(x*, x_j) / d x*_c
     sigma^2 = k(x*, x*) - v . v          d sigma^2 / d x*_c = -2 sum_j w_j     dk(x*, x_j) / d x*_c
-    dk / d x*_c = -h_j (x*_c - x_jc) t_c,  s = |x* - x_j|^2, r = sqrt(s):
-        sqrexp (l)                 h = k / l^2
-        sqrexp_ard (l_1 .. l_d)    h = k, t_c = 1 / l_c^2
-        gammaexp (l, gamma)        h = k gamma (r / l)^gamma / s;   h = 0 at r = 0
-        rationalquadratic (l, a)   q = 1 + s / (2 a l^2),  h = k / (q l^2)
+    dk / d x*_c = -h_j (x*_c - x_jc) t_c:  k, h and t of every kernel are tests/kernel_ref.py's `pairwise` (the formula table is there)
 
 predict_grad(..., dtype): everything in `dtype` -- numpy.float64 (Cholesky and triangular solves of LAPACK) or numpy.longdouble (the
 column Cholesky and substitutions below).  X: d x n, X_star: d x m, one point per column, as the library takes them.
 """
 import numpy as np
 
+from kernel_ref import pairwise
+
 LD = np.longdouble
-
-# (kernel name, parameters in the ABI's order, d): the cases of the CPU and the GPU tests
-CASES = [
-    ("sqrexp", [0.7], 3),
-    ("sqrexp", [1.5], 8),
-    ("sqrexp_ard", [0.5, 1.5, 3.0], 3),
-    ("gammaexp", [1.2, 1.5], 3),
-    ("gammaexp", [1.2, 1.0], 2),
-    ("rationalquadratic", [0.9, 1.7], 3),
-]
-SIZES = [(300, 0.1), (600, 0.01)]      # (n, noise)
-KERNEL_ID = {"sqrexp": 3, "gammaexp": 4, "rationalquadratic": 5, "sqrexp_ard": 6}   # include/gprc_native.h
-
-
-def case_id(case):
-    name, par, d = case
-    return "%s-%s-d%d" % (name, "_".join("%g" % p for p in par), d)
-
-
-def kernel_and_h(name, par, A, B, dtype):
-    """(k, h, t): k[i, j] = k(A[:, i], B[:, j]), h as above, t the d per-coordinate factors; everything in dtype"""
-    A, B = np.asarray(A, dtype=dtype), np.asarray(B, dtype=dtype)
-    par = [dtype(p) for p in par]
-    d = A.shape[0]
-    diff = A[:, :, None] - B[:, None, :]                  # d x m x n
-    one, two = dtype(1), dtype(2)
-    if name == "sqrexp_ard":
-        l = np.asarray(par, dtype=dtype)
-        s = ((diff / l[:, None, None]) ** 2).sum(0)
-        k = np.exp(-s / two)
-        return k, k, one / (l * l)
-    s = (diff * diff).sum(0)
-    t = np.ones(d, dtype=dtype)
-    if name == "sqrexp":
-        l = par[0]
-        k = np.exp(-s / (two * l * l))
-        return k, k / (l * l), t
-    if name == "gammaexp":
-        l, g = par
-        r = np.sqrt(s)
-        u = (r / l) ** g
-        k = np.exp(-u)
-        zero = s == 0
-        h = np.where(zero, dtype(0), k * g * u / np.where(zero, one, s))
-        return k, h, t
-    if name == "rationalquadratic":
-        l, al = par
-        q = one + s / (two * al * l * l)
-        k = q ** (-al)
-        return k, k / (q * l * l), t
-    raise ValueError(name)
 
 
 def chol(A):
@@ -102,7 +49,7 @@ def solve_lower(L, B, transpose=False):
 def fit(name, par, X, y, noise, dtype=np.float64):
     """(L, alpha) of K + noise I in dtype"""
     X = np.asarray(X, dtype=dtype)
-    K = kernel_and_h(name, par, X, X, dtype)[0] + dtype(noise) * np.eye(X.shape[1], dtype=dtype)
+    K = pairwise(name, par, X, X, dtype)[0] + dtype(noise) * np.eye(X.shape[1], dtype=dtype)
     L = chol(K)
     yv = np.asarray(y, dtype=dtype).reshape(-1, 1)
     alpha = solve_lower(L, solve_lower(L, yv), transpose=True)[:, 0]
@@ -111,17 +58,24 @@ def fit(name, par, X, y, noise, dtype=np.float64):
 
 def mean_var(name, par, X, L, alpha, Xs, dtype=np.float64):
     """(mean, var) at the test points alone (what the central differences difference)"""
-    ks = kernel_and_h(name, par, Xs, X, dtype)[0]        # m x n
+    ks = pairwise(name, par, Xs, X, dtype)[0]        # m x n
     v = solve_lower(L, ks.T)                               # n x m
-    kss = np.ones(ks.shape[0], dtype=dtype)                # k(x*, x*) = 1 for the four stationary kernels
+    kss = np.ones(ks.shape[0], dtype=dtype)                # k(x*, x*) = 1 for the eight stationary kernels
     return ks @ alpha, kss - (v * v).sum(0)
+
+
+def predict_cov(name, par, X, L, alpha, Xs, dtype=np.float64):
+    """(mean, full posterior covariance) at the test points"""
+    ks = pairwise(name, par, Xs, X, dtype)[0]
+    v = solve_lower(L, ks.T)
+    return ks @ alpha, pairwise(name, par, Xs, Xs, dtype)[0] - v.T @ v
 
 
 def predict_grad(name, par, X, y, noise, Xs, dtype=np.float64, factor=None):
     """(mean[m], var[m], dmean[d, m], dvar[d, m]) in dtype; factor: (L, alpha) of fit() to reuse"""
     X, Xs = np.asarray(X, dtype=dtype), np.asarray(Xs, dtype=dtype)
     L, alpha = factor if factor is not None else fit(name, par, X, y, noise, dtype)
-    ks, h, t = kernel_and_h(name, par, Xs, X, dtype)      # m x n
+    ks, h, t = pairwise(name, par, Xs, X, dtype)      # m x n
     v = solve_lower(L, ks.T)                               # n x m
     w = solve_lower(L, v, transpose=True)                  # n x m: K_y^-1 k*
     mean = ks @ alpha

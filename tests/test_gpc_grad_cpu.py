@@ -11,23 +11,16 @@ import gpc_grad_ref as ref
 from conftest import ROOT, nerr
 from gprc_amd import _native as nat
 from gprc_amd.fit import optimize_gpc
+from gpu_calls import gpc_problem
 
 CASES = [("sqrexp", [0.8], 300, 2), ("gammaexp", [0.9, 1.5], 300, 2), ("gammaexp", [1.2, 1.0], 600, 3),
          ("rationalquadratic", [1.1, 1.7], 600, 3), ("sqrexp_ard", [0.8, 1.9], 300, 2), ("sqrexp_ard", [0.8, 1.1, 1.9], 600, 3)]
 
 
-def problem(n, d, seed):
-    rng = np.random.default_rng(seed)
-    X = rng.uniform(-1, 1, (d, n))
-    y = np.sign(X[0] - 0.5 * X[d - 1] + 0.3 * rng.normal(size=n))
-    y[y == 0] = 1.0
-    return X, y
-
-
 @pytest.mark.parametrize("name,theta,n,d", CASES)
 def test_reference_gradient_against_differences_of_its_own_log_q(name, theta, n, d):
     """normwise <= 1e-6 with a relative step of 1e-5 (measured: <= 9e-10).  With the book's printed sign of s2 the error is 3-15 %."""
-    X, y = problem(n, d, 7000 + n + d)
+    X, y = gpc_problem(n, d)
     theta = np.array(theta)
     _, grad, iters, _ = ref.logq_grad(name, theta, X, y)
     assert iters < 50
@@ -45,7 +38,7 @@ def test_reference_gradient_against_differences_of_its_own_log_q(name, theta, n,
 def test_rank_two_form_equals_the_per_parameter_form(name, theta, n, d):
     """sum_ij M_ij dK_ij, M = 1/2 (a a^T - R) + 1/2 (u g^T + g u^T), is the algebra the device kernel implements: <= 1e-12
     against the book's s1 + s2.s3 (measured: <= 2e-15)."""
-    X, y = problem(n, d, 7000 + n + d)
+    X, y = gpc_problem(n, d)
     _, grad, _, _ = ref.logq_grad(name, theta, X, y)
     st = ref.laplace_state(name, theta, X, y, 1e-10)
     err = nerr(ref.gradient_rank_two(name, theta, X, st), grad)

@@ -1,34 +1,25 @@
 """Exact marginal-likelihood gradient (gprc_gpr_logp_grad) and the ARD squared exponential on the MI355X.
 
 ARD values and models against the CPU oracle's isotropic squared exponential on the scaled inputs X / l (the fills' 1e-13 and the
-north-star 1e-10 gates); the gradient against the numpy float64 closed form of tests/ard_grad_ref.py (1e-10 normwise) and against
-central differences of the library's own gprc_gpr_log_marginal (1e-6); pointer kinds, determinism, errors; fit.optimize end to end.
+north-star 1e-10 gates); the gradient of every kernel of fit.grad_dict against the numpy float64 closed form of tests/ard_grad_ref.py
+(1e-10 normwise) and against central differences of the library's own gprc_gpr_log_marginal (1e-6); pointer kinds, determinism, errors;
+fit.optimize end to end.
 
-Every gradient case asserts that the oracle's fit of it succeeds at the FIRST attempt: no case tests a jittered matrix.
+Every gradient case of a kernel the oracle has asserts that the oracle's fit of it succeeds at the FIRST attempt; the oracle has no Matern
+kernel, and there numpy's Cholesky of K_y as it stands is the precondition (it raises).  No case tests a jittered matrix.
 """
-import ctypes as C
-import faulthandler
-
 import numpy as np
 import pytest
 
-import ard_grad_ref as ref
 from conftest import TOL, nerr
 from gprc_amd import (GPC, GPR, GPR_sqrexp_ard, GprcError, NotPositiveDefinite, cov_func, covariance_matrix, sqrexp, sqrexp_ard)
 from gprc_amd import _native as nat
+from case_checks import check_logp_grad_against_the_closed_form, logp_case
 from gprc_amd.fit import dens, logp_grad, optimize
+from gpu_calls import grad_problem, raw_logp_grad, step_time_limit  # noqa: F401  (the autouse fixture)
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-STEP_LIMIT_S = 900   # a hung step ends the process (with every thread's traceback) instead of holding the GPU
-
-
-@pytest.fixture(autouse=True)
-def step_time_limit():
-    faulthandler.dump_traceback_later(STEP_LIMIT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
 
 
 # ---- 1. ARD values ----------------------------------------------------------------------------------------------------------
@@ -99,58 +90,12 @@ def test_ard_model_against_oracle_on_scaled_inputs(n):
 
 
 # ---- 3. gradient against the closed form ------------------------------------------------------------------------------------
-def grad_problem(n, d):
-    rng = np.random.default_rng(1000 + n + d)
-    X = rng.uniform(-2, 2, (d, n))
-    y = np.sin(X.sum(0)) + 0.1 * rng.normal(size=n)
-    return X, y, rng.uniform(0.7, 2.0, d)
-
-
-def grad_case(case, n):
-    """(name, theta, oracle kernel id, oracle params, oracle inputs, X, y) of a named case at size n"""
-    if case.startswith("ard"):
-        d = int(case[3:])
-        X, y, ell = grad_problem(n, d)
-        if d > 16:
-            ell = ell * np.sqrt(d / 3)       # (see WIDE_CASES)
-        return "sqrexp_ard", ell, orc.SQREXP, [1.0], X / ell[:, None], X, y
-    if case == "sqrexp_d17":
-        X, y, _ = grad_problem(n, 17)
-        theta = np.array([1.3 * np.sqrt(17 / 3)])
-        return "sqrexp", theta, orc.SQREXP, list(theta), X, X, y
-    name, theta = {"sqrexp": ("sqrexp", [1.3]), "gammaexp1.5": ("gammaexp", [0.9, 1.5]), "gammaexp1": ("gammaexp", [1.2, 1.0]),
-                   "ratquad": ("rationalquadratic", [1.1, 1.7])}[case]
-    X, y, _ = grad_problem(n, 3)
-    return name, np.array(theta), orc.KERNEL_IDS[name], list(theta), X, X, y
-
-
-# d > 16: the contraction stages the coordinates 16 at a time, so d = 17 takes two passes and d = 33 three, the last of one coordinate
-# each, and ARD stages them again for its second pass.  The length scales are multiplied by sqrt(d / 3): at the scales of d = 3 the
-# kernel matrix of 17 coordinates is nearly the identity, the length-scale gradient is ~1e-2 of the noise derivative and a normwise
-# bound over the whole vector would hide a wrong coordinate.  With the scaling (numpy reference, ard17, n = 300, noise 0.1):
-# max |d/dl| = 1.39, min |d/dl| = 0.018, d/dnoise = -28.9; these cases also bound the parameter block on its own.
-WIDE_CASES = ["ard17", "sqrexp_d17", "ard33"]
-
-
+# (the Matern rows of case_checks.LOGP_CASES run at their own sizes, under the names they have always had, in tests/test_gpu_matern.py)
 @pytest.mark.parametrize("case,n,noise", [(c, n, noise) for n, noise in [(300, 0.1), (600, 0.01), (3000, 0.05), (5000, 0.05)]
                                           for c in ["sqrexp", "gammaexp1.5", "gammaexp1", "ratquad", "ard3", "ard8"]]
-                         + [(c, 300, 0.1) for c in WIDE_CASES])
+                         + [(c, 300, 0.1) for c in ["ard17", "sqrexp_d17", "ard33"]])
 def test_gradient_against_the_closed_form(case, n, noise):
-    name, theta, kid, opar, Xo, X, y = grad_case(case, n)
-    assert orc.gpr_fit(kid, opar, Xo, y, noise)["attempts"] == 1
-    want_logp, want = ref.logp_grad(name, theta, X, y, noise)
-    logp, grad = logp_grad(X, y, noise, name, theta)
-    assert grad.shape == (theta.size + 1,)
-    e = nerr(grad, want)
-    print(f"logp_grad {case} n={n} noise={noise}: nerr(grad)={e:.3e} rel(logp)={abs(logp - want_logp) / abs(want_logp):.3e}")
-    assert e <= TOL
-    if case in WIDE_CASES:
-        eb = nerr(grad[:-1], want[:-1])
-        print(f"logp_grad {case} n={n}: nerr(parameter block)={eb:.3e} max|d/dtheta|={np.abs(want[:-1]).max():.3g} "
-              f"min|d/dtheta|={np.abs(want[:-1]).min():.3g} d/dnoise={want[-1]:.3g}")
-        assert eb <= TOL
-    assert abs(logp - want_logp) <= TOL * abs(want_logp)
-    assert logp == dens(X, y, noise, name, theta)          # the value is the existing objective, bit for bit
+    check_logp_grad_against_the_closed_form(case, n, noise)
 
 
 # ---- 4. gradient against differences of the library's own value -------------------------------------------------------------
@@ -171,17 +116,10 @@ def test_gradient_against_differences_of_log_marginal():
 
 
 # ---- 5. pointer kinds and determinism ---------------------------------------------------------------------------------------
-def raw_logp_grad(kid, theta, Xptr, d, n, yptr, noise, ctx):
-    _, pp, npar = nat.params_array(theta)
-    g, lp = np.empty(npar + 1), C.c_double()
-    nat.check(nat.lib().gprc_gpr_logp_grad(ctx.handle, kid, pp, npar, Xptr, d, n, yptr, noise, C.byref(lp), g.ctypes.data_as(C.POINTER(C.c_double))))
-    return lp.value, g
-
-
 @pytest.mark.parametrize("case", ["ard8", "gammaexp1.5"])
 def test_pointer_kinds_repeat_calls_and_trim_give_the_same_bits(case):
     torch = pytest.importorskip("torch")
-    name, theta, *_, X, y = grad_case(case, 1100)
+    name, theta, X, y, _ = logp_case(case, 1100)
     X = np.asfortranarray(X)
     d, n = X.shape
     kid = {"sqrexp_ard": nat.SQREXP_ARD, "gammaexp": nat.GAMMAEXP}[name]
@@ -200,7 +138,7 @@ def test_pointer_kinds_repeat_calls_and_trim_give_the_same_bits(case):
 
 
 def test_profile_kinds_of_the_new_stages():
-    name, theta, *_, X, y = grad_case("ard3", 1100)
+    name, theta, X, y, _ = logp_case("ard3", 1100)
     nat.lib().gprc_prof_enable(1)
     nat.lib().gprc_prof_reset()
     try:

@@ -13,83 +13,33 @@ alone, that it converged in < 50 steps and that none of its objective decrements
 step at which the search stops cannot depend on rounding and the iteration counts can be compared.
 """
 import ctypes as C
-import faulthandler
 
 import numpy as np
 import pytest
 
-import gpc_grad_ref as ref
 from conftest import TOL, nerr
 from gprc_amd import GPC, GprcError
 from gprc_amd import _native as nat
 from gprc_amd.fit import grad_dict, logp_grad, logq_grad, optimize_gpc
+from case_checks import (LOGQ_CASES as CASES, LOGQ_MATERN_CASES as MATERN_CASES, LOGQ_MATERN_WIDE as MATERN_WIDE, LOGQ_WIDE_CASES as WIDE_CASES,
+                         check_value_is_tied_to_the_fitted_classifier, logq_case, logq_reference)
+from gpu_calls import EPS, gpc_problem, raw_logq_grad, step_time_limit  # noqa: F401  (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
-STEP_LIMIT_S = 900   # a hung step ends the process (with every thread's traceback) instead of holding the GPU
-EPS = 1e-10
-
-
-@pytest.fixture(autouse=True)
-def step_time_limit():
-    faulthandler.dump_traceback_later(STEP_LIMIT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-CASES = {"sqrexp": ("sqrexp", [0.8], 3), "gammaexp1.5": ("gammaexp", [0.9, 1.5], 3), "gammaexp1": ("gammaexp", [1.2, 1.0], 3),
-         "ratquad": ("rationalquadratic", [1.1, 1.7], 3), "ard3": ("sqrexp_ard", [0.8, 1.1, 1.9], 3),
-         "ard8": ("sqrexp_ard", np.linspace(1.0, 3.0, 8), 8)}
-# d > 16: the contraction stages the coordinates 16 at a time, so d = 17 takes two passes and d = 33 three, the last of one coordinate
-# each, and ARD stages them again for its second pass.  The length scales are multiplied by sqrt(d / 3): at the scales of d = 3 the
-# kernel matrix of 17 coordinates is nearly the identity.  The gradient has no noise entry here: the whole vector is the parameter
-# block, and the normwise bound is on it.
-WIDE_CASES = {"ard17": ("sqrexp_ard", np.linspace(1.0, 3.0, 17) * np.sqrt(17 / 3), 17), "sqrexp_d17": ("sqrexp", [0.8 * np.sqrt(17 / 3)], 17),
-              "ard33": ("sqrexp_ard", np.linspace(1.0, 3.0, 33) * np.sqrt(33 / 3), 33)}
-
-
-def problem(n, d, seed=None):
-    rng = np.random.default_rng(7000 + n + d if seed is None else seed)
-    X = rng.uniform(-1, 1, (d, n))
-    y = np.sign(X[0] - 0.5 * X[d - 1] + 0.3 * rng.normal(size=n))
-    y[y == 0] = 1.0
-    return X, y
-
-
-def grad_case(case, n):
-    name, theta, d = CASES[case] if case in CASES else WIDE_CASES[case]
-    X, y = problem(n, d)
-    return name, np.asarray(theta, dtype=float), X, y
-
-
-def reference(name, theta, X, y):
-    """the numpy reference, with the two preconditions on it that make the comparison meaningful"""
-    want_logq, want, iters, decrements = ref.logq_grad(name, theta, X, y, EPS)
-    assert iters < 50
-    assert not any(EPS / 1.2 <= dcr <= 1.2 * EPS for dcr in decrements), decrements
-    return want_logq, want, iters
-
-
-def raw_logq_grad(kid, theta, Xptr, d, n, yptr, ctx, epsilon=EPS, max_iter=0):
-    _, pp, npar = nat.params_array(theta)
-    g, lq, it = np.empty(npar), C.c_double(), C.c_int()
-    nat.check(nat.lib().gprc_gpc_logq_grad(ctx.handle, kid, pp, npar, Xptr, d, n, yptr, epsilon, max_iter, C.byref(lq),
-                                           g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it)))
-    return lq.value, g, it.value
-
 
 # ---- 1. closed form ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case,n", [(c, n) for n in [300, 600, 3000, 5000] for c in CASES] + [(c, 300) for c in WIDE_CASES])
+@pytest.mark.parametrize("case,n", [(c, n) for n in [300, 600, 3000, 5000] for c in CASES] + [(c, 300) for c in WIDE_CASES]
+                         + [(c, n) for n in [600, 1100] for c in MATERN_CASES] + [(c, 300) for c in MATERN_WIDE])
 def test_gradient_against_the_closed_form(case, n):
-    name, theta, X, y = grad_case(case, n)
-    want_logq, want, want_iters = reference(name, theta, X, y)
+    name, theta, X, y = logq_case(case, n)
+    want_logq, want, want_iters = logq_reference(name, theta, X, y)
     Xf = np.asfortranarray(X)
     logq, grad, iters = raw_logq_grad(grad_dict[name].kernel_id, theta, Xf.ctypes.data, X.shape[0], n, y.ctypes.data, nat.default_context())
     assert grad.shape == (theta.size,)
     e = nerr(grad, want)
-    if case in WIDE_CASES:
-        print(f"logq_grad {case} n={n}: max|d/dtheta|={np.abs(want).max():.3g} min|d/dtheta|={np.abs(want).min():.3g}")
-    print(f"logq_grad {case} n={n}: nerr(grad)={e:.3e} rel(logq)={abs(logq - want_logq) / abs(want_logq):.3e} iters={iters} ref={want_iters}")
+    print(f"logq_grad {case} n={n}: nerr(grad)={e:.3e} rel(logq)={abs(logq - want_logq) / abs(want_logq):.3e} iters={iters} ref={want_iters} "
+          f"max|d/dtheta|={np.abs(want).max():.3g} min|d/dtheta|={np.abs(want).min():.3g}")
     assert e <= TOL
     assert abs(logq - want_logq) <= TOL * abs(want_logq)
     assert iters == want_iters
@@ -98,27 +48,16 @@ def test_gradient_against_the_closed_form(case, n):
 
 
 # ---- 2. tie to the existing path --------------------------------------------------------------------------------------------
+# (the Matern cases of this check keep the name they have always had, in tests/test_gpu_matern.py)
 @pytest.mark.parametrize("n", [300, 600, 3000])
 @pytest.mark.parametrize("case", list(CASES))
 def test_value_is_tied_to_the_fitted_classifier(case, n):
-    from gprc_amd import CovFunc
-    name, theta, X, y = grad_case(case, n)
-    func = grad_dict[name]
-    k = CovFunc(func, {"l": theta} if name == "sqrexp_ard" else func.bind(tuple(theta), {}))
-    Xf = np.asfortranarray(X)                                      # kept alive: the call borrows its memory
-    logq, _, iters = raw_logq_grad(func.kernel_id, theta, Xf.ctypes.data, X.shape[0], n, y.ctypes.data, nat.default_context())
-    gc = GPC(X, y, k, EPS, reference_stop=False)
-    dl = np.diag(gc.L)
-    want = gc.logq + dl.sum() - np.log(dl).sum()
-    print(f"logq_grad {case} n={n}: logq={logq!r} from the classifier {want!r} iterations {gc.iterations} / {iters}")
-    assert gc.iterations == iters
-    assert abs(logq - want) <= TOL * abs(want)
-    gc.close()
+    check_value_is_tied_to_the_fitted_classifier(case, n)
 
 
 # ---- 3. gradient against differences of the library's own value -------------------------------------------------------------
 def test_gradient_against_differences_of_the_library_value():
-    name, theta, X, y = grad_case("ard8", 3000)
+    name, theta, X, y = logq_case("ard8", 3000)
     _, grad = logq_grad(X, y, name, theta)
     fd = np.empty(8)
     for k in range(8):
@@ -134,7 +73,7 @@ def test_gradient_against_differences_of_the_library_value():
 @pytest.mark.parametrize("case", ["ard8", "gammaexp1.5"])
 def test_pointer_kinds_repeat_calls_and_trim_give_the_same_bits(case):
     torch = pytest.importorskip("torch")
-    name, theta, X, y = grad_case(case, 1100)
+    name, theta, X, y = logq_case(case, 1100)
     X = np.asfortranarray(X)
     d, n = X.shape
     kid = grad_dict[name].kernel_id
@@ -158,14 +97,14 @@ def test_regression_gradient_keeps_its_bits_around_a_classification_call():
     Xr = rng.uniform(-2, 2, (3, 1300))
     yr = np.sin(Xr.sum(0)) + 0.1 * rng.normal(size=1300)
     before = logp_grad(Xr, yr, 0.05, "rationalquadratic", [1.1, 1.7])
-    name, theta, X, y = grad_case("ard3", 900)
+    name, theta, X, y = logq_case("ard3", 900)
     logq_grad(X, y, name, theta)
     after = logp_grad(Xr, yr, 0.05, "rationalquadratic", [1.1, 1.7])
     assert after[0] == before[0] and np.array_equal(after[1], before[1])
 
 
 def test_profile_kinds_of_the_stages():
-    name, theta, X, y = grad_case("ard3", 1100)
+    name, theta, X, y = logq_case("ard3", 1100)
     nat.lib().gprc_prof_enable(1)
     nat.lib().gprc_prof_reset()
     try:
@@ -181,7 +120,7 @@ def test_profile_kinds_of_the_stages():
 
 # ---- 5. errors --------------------------------------------------------------------------------------------------------------
 def test_errors():
-    X, y = problem(40, 2)
+    X, y = gpc_problem(40, 2)
     ctx = nat.default_context()
     Xf = np.asfortranarray(X)
     for kid, par in ((nat.POLYNOMIAL, [1.0, 2.0]), (nat.LINEAR, [1.0]), (nat.CONSTANT, [1.0])):
@@ -203,8 +142,8 @@ def test_errors():
     assert lib.gprc_gpc_logq_grad(ctx.handle, nat.SQREXP, pp, npar, Xf.ctypes.data, 2, 40, y.ctypes.data, EPS, 0, None, gp, None) == nat.ERR_ARG
     assert lib.gprc_gpc_logq_grad(ctx.handle, nat.SQREXP, pp, npar, Xf.ctypes.data, 2, 40, y.ctypes.data, EPS, 0, C.byref(lq), None, None) == nat.ERR_ARG
     # a case that needs 6 steps, capped at 2
-    name, theta, Xb, yb = grad_case("ard3", 600)
-    _, _, iters = reference(name, theta, Xb, yb)
+    name, theta, Xb, yb = logq_case("ard3", 600)
+    _, _, iters = logq_reference(name, theta, Xb, yb)
     assert iters >= 6
     Xbf = np.asfortranarray(Xb)
     with pytest.raises(GprcError) as ei:

@@ -12,30 +12,23 @@ cond 6.4e3); against a model fitted without the point <= 2.7e-15; gprc_gpr_loo_g
 central differences of the library's own score <= 6.0e-11; the two paths to the score agree to the last bit on the two cases here.
 """
 import ctypes as C
-import faulthandler
 import functools
 
 import numpy as np
 import pytest
 
+import kernel_ref as K
 import loo_ref as R
 from conftest import TOL, nerr
 from gprc_amd import GPC, GPR, GprcError, NotPositiveDefinite, cov_func, linear, sqrexp
 from gprc_amd import _native as nat
-from gprc_amd.fit import _func_of, loo_grad, optimize
+from gprc_amd.fit import loo_grad, optimize
+from gpu_calls import kfun, same_bits, step_time_limit  # noqa: F401  (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
-STEP_LIMIT_S = 900   # a hung step ends the process (with every thread's traceback) instead of holding the GPU
 NOISE = 0.1
 COND_MAX = 1e4
-
-
-@pytest.fixture(autouse=True)
-def step_time_limit():
-    faulthandler.dump_traceback_later(STEP_LIMIT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
 
 
 def problem(n, d):
@@ -59,10 +52,10 @@ def kname(name):
     return "gammaexp" if name == "gammaexp1" else name
 
 
-def kfun(name, theta):
+def kernel_of(name, theta):
     if name == "linear":
         return cov_func(linear, sigma=theta[0])
-    return _func_of(kname(name), tuple(float(v) for v in theta))
+    return kfun(kname(name), theta)
 
 
 @functools.lru_cache(maxsize=None)
@@ -89,10 +82,6 @@ def raw_loo(model, n, mean=True, var=True, dens=True, score=True):
     return out + [sc.value if score else None]
 
 
-def same_bits(a, b):
-    return all((x is None and y is None) or np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
-
-
 # ---- 1. gprc_gpr_loo against the closed form --------------------------------------------------------------------------------------
 LOO_CASES = [("sqrexp", 5, 1), ("linear", 300, 3), ("gammaexp", 300, 1), ("matern32_ard", 300, 3), ("rationalquadratic", 700, 3),
              ("sqrexp_ard", 700, 20), ("matern52", 700, 1), ("matern32", 1300, 3), ("matern52_ard", 1300, 20), ("sqrexp", 1300, 1)]
@@ -102,7 +91,7 @@ LOO_CASES = [("sqrexp", 5, 1), ("linear", 300, 3), ("gammaexp", 300, 1), ("mater
 def test_loo_against_the_closed_form(name, n, d):
     ref = reference(name, n, d)
     assert ref["cond"] <= COND_MAX, ref["cond"]
-    g = GPR(ref["X"], ref["y"], NOISE, kfun(name, ref["theta"]))
+    g = GPR(ref["X"], ref["y"], NOISE, kernel_of(name, ref["theta"]))
     assert g.noise == NOISE                                   # the fit succeeded at the first attempt
     got = g.loo()
     score = g.loo_score
@@ -122,14 +111,14 @@ def test_loo_is_the_prediction_of_a_model_without_the_point():
     n, d, name = 700, 3, "matern52_ard"
     X, y = problem(n, d)
     th = theta_of(name, d)
-    g = GPR(X, y, NOISE, kfun(name, th))
+    g = GPR(X, y, NOISE, kernel_of(name, th))
     assert g.noise == NOISE
     got = g.loo()
     g.close()
     worst = 0.0
     for i in (0, 350, 699):
         keep = np.arange(n) != i
-        h = GPR(np.asfortranarray(X[:, keep]), y[keep], NOISE, kfun(name, th))
+        h = GPR(np.asfortranarray(X[:, keep]), y[keep], NOISE, kernel_of(name, th))
         assert h.noise == NOISE
         pred = h.predict(X[:, i:i + 1])
         h.close()
@@ -142,7 +131,7 @@ def test_loo_is_the_prediction_of_a_model_without_the_point():
 # ---- 3. chunking and repetition ----------------------------------------------------------------------------------------------------
 def test_loo_is_bitwise_chunk_invariant_and_repeatable(monkeypatch):
     ref = reference("rationalquadratic", 700, 3)
-    k = kfun("rationalquadratic", ref["theta"])
+    k = kernel_of("rationalquadratic", ref["theta"])
     g = GPR(ref["X"], ref["y"], NOISE, k)
     whole = raw_loo(g._model, 700)
     assert same_bits(raw_loo(g._model, 700), whole)
@@ -162,7 +151,7 @@ def test_pointer_kinds_null_outputs_and_refusals():
     torch = pytest.importorskip("torch")
     n = 700
     ref = reference("rationalquadratic", n, 3)
-    g = GPR(ref["X"], ref["y"], NOISE, kfun("rationalquadratic", ref["theta"]))
+    g = GPR(ref["X"], ref["y"], NOISE, kernel_of("rationalquadratic", ref["theta"]))
     host = raw_loo(g._model, n)
     dev = torch.device("cuda:0")
     outs = [torch.full((n,), float("nan"), dtype=torch.float64, device=dev) for _ in range(3)]
@@ -190,7 +179,7 @@ def test_pointer_kinds_null_outputs_and_refusals():
 # ---- 5. several (virtual) ranks ---------------------------------------------------------------------------------------------------
 def test_loo_of_a_model_over_virtual_ranks_is_the_single_gpu_one():
     ref = reference("matern32", 1300, 3)
-    k = kfun("matern32", ref["theta"])
+    k = kernel_of("matern32", ref["theta"])
     one = GPR(ref["X"], ref["y"], NOISE, k)
     two = GPR(ref["X"], ref["y"], NOISE, k, devices=[0, 0])
     a, b = one.loo(), two.loo()
@@ -203,7 +192,7 @@ def test_loo_of_a_model_over_virtual_ranks_is_the_single_gpu_one():
 
 # ---- 6. gprc_gpr_loo_grad against the closed form --------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,d", [(300, 3), (1300, 20)])
-@pytest.mark.parametrize("name", R.GRAD_NAMES)
+@pytest.mark.parametrize("name", K.NAMES)
 def test_loo_grad_against_the_closed_form(name, n, d):
     ref = reference(name, n, d, True)
     assert ref["cond"] <= COND_MAX, ref["cond"]
@@ -217,7 +206,7 @@ def test_loo_grad_against_the_closed_form(name, n, d):
 
 # ---- 7. gradient against central differences of the library's own score ------------------------------------------------------------
 def library_score(X, y, noise, name, theta):
-    g = GPR(X, y, noise, kfun(name, theta))
+    g = GPR(X, y, noise, kernel_of(name, theta))
     assert g.noise == noise
     s = g.loo_score
     g.close()

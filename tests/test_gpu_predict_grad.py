@@ -1,47 +1,24 @@
 """gprc_gpr_predict_grad / GPR.predict_grad on the MI355X against tests/pred_grad_ref.py (float64; itself within 1.6e-13 of the
 longdouble formulas, tests/test_pred_grad_cpu.py), normwise TOL = 1e-10 on each of mean, variance and the two gradients; the mean and
-the variance are also the very bits of gprc_gpr_predict.  Geometry: n = 1, 512 (no padding, one panel), 700 (padding of 324 columns: not
+the variance are also the very bits of gprc_gpr_predict.  (The Matern kernels: tests/test_gpu_matern.py, against the longdouble reference.)
+Geometry: n = 1, 512 (no padding, one panel), 700 (padding of 324 columns: not
 a multiple of 128), 1100 (three panels); n* = 1, 129, 300; d = 1, 3, 8 and 17 (two passes over the coordinates, three coordinate groups).
 Then what must not change the bits (chunking, the solve's schedule, where the pointers live, which outputs are asked for), the reversed
 factor's life (built on demand, dropped by add_data), the refusals, and a loose cross-check against differences of GPR.predict."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from conftest import TOL
-from gprc_amd import GPR, GPC, cov_func, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard
+from gprc_amd import GPR, GPC, cov_func, polynomial, sqrexp
 from gprc_amd import _native as nat
+from gpu_calls import call_predict_grad as call, kfun, same_bits, step_time_limit  # noqa: F401  (the autouse fixture)
+import kernel_ref as K
 import pred_grad_ref as G
 
 pytestmark = pytest.mark.gpu
 
 NOISE = 0.1
-SQ3, SQ8, ARD3, GE15, GE10, RQ = G.CASES
-
-
-def kfun(name, par):
-    if name == "sqrexp":
-        return cov_func(sqrexp, l=par[0])
-    if name == "sqrexp_ard":
-        return cov_func(sqrexp_ard, l=np.asarray(par, dtype=float))
-    if name == "gammaexp":
-        return cov_func(gammaexp, l=par[0], gamma=par[1])
-    return cov_func(rationalquadratic, l=par[0], alpha=par[1])
-
-
-def call(g, Xs, mean=True, var=True, dmean=True, dvar=True):
-    """gprc_gpr_predict_grad with host pointers; an output not asked for is passed as NULL and returned as None"""
-    d, ns = Xs.shape
-    Xs = np.asfortranarray(Xs)
-    out = [np.full(ns, np.nan) if mean else None, np.full(ns, np.nan) if var else None,
-           np.full((d, ns), np.nan, order="F") if dmean else None, np.full((d, ns), np.nan, order="F") if dvar else None]
-    nat.check(nat.lib().gprc_gpr_predict_grad(g._model, Xs.ctypes.data, ns, *[o.ctypes.data if o is not None else None for o in out]))
-    return out
-
-
-def same_bits(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
+SQ3, SQ8, ARD3, GE15, GE10, RQ = K.BASE_CASES[:6]
 
 
 def check_against_reference(case, n, ns, at_training_point=None):
@@ -52,7 +29,7 @@ def check_against_reference(case, n, ns, at_training_point=None):
     ref = G.predict_grad(name, par, X, y, NOISE, Xs)
     for what, a, b in zip(("mean", "var", "dmean", "dvar"), got, ref):
         e = G.nerr(a, b)
-        print("%s n %d n* %d %s %.2e" % (G.case_id(case), n, ns, what, e))
+        print("%s n %d n* %d %s %.2e" % (K.case_id(case), n, ns, what, e))
         assert np.isfinite(a).all() and e <= TOL, (what, e)
     pred = g.predict(Xs)
     assert np.array_equal(got[0], pred[:, 0]) and np.array_equal(got[1], pred[:, 1])    # the bits of gprc_gpr_predict(pointwise = 1)
@@ -60,7 +37,7 @@ def check_against_reference(case, n, ns, at_training_point=None):
     return got
 
 
-@pytest.mark.parametrize("case", G.CASES, ids=G.case_id)
+@pytest.mark.parametrize("case", K.BASE_CASES, ids=K.case_id)
 def test_every_kernel_against_the_reference(case):
     check_against_reference(case, 700, 129)
 
@@ -79,7 +56,7 @@ def test_one_and_seventeen_coordinates(name, d):
     check_against_reference((name, par, d), 700, 129)
 
 
-@pytest.mark.parametrize("case", [SQ3, GE15], ids=G.case_id)
+@pytest.mark.parametrize("case", [SQ3, GE15], ids=K.case_id)
 def test_one_training_point_one_test_point_far_apart(case):
     name, par, d = case
     X, y, Xs = np.zeros((d, 1), order="F"), np.array([1.3]), np.full((d, 1), 1.5, order="F")
@@ -228,7 +205,7 @@ def test_refusals():
         m.close()
 
 
-@pytest.mark.parametrize("case", [SQ3, RQ], ids=G.case_id)
+@pytest.mark.parametrize("case", [SQ3, RQ], ids=K.case_id)
 def test_public_api_against_differences_of_predict(case):
     """loose on purpose (central differences of float64 predictions, h = 1e-5): a sign, a factor 2 or a transposed layout shows"""
     name, par, d = case
