@@ -135,6 +135,15 @@ PROTOTYPES = {
     "gprc_prof_summary": (C.c_int, [C.c_int, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gprc_dev_solve_rows": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64]),
     "gprc_dev_reverse_factor": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "gprc_sgpr_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, _vp, _i64, C.c_double, C.POINTER(_vp)]),
+    "gprc_sgpr_elbo": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, _vp, _i64, C.c_double,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gprc_sgpr_predict": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gprc_sgpr_get_elbo": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gprc_sgpr_get_c": (C.c_int, [_vp, _vp]),
+    "gprc_dev_gemm_nt": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int]),
+    "gprc_dev_gram_rows": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "gprc_dev_col_reduce": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -39,7 +39,7 @@ struct gprc_ctx {
   size_t pool_cap = (size_t)16 << 30;     // GPRC_POOL_BYTES; blocks larger than the cap are never kept
 };
 
-enum ModelType { MODEL_GPR = 1, MODEL_GPC = 2 };
+enum ModelType { MODEL_GPR = 1, MODEL_GPC = 2, MODEL_SGPR = 3 };
 
 struct gprc_model {
   gprc_ctx* ctx = nullptr;
@@ -59,6 +59,12 @@ struct gprc_model {
   double* winv_rev = nullptr;    // wants the variance's gradient, owned by the model (never borrowed), gone after gprc_gpr_extend
   double logp = 0.0, noise = 0.0, logq = 0.0;
   bool borrowed = false;     // X, y, packed, winv, alpha belong to the caller
+  // MODEL_SGPR (gprc_sparse.hip): n = m inducing points, X = Z (d x m), packed / winv = L_u, alpha = c, y = nullptr (the training set is
+  // not kept); the factor of B, the bound, its trace term, the jitter of K_uu and the number of training points:
+  double* packed_b = nullptr;
+  double* winv_b = nullptr;
+  double elbo = 0.0, trace = 0.0, jitter = 0.0;
+  int64_t n_train = 0;
 };
 
 namespace gprc {

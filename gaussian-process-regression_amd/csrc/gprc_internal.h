@@ -5,6 +5,7 @@
 //   gprc_sched.hip  the factor and solve schedules, chunk workspaces, every schedule knob of the host layer; the layout helpers and
 //                   the gprc_dev_* building blocks
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
+//   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound, predict) and its entry points
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip and kernels_pgrad.hip, the
@@ -172,6 +173,16 @@ int launch_trailing_update(hipStream_t s, double* packed, int64_t n_pad, int64_t
 // ... with the source panels [p_begin, p_end) in one pass (p_begin = 0, p_end = q_begin: the left-looking update of a group)
 int launch_trailing_range(hipStream_t s, double* packed, int64_t n_pad, int64_t p_begin, int64_t p_end, int64_t q_begin, int64_t q_end,
                           int64_t q_stride);
+
+// ---- launchers (kernels_gram.hip: the sparse GPR's reductions over the rows of a solved chunk) ----
+// packed(lower) += vt[0:rows, 0:n_pad]^T vt[0:rows, 0:n_pad], straight into the packed block-column layout (128 x 128 tiles on or below
+// the block diagonal; a diagonal tile is written whole).  vt: column-major, ld even; rows % 256 == 0.  An element is the stored value
+// plus its rows' products in ascending row order: a call with r1 + r2 rows gives the bits of two calls with r1, then r2 rows.
+int launch_gram_rows(hipStream_t s, const double* vt, int64_t ld, int64_t rows, int64_t n_pad, double* packed);
+// out[j] += sum_i vt[i, j] w[i], j < cols; rows % 256 == 0, w: `rows` doubles (zero where vt's rows are padding); the same invariance
+int launch_col_reduce(hipStream_t s, const double* vt, int64_t ld, int64_t rows, int64_t cols, const double* w, double* out);
+int launch_gram_to_b(hipStream_t s, double* packed, int64_t n_pad, double sigma2);   // packed := I + packed / sigma2 (every stored element)
+int launch_div_vec(hipStream_t s, double* x, int64_t n, double f);                    // x /= f
 
 // ---- launchers (kernels_chol.hip: PanelSync flags, the wait records) --------------------------
 // (what they are told -- trace, split, part, forced, wgs, core, head_slices -- is decided in gprc_sched.hip)

@@ -481,6 +481,22 @@ int gprc_dev_row_reduce(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t row
   return launch_row_reduce(ctx->stream, vt, ld, rows, cols, w, out, work);
 }
 
+int gprc_dev_gemm_nt(gprc_ctx* ctx, double* Cm, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M, int64_t N,
+                     int64_t K, int lower) {
+  GPRC_TRY(use_device_unless(ctx, !Cm || !A || !B || ldc < M || lda < M || ldb < N, "dev_gemm_nt: bad arguments"));
+  return launch_gemm_nt(ctx->stream, Cm, ldc, A, lda, B, ldb, M, N, K, lower ? 1 : 0, PK_COV_SYRK);
+}
+
+int gprc_dev_gram_rows(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t rows, int64_t n_pad, double* packed) {
+  GPRC_TRY(use_device(ctx));
+  return launch_gram_rows(ctx->stream, vt, ld, rows, n_pad, packed);
+}
+
+int gprc_dev_col_reduce(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t rows, int64_t cols, const double* w, double* out) {
+  GPRC_TRY(use_device(ctx));
+  return launch_col_reduce(ctx->stream, vt, ld, rows, cols, w, out);
+}
+
 int gprc_dev_logp(gprc_ctx* ctx, const double* packed, int64_t n_pad, int64_t n, const double* y, const double* alpha,
                   double* out_dev) {
   GPRC_TRY(use_device(ctx));

@@ -39,7 +39,7 @@ from . import _native as nat
 from .covfunc import (CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
                       matern32_ard, matern52_ard)
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "loo_grad", "optimize", "logq_grad", "optimize_gpc", "cov_dict", "brent_fmin", "vmmin"]
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "loo_grad", "optimize", "logq_grad", "optimize_gpc", "elbo", "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
 cov_dict = {
@@ -144,6 +144,14 @@ def loo_grad(X, y, noise, name, v, ctx=None):
     nat.check(nat.lib().gprc_gpr_loo_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
                                           C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double))))
     return out.value, g
+
+
+def elbo(X, y, noise, k, Z, jitter=1e-6, ctx=None):
+    """The collapsed variational bound of the sparse GPR with inducing points Z (sparse.SparseGPR; gprc_sgpr_elbo): a lower bound of
+    what `dens` returns for the same kernel and noise, equal to it at Z = X, jitter = 0.  `k` is a cov_func() object, as GPR takes it.
+    No gradient of the bound yet: it is an objective to compare inducing sets and hyper-parameters by, not to run `optimize` on."""
+    from .sparse import elbo as _elbo
+    return _elbo(X, y, noise, k, Z, jitter, ctx=ctx)
 
 
 def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):

@@ -228,6 +228,36 @@ GPRC_API int gprc_gpr_get_logp(gprc_model* model, double* logp_out);
 GPRC_API int gprc_gpr_get_noise(gprc_model* model, double* noise_out);
 GPRC_API int gprc_model_free(gprc_model* model);
 
+/* ---- L2: sparse GPR with inducing points (Titsias' variational bound, collapsed; no reference counterpart) -------- *
+ * X: d x n, y: n, noise = sigma^2 > 0 (the variance), Z: d x m inducing points, jitter >= 0, any kernel id.
+ *   K_uu = k(Z,Z) + jitter I = L_u L_u^T            V = K(X,Z) L_u^-T  (n x m, row i = v_i^T)
+ *   B    = I + V^T V / sigma^2 = L_B L_B^T          b = V^T y,   c = L_B^-1 b / sigma^2
+ *   t    = sum_i ( k(x_i,x_i) - |v_i|^2 )           (the trace term, >= 0 up to rounding)
+ *   elbo = -n/2 log(2 pi sigma^2) - sum_j log (L_B)_jj - y^T y / (2 sigma^2) + c^T c / 2 - t / (2 sigma^2)
+ * elbo <= log p(y) (gprc_gpr_log_marginal) for every Z and jitter >= 0, with equality at Z = X, jitter = 0.  The fit is one pass
+ * over the training points in row chunks (GPRC_CHUNK_BYTES as for predict, 256-row granularity), 2 n m^2 flop; MEMORY: two packed
+ * m x m factors with their block inverses (2 x (gprc_packed_size + gprc_winv_size)(gprc_pad(m)) doubles, the model's) and one chunk of
+ * the context's workspace -- never n x n, never X: X and y may be host or device pointers, host data is staged chunk by chunk.  The
+ * model keeps Z, both factors and c, not X or y.  No jitter retry: returns info > 0 (the leading minor) when K_uu + jitter I or B is not
+ * positive definite; the error text says which.  Every result -- elbo, t, c, both factors, every prediction -- is the same bit for bit
+ * under every chunking: t and y^T y are summed on the host in index order in long double.  m > n is allowed.
+ * GPRC_ERR_ARG: m < 1, n < 1, noise <= 0 or not finite, jitter < 0 or not finite, null pointers.
+ * A sparse model answers gprc_model_dims with (m, d) and is released by gprc_model_free; gprc_gpr_predict, gprc_gpr_predict_grad,
+ * gprc_gpr_loo, gprc_gpr_extend, gprc_model_get_L, the gprc_gpr_get_* getters and the GPC calls return GPRC_ERR_ARG for it, as the
+ * gprc_sgpr_* calls that take a model do for a GPR or GPC model. */
+GPRC_API int gprc_sgpr_fit(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                           const double* y, double noise, const double* Z, int64_t m, double jitter, gprc_model** model_out);
+/* The objective without keeping a model: *elbo_out and (may be NULL) *trace_out = t, the bits gprc_sgpr_fit + gprc_sgpr_get_elbo give */
+GPRC_API int gprc_sgpr_elbo(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                            const double* y, double noise, const double* Z, int64_t m, double jitter, double* elbo_out, double* trace_out);
+/* At x*: v* = L_u^-1 k(Z,x*), w* = L_B^-1 v*, mean = w*^T c, var = k(x*,x*) - |v*|^2 + |w*|^2 -- the LATENT variance, without the noise,
+ * as gprc_gpr_predict(pointwise = 1).  X_star: d x n_star; mean_out, var_out: n_star doubles, host or device; either may be NULL, not
+ * both.  Chunked over the test points, O(m^2) flop per point, chunk-invariant bit for bit. */
+GPRC_API int gprc_sgpr_predict(gprc_model* model, const double* X_star, int64_t n_star, double* mean_out, double* var_out);
+GPRC_API int gprc_sgpr_get_elbo(gprc_model* model, double* elbo_out, double* trace_out /* may be NULL */);
+/* c = L_B^-1 V^T y / sigma^2 (m doubles, host or device): the vector the predictive mean is a product with */
+GPRC_API int gprc_sgpr_get_c(gprc_model* model, double* c_out);
+
 /* ---- L2: GPC ------------------------------------------------------------------------------ */
 /* GPC$initialize (R/GPCclass.R:66-107): Laplace mode by Newton/IRLS; y in {-1,+1}.
  * max_iter <= 0 selects 1000.  *iters_out = the "Convergence after %s iterations" count (:98).
@@ -368,6 +398,20 @@ GPRC_API int gprc_dev_solve_rows(gprc_ctx* ctx, const double* packed, const doub
  * winv_rev = J winv_block(n_pad / 128 - 1 - b)^T J.  Pure data movement: exact.  Asynchronous, as the other gprc_dev_*. */
 GPRC_API int gprc_dev_reverse_factor(gprc_ctx* ctx, const double* packed, const double* winv, int64_t n_pad, double* packed_rev,
                                      double* winv_rev);
+/* C[M x N] -= A[M x K] B[N x K]^T on the 128 x 128 MFMA tile core (column-major, M, N multiples of 128, K a multiple of 32 and >= 64,
+ * lda, ldb even); lower != 0: only the tiles on or below the block diagonal.  Counted under profiling kind 8.  The yardstick
+ * tools/sgpr_bench.py holds gprc_dev_gram_rows against: the same tiles and flops with k along the leading dimension. */
+GPRC_API int gprc_dev_gemm_nt(gprc_ctx* ctx, double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M,
+                              int64_t N, int64_t K, int lower);
+/* The sparse GPR's two reductions over the ROWS of a solved chunk (device pointers, asynchronous).  vt: rows x n_pad (x cols),
+ * column-major, leading dimension ld >= rows, ld even; rows % 256 == 0; 16-byte aligned buffers.
+ * gram_rows: packed(lower) += vt^T vt straight into the packed block-column layout of an n_pad x n_pad matrix (n_pad % 512 == 0): the
+ * 128 x 128 tiles on or below the block diagonal (a diagonal tile is written whole; the tiles above the diagonal inside a panel's
+ * diagonal block are not touched).  col_reduce: out[j] += sum_i vt[i,j] w[i], j < cols; w: `rows` doubles.
+ * Both add an element's rows in ascending order to the stored value, in groups that end at multiples of 256 rows: one call with
+ * r1 + r2 rows gives the bits of two calls with r1, then r2 rows. */
+GPRC_API int gprc_dev_gram_rows(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t rows, int64_t n_pad, double* packed);
+GPRC_API int gprc_dev_col_reduce(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t rows, int64_t cols, const double* w, double* out);
 
 /* ---- multi-GPU from ONE process (SURVEY 8b "Threading", 8e): the form the R `.Call` boundary can use ------------ *
  * The reference's host is a single R process; it cannot be forked per GPU.  A gprc_mgpu drives G ranks -- one per
