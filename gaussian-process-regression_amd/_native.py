@@ -144,6 +144,9 @@ PROTOTYPES = {
     "gprc_dev_gemm_nt": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int]),
     "gprc_dev_gram_rows": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
     "gprc_dev_col_reduce": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "gprc_sgpr_elbo_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, _vp, _i64, C.c_double,
+                                      C.POINTER(C.c_double), _vp, _vp]),
+    "gprc_dev_cross_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, C.c_double, _vp, _vp]),
 }
 
 _lib = None

@@ -5,11 +5,11 @@
 //   gprc_sched.hip  the factor and solve schedules, chunk workspaces, every schedule knob of the host layer; the layout helpers and
 //                   the gprc_dev_* building blocks
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
-//   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound, predict) and its entry points
+//   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound and its gradient, predict) and its entry points
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
-// pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip and kernels_pgrad.hip, the
-// kernel-id dispatcher and the set of kernels with an exact gradient).
+// pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
+// kernels_sgrad.hip, the kernel-id dispatcher and the set of kernels with an exact gradient).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -152,6 +152,31 @@ int launch_pred_grad(hipStream_t s, const KernelSpec& ks, const double* Xs, int6
                      int64_t d, const double* alpha, const double* W, int64_t ldw, double* pmean, double* pvar);
 int launch_pred_grad_sum(hipStream_t s, const KernelSpec& ks, const double* part, int64_t n_pad, int64_t d, int64_t m_pad, int64_t m, bool variance,
                          double* out);
+
+// ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
+// the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),
+// k and its derivatives recomputed from the row points A (d x rows) and the column points Z (d x cols); rows >= rows and columns >= cols
+// of G are never used.  Per workgroup (stripe of row tiles x column tile) `part` gets the n_params sums
+//   sum_ij G_ij (integrand of theta_k)      without the factors that do not depend on (i, j): cross_grad_wgs() rows of n_params,
+// and, pz != nullptr, per (stripe, coordinate, column)   pz[(st d + c) cols_pad + j] = sum_i G_ij h_ij (a_ic - z_jc)   (ARD: the scaled
+// difference).  cross_grad_stripes(rows_pad) stripes, a function of rows_pad only; cross_grad_partials / _zpartials: the doubles of
+// part / pz that serve every rows_pad.
+// cross_grad_add_partials: acc[k] += f * (the sum of a launch's partials, copied to the host, in workgroup order);  cross_grad_finish:
+// grad_out[k] = factor_k * acc[k];  launch_cross_grad_sum: dZ[c + d j] += f * factor_c * (the stripes of pz in order), j < cols.
+// Kernels: those of with_gradient_kernel.  Profiled as PK_GRAD_CONTRACT.
+int64_t cross_grad_stripes(int64_t rows_pad);
+int64_t cross_grad_wgs(int64_t rows_pad, int64_t cols_pad);
+int64_t cross_grad_partials(int64_t cols_pad, int n_params);
+int64_t cross_grad_zpartials(int64_t cols_pad, int64_t d);
+int launch_cross_grad(hipStream_t s, const KernelSpec& ks, const double* G, int64_t ld, const double* A, int64_t rows, int64_t rows_pad,
+                      const double* Z, int64_t cols, int64_t cols_pad, int64_t d, double* part, double* pz);
+int launch_cross_grad_sum(hipStream_t s, const KernelSpec& ks, const double* pz, int64_t rows_pad, int64_t cols_pad, int64_t cols, int64_t d, double f,
+                          double* dZ);
+void cross_grad_add_partials(const double* part_host, int64_t rows_pad, int64_t cols_pad, int n_params, long double f, long double* acc);
+void cross_grad_finish(const KernelSpec& ks, const long double* acc, double* grad_out);
+int launch_rank_one(hipStream_t s, double* C, int64_t ld, int64_t rows, int64_t cols, const double* u, const double* v, double sign);   // C[i,j] = sign u_i v_j
+// from the lower triangles of W = -B^-1 and of B (n x n, pitch n), in place, both triangles written:  W := I + W,  B := 2 I + W - B
+int launch_sgrad_mid(hipStream_t s, double* W, double* B, int64_t n);
 
 // ---- launchers (kernels_gemm.hip: no flags between workgroups) ---------------------------------
 // the predict's in-panel solve of panel p in one launch (see solve_panel_fused_kernel)

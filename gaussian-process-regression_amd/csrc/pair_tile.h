@@ -1,5 +1,6 @@
 // pair_tile.h -- the pairwise-tile core of the covariance side for gfx950 (MI355X), shared by kernels_fill.hip (the fills),
-// kernels_grad.hip (the contractions of both exact evidence gradients) and kernels_pgrad.hip (the prediction gradients' contraction).
+// kernels_grad.hip (the contractions of both exact evidence gradients), kernels_pgrad.hip (the prediction gradients' contraction) and
+// kernels_sgrad.hip (the sparse bound gradient's contraction; its weight per pair is its own, for the reasons below).
 //
 // One tile of point pairs: PT_R x PT_C = 128 x 64 per 256-thread workgroup, two consecutive rows x 16 columns per lane.  Both point
 // sets go through LDS PT_D = 16 coordinates at a time (As[r][i] coordinate-major for the 16-byte row reads, Bs[j][r] padded by one for

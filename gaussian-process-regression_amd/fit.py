@@ -23,6 +23,9 @@ parameter and the noise), and `optimize` maximises it over log(theta) (and log(n
 makes gammaexp / rationalquadratic searches move and what the d length scales of `sqrexp_ard`, `matern32_ard` and `matern52_ard` need.
 Classification has the same pair: `logq_grad` is the Laplace log evidence of GPC and its exact gradient (gprc_gpc_logq_grad: the
 mode search of GPC$new, then one contraction), `optimize_gpc` maximises it over log(theta).
+The sparse GPR has it too: `elbo_grad` is Titsias' collapsed bound and its exact gradient with respect to the kernel parameters, the
+noise and the inducing points (gprc_sgpr_elbo_grad: the fit's pass, a second pass and one contraction), `optimize_sparse` maximises it
+over log(theta), log(noise) and the inducing points themselves.
 Parity status: unpinned (the reference holds no numeric expectations for fit(); tests/testthat/test-fit.R:12-17 only
 checks which kernel NAME wins); cross-checked against scipy's bounded Brent on the same native objective, and the
 BFGS branch against the same driver running on the CPU oracle's objective and gradient.
@@ -39,7 +42,8 @@ from . import _native as nat
 from .covfunc import (CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
                       matern32_ard, matern52_ard)
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "loo_grad", "optimize", "logq_grad", "optimize_gpc", "elbo", "cov_dict", "brent_fmin", "vmmin"]
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "loo_grad", "optimize", "logq_grad", "optimize_gpc", "elbo", "elbo_grad", "optimize_sparse",
+           "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
 cov_dict = {
@@ -149,9 +153,34 @@ def loo_grad(X, y, noise, name, v, ctx=None):
 def elbo(X, y, noise, k, Z, jitter=1e-6, ctx=None):
     """The collapsed variational bound of the sparse GPR with inducing points Z (sparse.SparseGPR; gprc_sgpr_elbo): a lower bound of
     what `dens` returns for the same kernel and noise, equal to it at Z = X, jitter = 0.  `k` is a cov_func() object, as GPR takes it.
-    No gradient of the bound yet: it is an objective to compare inducing sets and hyper-parameters by, not to run `optimize` on."""
+    `elbo_grad` is the same value with its exact gradient, `optimize_sparse` the optimiser over it."""
     from .sparse import elbo as _elbo
     return _elbo(X, y, noise, k, Z, jitter, ctx=ctx)
+
+
+def elbo_grad(X, y, noise, name, v, Z, jitter=1e-6, with_Z=True, ctx=None):
+    """(elbo, grad, dZ) of SparseGPR(X, y, noise, name(v), Z, jitter): the collapsed bound -- the bits `elbo` returns -- and its exact
+    gradient, one native call (gprc_sgpr_elbo_grad).  `name` a key of grad_dict, `v` in the order `dens` takes it; grad has len(v) + 1
+    entries, d elbo / d noise last; dZ is d x m like Z, d elbo / d Z[c, j], or None when not with_Z (grad has the same bits either
+    way).  Raises nat.NotPositiveDefinite when K_uu + jitter I or B is not positive definite."""
+    func = grad_dict[name]
+    Xm = np.asfortranarray(as_points(X))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    d, n = Xm.shape
+    if y.ndim != 1 or y.size != n:
+        raise ValueError("length(y) == ncol(X) is not TRUE")
+    Zm = np.asfortranarray(as_points(Z, d=d, what="Z") if np.ndim(Z) <= 1 else as_points(Z, what="Z"))
+    if Zm.shape[0] != d:
+        raise ValueError("Z must have nrow(X) rows")
+    ctx = ctx or nat.default_context()
+    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    g = np.empty(p.size + 1)
+    dZ = np.empty(Zm.shape, order="F") if with_Z else None
+    out = C.c_double()
+    nat.check(nat.lib().gprc_sgpr_elbo_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
+                                            Zm.ctypes.data, Zm.shape[1], float(jitter), C.byref(out), g.ctypes.data,
+                                            dZ.ctypes.data if with_Z else None))
+    return out.value, g, dZ
 
 
 def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):
@@ -176,21 +205,26 @@ def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):
     return out.value, g
 
 
-def _maximise_over_log(z0, value_and_grad_theta, maxit):
+def _maximise_over_log(z0, value_and_grad_theta, maxit, n_log=None):
     """vmmin on z = log(theta) of a function to MAXIMISE: value_and_grad_theta(theta) -> (value, d value / d theta); the chain
     rule d / dz = theta * d / dtheta; an evaluation that raises NotPositiveDefinite / ArithmeticError / a native iteration cap,
-    or whose exp(z) over- or underflows, is the sentinel -10000 (optim_until_error).  Returns vmmin's tuple."""
+    or whose exp(z) over- or underflows, is the sentinel -10000 (optim_until_error).  n_log: only the first n_log entries of z are
+    logarithms, the rest are the variables themselves (the inducing points of optimize_sparse; they must stay finite).  Returns
+    vmmin's tuple (z in the same mixed form)."""
     last = {}   # vmmin asks for the gradient at the point whose value it has just accepted: one evaluation serves both
+    n_log = len(z0) if n_log is None else n_log
 
     def evaluate(z):
         key = z.tobytes()
         if last.get("key") != key:
+            t, chain = z.copy(), np.ones(z.size)
             with np.errstate(over="ignore"):
-                t = np.exp(z)
-            if not (np.all(np.isfinite(t)) and np.all(t > 0)):
+                t[:n_log] = np.exp(z[:n_log])
+            chain[:n_log] = t[:n_log]
+            if not (np.all(np.isfinite(t)) and np.all(t[:n_log] > 0)):
                 raise ArithmeticError("parameter out of range")
             val, g = value_and_grad_theta(t)
-            last.update(key=key, val=float(val), grad=np.asarray(g, dtype=np.float64) * t)
+            last.update(key=key, val=float(val), grad=np.asarray(g, dtype=np.float64) * chain)
         return last["val"], last["grad"]
 
     def fn(z):
@@ -241,6 +275,57 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
     par = tuple(float(v) for v in t[:npar])
     return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
             "convergence": fail, "func": _func_of(name, par)}
+
+
+def optimize_sparse(X, y, noise, name, Z, start=None, *, optimize_noise=True, optimize_Z=True, jitter=1e-6, maxit=100, value_and_grad=None,
+                    ctx=None):
+    """Maximise the collapsed bound of the sparse GPR (sparse.SparseGPR) of kernel `name` (a key of grad_dict) over its parameters, over the
+    noise when `optimize_noise`, and over the inducing points when `optimize_Z`, with vmmin on [log(theta), log(noise), vec(Z)]: the
+    parameters and the noise stay positive (d / dz = theta * d / dtheta), the inducing points move freely (column-major, as Z lies in
+    memory).  Z: d x m start positions (sparse.select_inducing picks columns of X); start: parameter vector (default as `optimize`).
+    value_and_grad(theta, noise, Z) -> (elbo, grad, dZ) replaces the native objective `elbo_grad` (grad: len(theta) + 1, noise last; dZ:
+    d x m, ignored unless optimize_Z).  An evaluation that fails (K_uu + jitter I or B not positive definite, a parameter over- or
+    underflowing, an inducing point no longer finite) counts as the sentinel -10000, as in `optimize`.  Returns dict(par, noise, Z,
+    value, counts, convergence, func): SparseGPR(X, y, r["noise"], r["func"], r["Z"], jitter) is the fitted model; convergence 0:
+    converged, 1: maxit reached."""
+    func = grad_dict[name]
+    Xm = as_points(X)
+    d = Xm.shape[0]
+    Z0 = np.asfortranarray(as_points(Z, d=d, what="Z") if np.ndim(Z) <= 1 else as_points(Z, what="Z"))
+    if Z0.shape[0] != d:
+        raise ValueError("Z must have nrow(X) rows")
+    m = Z0.shape[1]
+    if start is None:
+        start = _default_start(name, d)
+    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
+    npar = theta0.size
+    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
+        raise ValueError("optimize_sparse: start values must be finite and > 0")
+    if not (noise > 0 and math.isfinite(noise)):
+        raise ValueError("optimize_sparse: noise must be finite and > 0")
+    with_noise, with_Z = bool(optimize_noise), bool(optimize_Z)
+    if value_and_grad is None:
+        ctx = ctx or nat.default_context()
+        value_and_grad = lambda theta, nz, Zc: elbo_grad(Xm, y, nz, name, theta, Zc, jitter, with_Z, ctx)   # noqa: E731
+    n_log = npar + (1 if with_noise else 0)
+    z0 = np.concatenate([np.log(theta0), [math.log(noise)] if with_noise else [], Z0.ravel(order="F") if with_Z else []])
+
+    def split(t):
+        return (t[:npar].copy(), float(t[npar]) if with_noise else float(noise),
+                np.asfortranarray(t[n_log:].reshape((d, m), order="F")) if with_Z else Z0)
+
+    def vg(t):
+        val, g, dZ = value_and_grad(*split(t))
+        g = np.asarray(g, dtype=np.float64)
+        return val, np.concatenate([g if with_noise else g[:npar], np.asarray(dZ, dtype=np.float64).ravel(order="F") if with_Z else []])
+
+    z, fmin, fncount, grcount, fail = _maximise_over_log(z0, vg, maxit, n_log)
+    t = z.copy()
+    t[:n_log] = np.exp(z[:n_log])
+    par_v, noise_v, Z_v = split(t)
+    par = tuple(float(v) for v in par_v)
+    return {"par": par, "noise": noise_v, "Z": Z_v, "value": -fmin, "counts": (fncount, grcount), "convergence": fail,
+            "func": _func_of(name, par)}
 
 
 def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_grad=None, ctx=None):

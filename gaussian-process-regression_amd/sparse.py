@@ -9,7 +9,9 @@ of rows -- never the n x n matrix, never X (gprc_sgpr_* of include/gprc_native.h
     elbo = -n/2 log(2 pi noise) - sum_j log (L_B)_jj - y^T y / (2 noise) + c^T c / 2 - trace / (2 noise)
     predict: v* = L_u^-1 k(Z,x*),  w* = L_B^-1 v*,  mean = w*^T c,  var = k(x*,x*) - |v*|^2 + |w*|^2   (the latent variance)
 
-Out of scope here: gradients of the bound and an optimiser over it, FITC, the full predictive covariance, several devices.
+The bound's exact gradient (kernel parameters, noise, Z) and the optimiser over it are fit.elbo_grad and fit.optimize_sparse
+(gprc_sgpr_elbo_grad; DESIGN.md section 7, "Sparse GPR gradient").  Out of scope here: FITC, the full predictive covariance, several
+devices.
 """
 from __future__ import annotations
 

@@ -250,6 +250,28 @@ GPRC_API int gprc_sgpr_fit(gprc_ctx* ctx, int kernel, const double* params, int 
 /* The objective without keeping a model: *elbo_out and (may be NULL) *trace_out = t, the bits gprc_sgpr_fit + gprc_sgpr_get_elbo give */
 GPRC_API int gprc_sgpr_elbo(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
                             const double* y, double noise, const double* Z, int64_t m, double jitter, double* elbo_out, double* trace_out);
+/* The bound AND its exact gradient with respect to the kernel parameters, the noise and the inducing points (no reference
+ * counterpart; DESIGN.md section 7, "Sparse GPR gradient").  Arguments as gprc_sgpr_elbo; kernels as gprc_gpr_logp_grad (sqrexp,
+ * gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52, matern32_ard, matern52_ard; any other id: GPRC_ERR_ARG).
+ *   *elbo_out   the bits gprc_sgpr_elbo returns
+ *   grad_out    n_params + 1 doubles, HOST: d elbo / d params[k] in the ABI's order, then d elbo / d noise (noise = sigma^2)
+ *   dZ_out      d x m doubles in Z's layout, host or device, or NULL: d elbo / d Z[c, j].  With NULL the column sums are not formed
+ *               (another instantiation of the contraction kernel); grad_out has the same bits either way.
+ * With q = L_B^-T c, mu = L_u^-T q, r = y - V q:
+ *   G_fu = [ V (I - B^-1) L_u^-1 + r mu^T ] / sigma^2,   G_uu = 1/2 L_u^-T (2 I - B^-1 - B) L_u^-1 - 1/2 mu mu^T
+ *   d elbo / d theta = sum_ij G_fu,ij dk(x_i,z_j)/d theta + sum_jk G_uu,jk dk(z_j,z_k)/d theta       (the jitter is a constant)
+ *   d elbo / d z_jc  = sum_i G_fu,ij dk(x_i,z_j)/d z_jc + 2 sum_k G_uu,jk dk(z_k,z_j)/d z_jc
+ *   d elbo / d sigma^2 = [ -n + m - tr B^-1 - c^T c - q^T q ] / (2 sigma^2) + [ y^T y + t ] / (2 sigma^4)      (host, long double)
+ * Whitened throughout: no K_uu^-1 is formed.  FLOP: the fit (2 n m^2) plus a second pass over the training points with one more
+ * row solve (n m^2) and one n x m x m product (2 n m^2), about 14 m^3 for the m x m algebra, and the contraction (n m (3 d + 50), exp-bound):
+ * 2.5 x the fit at n >> m.  MEMORY: the fit's, plus B once more (packed) and four m_pad^2 matrices (m_pad = gprc_pad(m)); the second
+ * pass keeps V and G_fu of a chunk side by side in the context's chunk workspace, so its chunks have half the rows of the fit's --
+ * never n x n, never X.  info > 0 as gprc_sgpr_fit.
+ * Two calls give the same bits (no atomics; the order of summation is fixed by the chunking: K_uu's part, then the chunks in order).
+ * Another chunking (GPRC_CHUNK_BYTES) sums in another order: the gradient then agrees to rounding, the bound bit for bit. */
+GPRC_API int gprc_sgpr_elbo_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                                 const double* y, double noise, const double* Z, int64_t m, double jitter, double* elbo_out,
+                                 double* grad_out, double* dZ_out);
 /* At x*: v* = L_u^-1 k(Z,x*), w* = L_B^-1 v*, mean = w*^T c, var = k(x*,x*) - |v*|^2 + |w*|^2 -- the LATENT variance, without the noise,
  * as gprc_gpr_predict(pointwise = 1).  X_star: d x n_star; mean_out, var_out: n_star doubles, host or device; either may be NULL, not
  * both.  Chunked over the test points, O(m^2) flop per point, chunk-invariant bit for bit. */
@@ -412,6 +434,14 @@ GPRC_API int gprc_dev_gemm_nt(gprc_ctx* ctx, double* C, int64_t ldc, const doubl
  * r1 + r2 rows gives the bits of two calls with r1, then r2 rows. */
 GPRC_API int gprc_dev_gram_rows(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t rows, int64_t n_pad, double* packed);
 GPRC_API int gprc_dev_col_reduce(gprc_ctx* ctx, const double* vt, int64_t ld, int64_t rows, int64_t cols, const double* w, double* out);
+/* The contraction kernel of gprc_sgpr_elbo_grad alone, on a caller-supplied matrix.  G: DEVICE, column-major with pitch ld, allocated
+ * for ceil(rows / 128) * 128 rows and ceil(cols / 64) * 64 columns (what lies past rows x cols is never used), 16-byte aligned, ld even;
+ * A: d x rows and Z: d x cols, DEVICE, one point per column; kernels as gprc_gpr_logp_grad.
+ *   grad_out[k] = f * sum_ij G_ij dk(a_i, z_j) / d params[k]            n_params doubles, HOST
+ *   dZ[c + d j] += f * sum_i G_ij dk(a_i, z_j) / d z_jc                 d x cols doubles, DEVICE, ADDED to; NULL: not formed
+ * Synchronous (grad_out is complete on return).  Fixed order of summation, no atomics: the same bits on every call. */
+GPRC_API int gprc_dev_cross_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* G, int64_t ld, const double* A,
+                                 int64_t rows, const double* Z, int64_t cols, int64_t d, double f, double* grad_out, double* dZ);
 
 /* ---- multi-GPU from ONE process (SURVEY 8b "Threading", 8e): the form the R `.Call` boundary can use ------------ *
  * The reference's host is a single R process; it cannot be forked per GPU.  A gprc_mgpu drives G ranks -- one per

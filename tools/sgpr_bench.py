@@ -14,6 +14,17 @@ Per m one JSON line:
                   rounded to 256 (alone_K), the same tiles and the same flop count for both, both pitches off the powers of two;
                   median of REPS launches each, timed by the in-library event profiler, and the (min, max) of each: the yardstick is the
                   NT launch of this run, and a gap counts when it exceeds the NT launch's own spread
+Gradient mode, the same inputs and sizes:
+    python tools/sgpr_bench.py grad                    # appends to profiles/sgpr_grad_bench.txt
+    python tools/sgpr_bench.py grad 262144 2048        # n, then the m's named
+Per m one JSON line:
+  elbo_ms / grad_ms / grad_noz_ms   median of 2 calls after a warm-up of gprc_sgpr_elbo, gprc_sgpr_elbo_grad with dZ and without, of the SAME
+                  run; ratio = grad_ms / elbo_ms (the flop count says 2 to 3: written down as an expectation, not a gate)
+  contract_ms, contract_gpairs      the contraction launches of one further gprc_sgpr_elbo_grad under the in-library event profiler (kind
+                  16, shared with the exact gradient's contraction: nothing else of this call counts there) and the point pairs per
+                  nanosecond they weigh -- (n + m_pad) m_pad pairs per coordinate group of 3, ceil(d / 3) groups
+  fill_ms, fill_gpairs              the fills of the same call (K_uu's panels and the cross fill of both passes) and their pairs per nanosecond:
+                  the contraction's yardstick, one exp per pair on both sides
 """
 import ctypes as C
 import json
@@ -62,7 +73,59 @@ def alone(lib, ctx, m_pad, K):
     return gram, nt
 
 
+def grad_main(args):
+    n = args[0] if args else 1 << 20
+    ms = args[1:] or [2048, 8192, 16384]
+    lib = nat.lib()
+    ctx = nat.Context(0)
+    d, noise, jitter = 8, 0.1, 1e-6
+    dev = torch.device("cuda:0")
+    theta = 1.0 + np.arange(d) / 16.0
+    _, pp, npar = nat.params_array(theta)
+    Xh, yh = synth(n, d)
+    X, y = torch.from_numpy(Xh).to(dev), torch.from_numpy(yh).to(dev)
+    torch.cuda.synchronize()
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sgpr_grad_bench.txt")
+    for m in ms:
+        m_pad = int(lib.gprc_pad(m))
+        idx = np.sort(np.random.default_rng(m).choice(n, size=m, replace=False))
+        Z = torch.from_numpy(np.ascontiguousarray(Xh[idx])).to(dev)
+        dZ = torch.empty((m, d), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        e, g = C.c_double(), np.empty(npar + 1)
+        common = (ctx.handle, nat.SQREXP_ARD, pp, npar, X.data_ptr(), d, n, y.data_ptr(), noise, Z.data_ptr(), m, jitter, C.byref(e))
+
+        def elbo():
+            nat.check(lib.gprc_sgpr_elbo(*common, None))
+
+        def grad(with_z=True):
+            nat.check(lib.gprc_sgpr_elbo_grad(*common, g.ctypes.data, dZ.data_ptr() if with_z else None))
+
+        elbo_ms = statistics.median(timed(elbo, 2))
+        grad_ms = statistics.median(timed(grad, 2))
+        noz_ms = statistics.median(timed(lambda: grad(False), 2))
+        lib.gprc_prof_enable(1)
+        lib.gprc_prof_reset()
+        grad()
+        prof = nat.prof_summary()
+        lib.gprc_prof_enable(0)
+        groups = -(-d // 3)
+        pairs_c, pairs_f = (n + m_pad) * m_pad * groups, (2 * n + m_pad) * m_pad
+        c_ms, f_ms = prof["grad_contract"]["ms"], prof["fill"]["ms"]
+        rec = dict(mode="grad", n=n, m=m, m_pad=m_pad, d=d, elbo_ms=round(elbo_ms, 2), grad_ms=round(grad_ms, 2), grad_noz_ms=round(noz_ms, 2),
+                   ratio=round(grad_ms / elbo_ms, 2), expected_ratio="2 to 3", elbo=e.value, contract_ms=round(c_ms, 2),
+                   contract_launches=prof["grad_contract"]["count"], contract_gpairs=round(pairs_c / c_ms / 1e6, 2), fill_ms=round(f_ms, 2),
+                   fill_gpairs=round(pairs_f / f_ms / 1e6, 2), grad_abs_max=float(np.abs(g).max()), dZ_abs_max=float(dZ.abs().max()))
+        line = json.dumps(rec)
+        print(line, flush=True)
+        with open(path, "a") as f:
+            f.write(line + "\n")
+        nat.check(lib.gprc_ctx_trim(ctx.handle))
+
+
 def main():
+    if sys.argv[1:2] == ["grad"]:
+        return grad_main([int(a) for a in sys.argv[2:]])
     args = [int(a) for a in sys.argv[1:]]
     n = args[0] if args else 1 << 20
     ms = args[1:] or [2048, 8192, 16384]
