@@ -180,5 +180,6 @@ int make_spec(int kernel, const double* params, int n_params, int64_t d, KernelS
 void free_model(gprc_model* m);
 struct ModelFree { void operator()(gprc_model* m) const { free_model(m); } };
 using ModelPtr = std::unique_ptr<gprc_model, ModelFree>;   // owns a model: every return frees it unless release() has handed it on
+int ensure_reversed_factor(gprc_model* m);   // packed_rev / winv_rev of a model that owns its buffers, built once and kept
 
 }  // namespace gprc

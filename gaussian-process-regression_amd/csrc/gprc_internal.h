@@ -6,10 +6,12 @@
 //                   the gprc_dev_* building blocks
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
 //   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound and its gradient, predict) and its entry points
+//   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create and eval) and their entry points
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
-// kernels_sgrad.hip, the kernel-id dispatcher and the set of kernels with an exact gradient).
+// kernels_sgrad.hip, the kernel-id dispatcher and the set of kernels with an exact gradient; kernels_paths.hip takes the tile
+// extents, the staging and the dispatcher from it and has its own lane layout, the MFMA operand's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -152,6 +154,22 @@ int launch_pred_grad(hipStream_t s, const KernelSpec& ks, const double* Xs, int6
                      int64_t d, const double* alpha, const double* W, int64_t ldw, double* pmean, double* pvar);
 int launch_pred_grad_sum(hipStream_t s, const KernelSpec& ks, const double* part, int64_t n_pad, int64_t d, int64_t m_pad, int64_t m, bool variance,
                          double* out);
+
+// ---- launchers (kernels_paths.hip) -------------------------------------------------------------
+// the generated-operand GEMM of the posterior sample paths, one chunk of rows (rows_pad = pad_up(rows, 128)):
+//   out[i + s ld] = (accumulate ? out[i + s ld] : 0) + scale * sum_j g(a_i, b_j) B[j + s ldb],   i < rows, s < S, j < cols
+// ks == nullptr: g = cospi(2 (sum_c Bp[c, j] a_i[c] + phase[j])), Bp the frequencies in cycles; else g = ks's kernel of the points a_i and
+// Bp[, j] (those of with_gradient_kernel).  part: gen_gemm_stripes(cols) x S x rows_pad doubles; the stripes are a function of cols only
+// and are added in order, so a row's bits do not depend on the other rows of the call.  Profiled as PK_PRED_GRAD.
+int64_t gen_gemm_stripes(int64_t cols);
+int launch_gen_gemm(hipStream_t s, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows,
+                    int64_t rows_pad, int64_t d, const double* B, int64_t ldb, int64_t S, double scale, bool accumulate, double* part, double* out,
+                    int64_t ld);
+// vt[s + j ldv] = y_j - F[j + (s0 + s) ldf] - sqn E[j + (s0 + s) lde] for s < scur, j < n, zero up to m_pad x n_pad: the rows of a solve chunk
+int launch_paths_residual(hipStream_t s, const double* y, const double* F, int64_t ldf, const double* E, int64_t lde, double sqn, int64_t s0,
+                          int64_t scur, int64_t n, int64_t m_pad, int64_t n_pad, double* vt, int64_t ldv);
+// U[j + (s0 + s) ldu] = vt[s + (n_pad - 1 - j) ldv], s < scur, j < n: out of the column-reversed solved chunk
+int launch_paths_weights(hipStream_t s, const double* vt, int64_t ldv, int64_t n_pad, int64_t s0, int64_t scur, int64_t n, double* U, int64_t ldu);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

@@ -528,7 +528,10 @@ int inverse_diagonal(gprc_model* m, double* kinv) {
   return 0;
 }
 
+}  // namespace
+
 // The reversed factor of a model (kernels_vec.hip, reverse_factor_kernel), built on the first call that needs it and kept
+// (gprc_gpr_predict_grad here, gprc_gpr_paths_create in gprc_paths.hip)
 int ensure_reversed_factor(gprc_model* m) {
   if (m->packed_rev && m->winv_rev) return 0;
   gprc_ctx* ctx = m->ctx;
@@ -548,8 +551,6 @@ int ensure_reversed_factor(gprc_model* m) {
   m->winv_rev = (double*)wr;
   return 0;
 }
-
-}  // namespace
 
 }  // namespace gprc
 

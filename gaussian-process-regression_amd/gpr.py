@@ -198,6 +198,37 @@ class GPR:
         self._L = None
         return self
 
+    def sample_paths(self, n_paths, n_features=1024, *, rng=None, nu=None, phase=None, w=None, e=None):
+        """n_paths functions drawn from the posterior by pathwise conditioning (gprc_gpr_paths_create; no reference counterpart): a prior
+        function from n_features random Fourier features plus one data-dependent update (Matheron's rule).  Returns a
+        sampling.SamplePaths: `paths(X_star)` gives the n* x n_paths values at any points, at O(n_features + n) per point and path, with
+        no n* x n* covariance; it describes the posterior now and survives add_data and close.  The mean of the paths is the exact
+        posterior mean; their covariance is the posterior's up to the finite-feature error of the prior.
+        Randomness is the caller's: `rng` (a numpy Generator) draws, in this order and only what is not given, nu (d x n_features, cycles:
+        sampling.spectral_frequencies), phase (n_features, turns, uniform on [0, 1)), w (n_features x n_paths) and e (n x n_paths), the
+        last two standard normal and filled column by column.  Kernels: sqrexp, sqrexp_ard, rationalquadratic and the four Matern
+        kernels (gammaexp has no frequency sampler here: pass nu)."""
+        from .sampling import SamplePaths, spectral_frequencies
+        if self._mmodel is not None:
+            raise ValueError("sample_paths: a model fitted over several devices has no sample paths; refit GPR on one device")
+        d, n = self._X.shape
+        S, D = int(n_paths), int(n_features)
+        if S < 1 or D < 1:
+            raise ValueError("n_paths >= 1, n_features >= 1 are not all TRUE")
+        rng = rng if rng is not None else np.random.default_rng()
+        if nu is None:
+            nu = spectral_frequencies(self._k, d, D, rng)
+        elif self._k.gprc_kernel[0] in (nat.CONSTANT, nat.LINEAR, nat.POLYNOMIAL):
+            raise ValueError("sample_paths: the kernel is not stationary (constant, linear and polynomial have no sample paths here)")
+        phase = rng.random(D) if phase is None else phase
+        w = rng.standard_normal((S, D)).T if w is None else w
+        e = rng.standard_normal((S, n)).T if e is None else e
+        nu = np.asfortranarray(np.asarray(nu, dtype=np.float64).reshape(d, D))
+        phase = np.ascontiguousarray(np.asarray(phase, dtype=np.float64).reshape(D))
+        w = np.asfortranarray(np.asarray(w, dtype=np.float64).reshape(D, S))
+        e = np.asfortranarray(np.asarray(e, dtype=np.float64).reshape(n, S))
+        return SamplePaths(self._model, d, nu, phase, w, e)
+
     def posterior_draws(self, n=5, limits=None, length_out=200, *, z=None, rng=None):
         """The data behind GPR$plot_posterior_draws(n = 5, limits = expand_range(X), length.out = 200)  --
         R/GPRclass.R:190-199 (one-dimensional inputs only, :192-195): test points, cbind(mean, diag(cov)) and n draws

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _native as nat
 
-__all__ = ["multivariate_normal", "expand_range", "mvn_factor", "sym_eigen"]
+__all__ = ["multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "spectral_frequencies", "SamplePaths"]
 
 
 def _sq(cov, what="covariance"):
@@ -87,3 +87,96 @@ def expand_range(x):
     lo, hi = float(x.min()), float(x.max())
     mid = (lo + hi) / 2.0
     return mid - 1.2 * (mid - lo), mid + 1.2 * (hi - mid)
+
+
+def spectral_frequencies(k, d, D, rng):
+    """Random Fourier frequencies of a stationary kernel: Nu (d x D, column-major, one frequency per column) in CYCLES, nu = omega / (2 pi)
+    with omega drawn from the kernel's spectral density, so that E cos(2 pi nu . r) = k(r).  With z ~ N(0, I_d):
+
+        sqrexp (l)                    omega = z / l
+        sqrexp_ard (l_1..l_d)         omega_c = z_c / l_c
+        matern32, matern52 (+ _ard)   omega = (z / l) sqrt(2 nu / g),   g ~ chi^2(2 nu),  nu = 3/2 or 5/2   (a multivariate t with 2 nu dof)
+        rationalquadratic (l, alpha)  omega = (z / l) sqrt(tau),        tau ~ Gamma(shape alpha, scale 1 / alpha)
+
+    gammaexp (an alpha-stable mixture), constant, linear and polynomial (not stationary) raise ValueError.
+    Order of the draws, so that a seed reproduces: first rng.standard_normal((D, d)) -- feature by feature, the d coordinates of a feature
+    together -- then, for the Matern kernels and rationalquadratic only, the D mixing variables in one call (rng.chisquare(2 nu, D) or
+    rng.gamma(alpha, 1 / alpha, D))."""
+    kid = k.gprc_kernel[0]
+    d, D = int(d), int(D)
+    par = np.atleast_1d(np.asarray(k.native_params(d), dtype=np.float64))
+    if D < 1:
+        raise ValueError("D >= 1 is not TRUE")
+    stationary = (nat.SQREXP, nat.SQREXP_ARD, nat.RATQUAD, nat.MATERN32, nat.MATERN52, nat.MATERN32_ARD, nat.MATERN52_ARD)
+    if kid == nat.GAMMAEXP:
+        raise ValueError("spectral_frequencies: gammaexp's spectral density (an alpha-stable mixture) is not implemented")
+    if kid not in stationary:
+        raise ValueError("spectral_frequencies: the kernel is not stationary (constant, linear and polynomial have no spectral density)")
+    z = rng.standard_normal((D, d))
+    l = par if kid in nat.ARD_KERNELS else np.full(d, par[0])
+    omega = z / l[None, :]
+    if kid in (nat.MATERN32, nat.MATERN32_ARD, nat.MATERN52, nat.MATERN52_ARD):
+        dof = 3.0 if kid in (nat.MATERN32, nat.MATERN32_ARD) else 5.0
+        omega = omega * np.sqrt(dof / rng.chisquare(dof, D))[:, None]
+    elif kid == nat.RATQUAD:
+        alpha = par[1]
+        omega = omega * np.sqrt(rng.gamma(alpha, 1.0 / alpha, D))[:, None]
+    return np.asfortranarray(omega.T / (2.0 * np.pi))
+
+
+class SamplePaths:
+    """Posterior sample paths of a fitted GPR (GPR.sample_paths; gprc_gpr_paths_*): n_paths functions that can be evaluated at any points,
+    again and again.  They describe the posterior at creation and stay valid after GPR.add_data or GPR.close.  `paths(X_star)` returns
+    the n* x n_paths array of their values; `.weights` the n x n_paths matrix U of the update term; `.close()` releases the device memory
+    (also a context manager)."""
+
+    def __init__(self, model_handle, d, nu, phase, w, e):
+        self._h = C.c_void_p()
+        self._d = int(d)
+        D, S = w.shape
+        nat.check(nat.lib().gprc_gpr_paths_create(model_handle, nu.ctypes.data, phase.ctypes.data, D, w.ctypes.data, e.ctypes.data, S,
+                                                  C.byref(self._h)))
+        self.n, self.n_features, self.n_paths = e.shape[0], D, S
+
+    def _handle(self):
+        if not self._h:
+            raise nat.GprcError(nat.ERR_ARG, "sample paths already closed")
+        return self._h
+
+    def paths(self, X_star):
+        """f_s(X_star[, i]) as an n* x n_paths array; X_star as GPR.predict takes it"""
+        from .covfunc import as_points
+        d = self._d
+        Xs = np.asarray(X_star)
+        if Xs.dtype.kind not in "fiub" or Xs.size % d:
+            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")
+        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
+        if Xs.shape[0] != d:
+            raise ValueError("X_star must have nrow(X) rows")
+        ns = Xs.shape[1]
+        out = np.empty((ns, self.n_paths), order="F")
+        nat.check(nat.lib().gprc_gpr_paths_eval(self._handle(), Xs.ctypes.data, ns, out.ctypes.data, ns))
+        return out
+
+    @property
+    def weights(self):
+        U = np.empty((self.n, self.n_paths), order="F")
+        nat.check(nat.lib().gprc_gpr_paths_get_weights(self._handle(), U.ctypes.data))
+        return U
+
+    def close(self):
+        if getattr(self, "_h", None):
+            nat.lib().gprc_gpr_paths_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

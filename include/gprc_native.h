@@ -210,6 +210,32 @@ GPRC_API int gprc_gpr_predict(gprc_model* model, const double* X_star, int64_t n
  * a kernel without a gradient (constant, linear, polynomial). */
 GPRC_API int gprc_gpr_predict_grad(gprc_model* model, const double* X_star, int64_t n_star, double* mean_out, double* var_out,
                                    double* dmean_out, double* dvar_out);
+/* Posterior sample paths by pathwise conditioning (Matheron's rule; Wilson et al. 2020; no reference counterpart): S functions drawn
+ * from the posterior of a fitted GPR model that can be evaluated anywhere, again and again, at O(D + n) per test point and path:
+ *   f_s(x) = sqrt(2 / D) sum_k cos 2 pi(nu_k . x + u_k) W[k, s]  +  sum_j k(x, x_j) U[j, s]
+ *   U[:, s] = K_y^-1 (y - sqrt(2 / D) Phi(X) W[:, s] - sqrt(noise) E[:, s]),     K_y = K + noise I
+ * with the model's stored noise (the variance, a jitter of the fit included) and its factor.  The caller draws, the library is
+ * deterministic: Nu (d x D, one frequency per column, in CYCLES: omega / 2 pi, from the kernel's spectral density), phase (D, in
+ * TURNS, uniform on [0, 1)), W (D x S) and E (n x S) standard normal, all column-major, host or device.  The mean of the paths over
+ * W and E is the exact posterior mean whatever the features.
+ * create computes U once (the model's row solve on S right-hand sides, then the same with the REVERSED factor: memory and failure text
+ * of that second copy of the factor exactly as for gprc_gpr_predict_grad's variance gradient, and kept in the model likewise).  A
+ * gprc_paths holds its own copies of X, the kernel, Nu, phase, W and U: it describes the posterior AT CREATION and stays valid after
+ * gprc_gpr_extend or gprc_model_free of the model; it dies with gprc_gpr_paths_free.  After its context is destroyed every call on it
+ * but free and dims returns GPRC_ERR_ARG.
+ * eval: out[i + s ld_out] = f_s(X_star[, i]), n_star x S column-major; X_star (d x n_star) and out host or device.  Chunked over the
+ * test points, rows x S x (1 + stripes) doubles of workspace per chunk and no n_star x n buffer; bit for bit the same under every
+ * chunking, and for a point evaluated alone or in a batch.
+ * get_weights: U (n x S, column-major, host or device).  dims: any output may be NULL.
+ * GPRC_ERR_ARG, each with text: a GPC, sparse or borrowed model; a kernel outside GPRC_SQREXP, GPRC_SQREXP_ARD, GPRC_GAMMAEXP,
+ * GPRC_RATQUAD and the four Matern ids; D < 1, S < 1, n_star < 1, null pointers; ld_out < n_star. */
+typedef struct gprc_paths gprc_paths;
+GPRC_API int gprc_gpr_paths_create(gprc_model* model, const double* Nu, const double* phase, int64_t D, const double* W, const double* E,
+                                   int64_t S, gprc_paths** paths_out);
+GPRC_API int gprc_gpr_paths_eval(gprc_paths* paths, const double* X_star, int64_t n_star, double* out, int64_t ld_out);
+GPRC_API int gprc_gpr_paths_get_weights(gprc_paths* paths, double* U_out);
+GPRC_API int gprc_gpr_paths_dims(const gprc_paths* paths, int64_t* n_out, int64_t* d_out, int64_t* D_out, int64_t* S_out);
+GPRC_API int gprc_gpr_paths_free(gprc_paths* paths);
 /* Append m observations (X_new: d x m, y_new: m) to a fitted GPR model in place of GPR$new on
  * cbind(X, X_new), c(y, y_new) with the model's kernel, parameters and stored $noise (jitter kept, never re-tried).
  * Only the factor's columns behind the last panel boundary n0 = floor(n / 512) 512 are recomputed: the new rows of the
@@ -442,6 +468,18 @@ GPRC_API int gprc_dev_col_reduce(gprc_ctx* ctx, const double* vt, int64_t ld, in
  * Synchronous (grad_out is complete on return).  Fixed order of summation, no atomics: the same bits on every call. */
 GPRC_API int gprc_dev_cross_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* G, int64_t ld, const double* A,
                                  int64_t rows, const double* Z, int64_t cols, int64_t d, double f, double* grad_out, double* dZ);
+/* The two generated-operand products of the sample paths alone (DEVICE pointers, synchronous):
+ *   out[i + s ld] = scale * sum_j g(a_i, b_j) B[j + s ldb],   i < rows, s < S, j < cols,   any rows, cols, S, d >= 1
+ * with the left operand never stored: each element is computed from the points in the lane that feeds it to v_mfma_f64_16x16x4_f64.
+ * A: d x rows, one point per column.
+ * feature_gemm: g = cos 2 pi(sum_c Nu[c, j] a_i[c] + phase[j]); Nu: d x D in cycles, phase: D in turns, B = W (D x S, pitch ldw >= D).
+ * kernel_gemm: g = k(a_i, b_j), Bpts: d x cols, B = U (cols x S, pitch ldu >= cols), scale 1; kernels as gprc_gpr_paths_create.
+ * j is added in ascending groups of four inside stripes that depend on cols alone, the stripes in order: fixed bits, and a row's
+ * result does not depend on which other rows are in the call. */
+GPRC_API int gprc_dev_feature_gemm(gprc_ctx* ctx, const double* Nu, const double* phase, int64_t D, const double* A, int64_t rows, int64_t d,
+                                   const double* W, int64_t ldw, int64_t S, double scale, double* out, int64_t ld);
+GPRC_API int gprc_dev_kernel_gemm(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* A, int64_t rows,
+                                  const double* Bpts, int64_t cols, int64_t d, const double* U, int64_t ldu, int64_t S, double* out, int64_t ld);
 
 /* ---- multi-GPU from ONE process (SURVEY 8b "Threading", 8e): the form the R `.Call` boundary can use ------------ *
  * The reference's host is a single R process; it cannot be forked per GPU.  A gprc_mgpu drives G ranks -- one per
@@ -529,7 +567,8 @@ GPRC_API int gprc_combine_all(gprc_ctx* ctx, const double* axis_values, const in
  * update (K=512), 6 trsv, 7 row reductions, 8 covariance SYRK, 9 derivative row sums, 10 Jacobi sweep, 11 predict
  * left-looking update, 12 trailing left-looking update, 13 fused panel factorisation, 14 fused in-panel solve of the predict, 15 inverse GEMM
  * (-L^-T L^-1, lower), 16 gradient contraction (gprc_gpr_logp_grad), 17 Laplace gradient contraction (gprc_gpc_logq_grad),
- * 18 factor reversal, 19 prediction-gradient contraction (gprc_gpr_predict_grad).  gprc_gpr_loo_grad adds no kind: its n^3 product is
+ * 18 factor reversal, 19 prediction-gradient contraction (gprc_gpr_predict_grad; the sample paths'
+ * generated-operand products are counted here too).  gprc_gpr_loo_grad adds no kind: its n^3 product is
  * counted under 8, its contraction under 17 and the builder of its scaled full inverse under 18.  flops/bytes are the ALGORITHMIC
  * figures of DESIGN.md for the launches seen, not counter readings. */
 GPRC_API int gprc_prof_enable(int on);
