@@ -149,11 +149,14 @@ PROTOTYPES = {
     "gprc_dev_cross_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, C.c_double, _vp, _vp]),
     "gprc_gpr_paths_create": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(_vp)]),
     "gprc_gpr_paths_eval": (C.c_int, [_vp, _vp, _i64, _vp, _i64]),
+    "gprc_gpr_paths_eval_grad": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64]),
     "gprc_gpr_paths_get_weights": (C.c_int, [_vp, _vp]),
     "gprc_gpr_paths_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_gpr_paths_free": (C.c_int, [_vp]),
     "gprc_dev_feature_gemm": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_double, _vp, _i64]),
     "gprc_dev_kernel_gemm": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64]),
+    "gprc_dev_feature_gemm_grad": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_double, _vp, _i64]),
+    "gprc_dev_kernel_gemm_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64]),
 }
 
 _lib = None

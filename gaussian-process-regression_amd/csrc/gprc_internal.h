@@ -6,12 +6,13 @@
 //                   the gprc_dev_* building blocks
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
 //   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound and its gradient, predict) and its entry points
-//   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create and eval) and their entry points
+//   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create, eval and eval_grad) and their entry points
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
 // kernels_sgrad.hip, the kernel-id dispatcher and the set of kernels with an exact gradient; kernels_paths.hip takes the tile
-// extents, the staging and the dispatcher from it and has its own lane layout, the MFMA operand's).
+// extents, the staging, the dispatcher and, for its gradient product, pair_weight from it and has its own lane layout, the MFMA
+// operand's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -165,6 +166,13 @@ int64_t gen_gemm_stripes(int64_t cols);
 int launch_gen_gemm(hipStream_t s, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows,
                     int64_t rows_pad, int64_t d, const double* B, int64_t ldb, int64_t S, double scale, bool accumulate, double* part, double* out,
                     int64_t ld);
+// its gradient with respect to the row points, one chunk of rows:
+//   dout[i + ld (s + S c)] = (accumulate ? dout[.] : 0) + d / da_i[c] of scale * sum_j g(a_i, b_j) B[j + s ldb],   c < d
+// part: gen_gemm_stripes(cols) x d x S x rows_pad doubles.  Same stripes, same order of summation, same independence of a row from the
+// other rows; the weight per pair is formed once and serves every coordinate (kernels_paths.hip).  Profiled as PK_PRED_GRAD.
+int launch_gen_gemm_grad(hipStream_t s, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows,
+                         int64_t rows_pad, int64_t d, const double* B, int64_t ldb, int64_t S, double scale, bool accumulate, double* part, double* dout,
+                         int64_t ld);
 // vt[s + j ldv] = y_j - F[j + (s0 + s) ldf] - sqn E[j + (s0 + s) lde] for s < scur, j < n, zero up to m_pad x n_pad: the rows of a solve chunk
 int launch_paths_residual(hipStream_t s, const double* y, const double* F, int64_t ldf, const double* E, int64_t lde, double sqn, int64_t s0,
                           int64_t scur, int64_t n, int64_t m_pad, int64_t n_pad, double* vt, int64_t ldv);

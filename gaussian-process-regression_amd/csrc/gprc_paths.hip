@@ -10,6 +10,8 @@
 // factor as predict_chunk's variance gradient does: (R L^-T L^-1) J, which paths_weights_kernel reads back into U.
 // eval: two products into the caller's array, the prior term first, the update added to it; rows in chunks sized by the context's
 // chunk budget.  Memory: rows x S x (1 + stripes) doubles per chunk; no n* x n and no n* x n* buffer.
+// eval_grad: the same two products differentiated with respect to the test point (gen_gemm_grad; the values, when asked for, by eval's
+// own two launches); rows x S x d x stripes doubles per chunk.  gprc_dev_feature_gemm_grad / gprc_dev_kernel_gemm_grad: each alone.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -64,6 +66,24 @@ int gen_gemm(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const double
   for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
     const int64_t mcur = std::min(chunk, rows - r0);
     GPRC_TRY(launch_gen_gemm(ctx->stream, ks, Bp, phase, cols, A + r0 * d, mcur, pad_up(mcur, PT_R), d, B, ldb, S, scale, accumulate, part.p, out + r0, ld));
+  }
+  return 0;
+}
+
+// Its gradient with respect to the rows' points: dout is rows x (S d), pitch ld.  A chunk's partials are rows x S x d x stripes doubles
+// inside the same budget, a chunk is never below one row tile, and the bits do not depend on the chunking either.
+int gen_gemm_grad(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows, int64_t d,
+                  const double* B, int64_t ldb, int64_t S, double scale, bool accumulate, double* dout, int64_t ld) {
+  const int64_t stripes = gen_gemm_stripes(cols);
+  const int64_t budget = (int64_t)std::min<size_t>(ctx->chunk_bytes, (size_t)1 << 30);
+  int64_t chunk = budget / ((int64_t)sizeof(double) * S * d * stripes) / PT_R * PT_R;
+  chunk = std::min(std::max<int64_t>(chunk, PT_R), pad_up(rows, PT_R));
+  DevMem part;
+  GPRC_TRY(part.alloc(stripes * S * d * chunk));
+  for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+    const int64_t mcur = std::min(chunk, rows - r0);
+    GPRC_TRY(launch_gen_gemm_grad(ctx->stream, ks, Bp, phase, cols, A + r0 * d, mcur, pad_up(mcur, PT_R), d, B, ldb, S, scale, accumulate, part.p,
+                                  dout + r0, ld));
   }
   return 0;
 }
@@ -148,6 +168,30 @@ int gprc_gpr_paths_eval(gprc_paths* p, const double* X_star, int64_t ns, double*
   return finish_sync(s, o);
 }
 
+int gprc_gpr_paths_eval_grad(gprc_paths* p, const double* X_star, int64_t ns, double* out, int64_t ld_out, double* dout, int64_t ld_dout) {
+  GPRC_TRY(paths_usable("paths_eval_grad", p));
+  if (ns < 1 || !X_star) { set_error("paths_eval_grad: bad arguments (n_star >= 1, non-null X_star)"); return GPRC_ERR_ARG; }
+  if (!dout) { set_error("paths_eval_grad: null dout (the values alone are gprc_gpr_paths_eval's)"); return GPRC_ERR_ARG; }
+  if (ld_dout < ns) { set_error("paths_eval_grad: ld_dout < n_star"); return GPRC_ERR_ARG; }
+  if (out && ld_out < ns) { set_error("paths_eval_grad: ld_out < n_star"); return GPRC_ERR_ARG; }
+  gprc_ctx* ctx = p->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const double scale = std::sqrt(2.0 / (double)p->D);
+  In xs;
+  Out o, g;
+  GPRC_TRY(xs.set(s, X_star, p->d * ns));
+  GPRC_TRY(g.set(dout, ld_dout, ns, p->S * p->d));
+  if (out) {   // the launches of gprc_gpr_paths_eval with its arguments: its bits
+    GPRC_TRY(o.set(out, ld_out, ns, p->S));
+    GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu, p->phase, p->D, xs.dev, ns, p->d, p->W, p->D, p->S, scale, false, o.dev, o.ld));
+    GPRC_TRY(gen_gemm(ctx, &p->ks, p->X, nullptr, p->n, xs.dev, ns, p->d, p->U, p->n, p->S, 1.0, true, o.dev, o.ld));
+  }
+  GPRC_TRY(gen_gemm_grad(ctx, nullptr, p->Nu, p->phase, p->D, xs.dev, ns, p->d, p->W, p->D, p->S, scale, false, g.dev, g.ld));
+  GPRC_TRY(gen_gemm_grad(ctx, &p->ks, p->X, nullptr, p->n, xs.dev, ns, p->d, p->U, p->n, p->S, 1.0, true, g.dev, g.ld));
+  return out ? finish_sync(s, g, &o) : finish_sync(s, g);
+}
+
 int gprc_gpr_paths_get_weights(gprc_paths* p, double* U_out) {
   GPRC_TRY(paths_usable("paths_get_weights", p));
   if (!U_out) { set_error("paths_get_weights: null output"); return GPRC_ERR_ARG; }
@@ -194,6 +238,27 @@ int gprc_dev_kernel_gemm(gprc_ctx* ctx, int kernel, const double* params, int n_
   KernelSpec ks;
   GPRC_TRY(make_spec(kernel, params, n_params, d, &ks));
   GPRC_TRY(gen_gemm(ctx, &ks, Bpts, nullptr, cols, A, rows, d, U, ldu, S, 1.0, false, out, ld));
+  GPRC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int gprc_dev_feature_gemm_grad(gprc_ctx* ctx, const double* Nu, const double* phase, int64_t D, const double* A, int64_t rows, int64_t d, const double* W,
+                               int64_t ldw, int64_t S, double scale, double* dout, int64_t ld) {
+  GPRC_TRY(use_device_unless(ctx, !Nu || !phase || !A || !W || !dout || D < 1 || rows < 1 || d < 1 || S < 1 || ldw < D || ld < rows,
+                             "dev_feature_gemm_grad: bad arguments"));
+  GPRC_TRY(gen_gemm_grad(ctx, nullptr, Nu, phase, D, A, rows, d, W, ldw, S, scale, false, dout, ld));
+  GPRC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int gprc_dev_kernel_gemm_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* A, int64_t rows, const double* Bpts,
+                              int64_t cols, int64_t d, const double* U, int64_t ldu, int64_t S, double* dout, int64_t ld) {
+  GPRC_TRY(use_device_unless(ctx, !A || !Bpts || !U || !dout || rows < 1 || cols < 1 || d < 1 || S < 1 || ldu < cols || ld < rows,
+                             "dev_kernel_gemm_grad: bad arguments"));
+  GPRC_TRY(check_grad_kernel("dev_kernel_gemm_grad", kernel));
+  KernelSpec ks;
+  GPRC_TRY(make_spec(kernel, params, n_params, d, &ks));
+  GPRC_TRY(gen_gemm_grad(ctx, &ks, Bpts, nullptr, cols, A, rows, d, U, ldu, S, 1.0, false, dout, ld));
   GPRC_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }

@@ -30,6 +30,10 @@
 //
 // Profiled under kind 19 (PK_PRED_GRAD, "prediction-gradient contraction"): like it, a contraction over pairs generated from the test
 // and the training points.  The number of kinds stays 20.
+//
+// The gradient of the product with respect to the row points (gprc_gpr_paths_eval_grad, gprc_dev_feature_gemm_grad,
+// gprc_dev_kernel_gemm_grad; DESIGN.md section 7, "Sample-path gradients and Thompson sampling") is gen_gemm_grad_kernel below: the same
+// operand form with one generated operand per coordinate, its own blocking, the same stripes and order of summation, the same kind.
 #include "pair_tile.h"
 
 #include <algorithm>
@@ -184,6 +188,191 @@ __global__ __launch_bounds__(256) void gen_gemm_sum_kernel(const double* part, i
   out[i + s * ld] = accumulate ? out[i + s * ld] + v : v;
 }
 
+// ---- the gradient with respect to the row points ---------------------------------------------------------------------------------
+//   part[((stripe d + c) S + s) rows_pad + i] = sum over the stripe's j of w(a_i, b_j) e_c(i, j) B[j + s ldb]
+// the product whose generated operand carries one more index, the coordinate c (gprc_gpr_paths_eval_grad, gprc_dev_*_gemm_grad):
+//   kernel     w = pair_weight<KID> (h of dk / da_c = -h (a_c - b_c) t_c without its pair-independent factor), e_c = a_ic - b_jc: the
+//              direct difference of the staged coordinates (ARD: both divided by l_c), never a_ic sum - sum b_jc
+//   features   w = sinpi(2 t), t as gen_gemm_kernel forms it, e_c = Nu[c, j]
+// w is formed ONCE per pair; then per coordinate one multiply (the kernel's difference before it) and ceil(ns / 16) x 2 MFMAs, the
+// operand in the lane as above.  The accumulators are coordinates x rows x sample columns, so a workgroup owns PGR_C = 4 coordinates and
+// PGR_SB = 32 sample columns of one row tile and one stripe: 4 x 2 x 2 double4 = 128 registers.  A column tile goes through in two
+// halves of PGR_TC = 32 columns, in order, so that the squared distances take 32 registers and not 64: with 64 five of the nine
+// instantiations needed more than 256 registers and ran one wave per SIMD; now all stay at two (profiles/paths_grad_isa.txt; eight
+// coordinates a workgroup would halve the generator's work and run one wave).  Further coordinate groups and sample blocks are
+// further workgroups (blockIdx.z = group * sblocks + block) that form the distance again, as pred_grad_kernel does for d > 8.  The
+// group's own coordinates of the column points are staged a second time (Bz), the lane's own of its two rows stay in registers.
+// Any d: the distance takes ceil(d / PT_D) staging passes before w is known.  Order of summation as gen_gemm_kernel: j ascending in
+// groups of four, tile after tile, one partial per (stripe, c, s, i); gen_gemm_grad_sum_kernel adds the stripes in order and applies
+// the pair-independent factor once.  No atomics, no scratch.
+constexpr int PGR_C = 4;
+constexpr int PGR_SB = 32;
+constexpr int PGR_TC = 32;   // columns staged at a time: half a column tile, so that the squared distances take 32 registers, not 64
+constexpr int PGR_LDB = PGR_TC + 2;
+
+struct GenGradArgs {
+  const double* A;       // d x rows
+  const double* Bp;      // d x cols
+  const double* phase;   // cols (features only)
+  const double* B;       // cols x S, pitch ldb
+  double* part;          // stripes x d x S x rows_pad
+  int64_t rows, cols, d, ldb, S, rows_pad;
+  int64_t stripe_tiles, ntiles, sblocks;
+  KernelSpec ks;
+};
+
+template <int GEN>
+__global__ __launch_bounds__(256) void gen_gemm_grad_kernel(GenGradArgs a) {
+  __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];
+  __shared__ double Bs[PGR_TC][PT_D + 1];
+  __shared__ __attribute__((aligned(16))) double Bt[PGR_SB][PGR_LDB];   // Bt[s][j]: the half tile's block of B
+  __shared__ double Bz[PGR_TC][PGR_C + 1];                             // the group's own coordinates of the half tile's column points
+  __shared__ double Ph[PGR_TC];
+  constexpr bool FEAT = GEN == GEN_FEATURES;
+  constexpr bool ARD = !FEAT && is_ard(GEN);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+  const int64_t ti = (int64_t)blockIdx.x * PT_R;
+  const int64_t stripe = blockIdx.y;
+  const int64_t zg = (int64_t)blockIdx.z / a.sblocks;
+  const int64_t z0 = zg * PGR_C;
+  const int64_t sb0 = ((int64_t)blockIdx.z - zg * a.sblocks) * PGR_SB;
+  const int dz = (int)((a.d - z0 < PGR_C) ? (a.d - z0) : PGR_C);        // coordinates and sample columns of this workgroup, uniform
+  const int ns = (int)((a.S - sb0 < PGR_SB) ? (a.S - sb0) : PGR_SB);
+  const bool two = ns > 16;
+  const int64_t tile0 = stripe * a.stripe_tiles;
+  const int64_t tile1 = (tile0 + a.stripe_tiles < a.ntiles) ? tile0 + a.stripe_tiles : a.ntiles;
+  const int i0 = wave * 32 + fr, i1 = i0 + 16;                       // the lane's two rows of the tile
+
+  double xa0[PGR_C], xa1[PGR_C];   // kernel generators: the lane's own coordinates of its two rows, as staged
+#pragma unroll
+  for (int c = 0; c < PGR_C; ++c) {
+    xa0[c] = xa1[c] = 0.0;
+    if constexpr (!FEAT) {
+      if (c < dz) {
+        const double sc = ARD ? a.ks.p[z0 + c] : 1.0;
+        if (ti + i0 < a.rows) xa0[c] = a.A[(ti + i0) * a.d + z0 + c] * sc;
+        if (ti + i1 < a.rows) xa1[c] = a.A[(ti + i1) * a.d + z0 + c] * sc;
+      }
+    }
+  }
+
+  double4_t acc[PGR_C][2][2];
+#pragma unroll
+  for (int c = 0; c < PGR_C; ++c)
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) acc[c][m][q] = double4_t{0.0, 0.0, 0.0, 0.0};
+
+  constexpr int HALVES = PT_C / PGR_TC, NKK = PGR_TC / 4;
+  for (int64_t sub = tile0 * HALVES; sub < tile1 * HALVES; ++sub) {   // the halves of the stripe's column tiles in order
+    const int64_t tj = sub * PGR_TC;
+    double s0[NKK], s1[NKK];   // per group of four columns kk: the lane's pair (i0 | i1, column 4 kk + fk)
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) { s0[kk] = 0.0; s1[kk] = 0.0; }
+    for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {
+      const int dc = (int)((a.d - r0 < PT_D) ? (a.d - r0) : PT_D);
+      __syncthreads();
+      if (a.d > PT_D || sub == tile0 * HALVES) {   // (d <= 16: the row points' only chunk stays in LDS for the whole stripe)
+        stage_points<ARD>(a.A, ti, a.rows, a.d, r0, dc, PT_R, a.ks.p, t, [&](int i, int r, double v) { As[r][i] = v; });
+      }
+      stage_points<ARD>(a.Bp, tj, a.cols, a.d, r0, dc, PGR_TC, a.ks.p, t, [&](int j, int r, double v) { Bs[j][r] = v; });
+      if (r0 == 0) {
+        for (int e = t; e < PGR_SB * PGR_TC; e += 256) {   // 32 consecutive j of one sample column per half wave
+          const int sc = e / PGR_TC, j = e % PGR_TC;
+          Bt[sc][j] = (sc < ns && tj + j < a.cols) ? a.B[(tj + j) + (sb0 + sc) * a.ldb] : 0.0;
+        }
+        stage_points<ARD>(a.Bp, tj, a.cols, a.d, z0, dz, PGR_TC, a.ks.p, t, [&](int j, int r, double v) { Bz[j][r] = v; });
+        if constexpr (FEAT) {
+          if (t < PGR_TC) Ph[t] = (tj + t < a.cols) ? a.phase[tj + t] : 0.0;
+        }
+      }
+      __syncthreads();
+      for (int r = 0; r < dc; ++r) {
+        const double a0 = As[r][i0], a1 = As[r][i1];
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) {
+          const double b = Bs[4 * kk + fk][r];
+          if constexpr (FEAT) {
+            s0[kk] = fma(a0, b, s0[kk]);
+            s1[kk] = fma(a1, b, s1[kk]);
+          } else {
+            const double t0 = a0 - b, t1 = a1 - b;
+            s0[kk] = fma(t0, t0, s0[kk]);
+            s1[kk] = fma(t1, t1, s1[kk]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) {
+      const int j = 4 * kk + fk;
+      double w0, w1;
+      if constexpr (FEAT) {
+        const double ph = Ph[j];
+        w0 = sinpi(2.0 * (s0[kk] + ph));
+        w1 = sinpi(2.0 * (s1[kk] + ph));
+      } else {
+        w0 = pair_weight<GEN>(s0[kk], a.ks);
+        w1 = pair_weight<GEN>(s1[kk], a.ks);
+      }
+      const double b0 = Bt[fr][j], b1 = Bt[16 + fr][j];   // zero in the padding of j and of s
+#pragma unroll
+      for (int c = 0; c < PGR_C; ++c) {
+        if (c < dz) {
+          const double bz = Bz[j][c];
+          double g0, g1;
+          if constexpr (FEAT) {
+            g0 = w0 * bz;
+            g1 = w1 * bz;
+          } else {
+            g0 = w0 * (xa0[c] - bz);
+            g1 = w1 * (xa1[c] - bz);
+          }
+          acc[c][0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, g0, acc[c][0][0], 0, 0, 0);
+          acc[c][1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, g1, acc[c][1][0], 0, 0, 0);
+          if (two) {
+            acc[c][0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, g0, acc[c][0][1], 0, 0, 0);
+            acc[c][1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, g1, acc[c][1][1], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+
+  // acc[c][m][q][reg] = element (coordinate z0 + c, s = sb0 + 16 q + fk + 4 reg, i = ti + wave 32 + 16 m + fr): rows < rows_pad always,
+  // coordinates and columns guarded
+#pragma unroll
+  for (int c = 0; c < PGR_C; ++c)
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int sc = 16 * q + fk + 4 * reg;
+        if (c < dz && sc < ns) {
+          double* dst = a.part + ((stripe * a.d + z0 + c) * a.S + sb0 + sc) * a.rows_pad + ti;
+          dst[i0] = acc[c][0][q][reg];
+          dst[i1] = acc[c][1][q][reg];
+        }
+      }
+}
+
+// dout[i + ld (s + S c)] = (accumulate ? dout[.] : 0) + f_c * (the stripes of part[((st d + c) S + s) rows_pad + i] in order),
+// f_c = sign * (ard ? iso * ks.p[c] : iso) as pred_grad_sum_kernel forms it
+__global__ __launch_bounds__(256) void gen_gemm_grad_sum_kernel(const double* part, int64_t stripes, int64_t d, int64_t S, int64_t rows_pad, int64_t rows,
+                                                                double sign, double iso, int ard, KernelSpec ks, int accumulate, double* dout,
+                                                                int64_t ld) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;   // rows fastest: the partials are read contiguously
+  if (idx >= rows * S * d) return;
+  const int64_t cs = idx / rows, i = idx - cs * rows;             // cs = s + S c
+  const int64_t c = cs / S, s = cs - c * S;
+  double v = 0.0;
+  for (int64_t st = 0; st < stripes; ++st) v += part[((st * d + c) * S + s) * rows_pad + i];
+  v *= sign * (ard ? iso * ks.p[c] : iso);
+  dout[i + cs * ld] = accumulate ? dout[i + cs * ld] + v : v;
+}
+
 // the rows of a solve chunk from the prior term F (n x S, pitch ldf):  vt[s + j ldv] = y_j - F[j, s0 + s] - sqn E[j, s0 + s] for
 // s < scur, j < n; zero in the padding (s < m_pad, j < n_pad)
 __global__ __launch_bounds__(256) void paths_residual_kernel(const double* y, const double* F, int64_t ldf, const double* E, int64_t lde, double sqn,
@@ -237,6 +426,38 @@ int launch_gen_gemm(hipStream_t s, const KernelSpec* ks, const double* Bp, const
   GPRC_LAUNCH_CHECK();
   hipLaunchKernelGGL(gen_gemm_sum_kernel, dim3((unsigned)((rows * S + 255) / 256)), dim3(256), 0, s, part, stripes, S, rows_pad, rows, scale,
                      accumulate ? 1 : 0, out, ld);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_gen_gemm_grad(hipStream_t s, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows,
+                         int64_t rows_pad, int64_t d, const double* B, int64_t ldb, int64_t S, double scale, bool accumulate, double* part, double* dout,
+                         int64_t ld) {
+  if (rows < 1 || cols < 1 || S < 1 || d < 1 || rows_pad % PT_R || rows_pad < rows || ldb < cols || ld < rows || !A || !Bp || !B || !part || !dout ||
+      (!ks && !phase)) {
+    set_error("gen_gemm_grad: bad arguments");
+    return GPRC_ERR_ARG;
+  }
+  if (ks) GPRC_TRY(check_grad_kernel("kernel_gemm_grad", ks->id));
+  const int64_t sblocks = (S + PGR_SB - 1) / PGR_SB, zgroups = (d + PGR_C - 1) / PGR_C;
+  if (sblocks * zgroups > 65535) { set_error("gen_gemm_grad: too many coordinates times sample columns"); return GPRC_ERR_ARG; }
+  const int64_t cols_pad = pad_up(cols, PT_C), stripes = gen_gemm_stripes(cols);
+  const KernelSpec ds = ks ? make_deriv_spec(*ks) : KernelSpec{};
+  GenGradArgs a{A, Bp, phase, B, part, rows, cols, d, ldb, S, rows_pad, stripe_tiles_of(cols_pad), cols_pad / PT_C, sblocks, ds};
+  const dim3 grid((unsigned)(rows_pad / PT_R), (unsigned)stripes, (unsigned)(sblocks * zgroups));
+  // per pair and workgroup of (coordinate group, sample block): the distance or the phase (3 d), the weight (~40), two flops per
+  // coordinate for the operand; 2 flops per sample column and coordinate on the MFMA
+  const double pairs = (double)rows_pad * (double)cols_pad;
+  ProfScope ps(s, PK_PRED_GRAD, pairs * ((3.0 * d + 40.0 + 2.0 * PGR_C) * sblocks * zgroups + 2.0 * S * d),
+               8.0 * ((double)(rows + cols) * d + (double)cols * S + (double)rows * S * d * (stripes + 1)));
+  if (!ks) hipLaunchKernelGGL((gen_gemm_grad_kernel<GEN_FEATURES>), grid, dim3(256), 0, s, a);
+  else with_gradient_kernel(ks->id, [&](auto kid) { hipLaunchKernelGGL((gen_gemm_grad_kernel<decltype(kid)::value>), grid, dim3(256), 0, s, a); });
+  GPRC_LAUNCH_CHECK();
+  // d / da_c of the value product: -t_c h (a_c - b_c) for a kernel (deriv_tail_factor, ARD's second 1 / l_c from the derived spec),
+  // -2 pi nu_c sin 2 pi t for the features; times `scale`
+  const double iso = (ks ? deriv_tail_factor(*ks) : 6.283185307179586476925) * scale;
+  hipLaunchKernelGGL(gen_gemm_grad_sum_kernel, dim3((unsigned)((rows * S * d + 255) / 256)), dim3(256), 0, s, part, stripes, d, S, rows_pad, rows, -1.0, iso,
+                     (ks && is_ard(ks->id)) ? 1 : 0, ds, accumulate ? 1 : 0, dout, ld);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

@@ -28,7 +28,8 @@
 // per (stripe, coordinate, row); the stripes are added in order by pred_grad_sum_kernel.  No atomics.  The stripe is a function of
 // n_pad alone, so a row's result does not depend on how the test points are chunked, bit for bit.
 //
-// The tile shape, the staging and the distance loop are pair_tile.h's.
+// The tile shape, the staging, the distance loop, h per pair (pair_weight) and the tail's factor (deriv_tail_factor) are pair_tile.h's:
+// the last two are shared with the sample paths' gradient product (kernels_paths.hip).
 #include "pair_tile.h"
 
 #include <algorithm>
@@ -52,25 +53,7 @@ struct PgradArgs {
   KernelSpec ks;         // derived constants, see make_deriv_spec
 };
 
-// h without the factor the tail applies
-template <int KID>
-__device__ __forceinline__ double pair_weight(double s, const KernelSpec& ks) {
-  if constexpr (KID == GPRC_SQREXP) return exp(-s * ks.p[1]);        // p[1] = 1 / (2 l^2)
-  else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);   // s is the scaled distance
-  else if constexpr (is_matern(KID)) {                               // p[1] = 3 / l^2 or 5 / l^2; ARD: s is the scaled distance
-    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
-    if constexpr (is_matern32(KID)) return e;
-    else return fma(a, e, e);
-  } else if constexpr (KID == GPRC_GAMMAEXP) {
-    if (!(s > 0.0)) return 0.0;                                      // the limit for gamma > 1, the convention for gamma <= 1
-    const double u = exp(ks.p[3] * log(s * ks.p[2]));                // p[2] = 1 / l^2, p[3] = gamma / 2
-    return exp(-u) * u / s;
-  } else {                                                           // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
-    const double x = s * ks.p[2];
-    return exp(-ks.p[1] * log1p(x)) / (1.0 + x);
-  }
-}
-
+// (h without the factor the tail applies: pair_tile.h's pair_weight)
 template <int KID, bool WITH_VAR>
 __global__ __launch_bounds__(256) void pred_grad_kernel(PgradArgs a) {
   __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];
@@ -212,18 +195,8 @@ int launch_pred_grad_sum(hipStream_t s, const KernelSpec& ks, const double* part
                          double* out) {
   if (m <= 0) return 0;
   GPRC_TRY(check_grad_kernel("predict_grad", ks.id));
-  // the factor the tail applies (ARD: its constant times 1 / l_c per coordinate, from the spec; sqrexp_ard's 1.0 * p[c] is p[c] exactly)
-  const double il2 = 1.0 / (ks.p[0] * ks.p[0]);
-  double iso = il2;
-  switch (ks.id) {
-    case GPRC_GAMMAEXP: iso = ks.p[1]; break;
-    case GPRC_SQREXP_ARD: iso = 1.0; break;
-    case GPRC_MATERN32: iso = 3.0 * il2; break;
-    case GPRC_MATERN52: iso = 5.0 / 3.0 * il2; break;
-    case GPRC_MATERN32_ARD: iso = 3.0; break;
-    case GPRC_MATERN52_ARD: iso = 5.0 / 3.0; break;
-    default: break;
-  }
+  // the factor the tail applies (ARD: its constant times 1 / l_c per coordinate, from the spec)
+  const double iso = deriv_tail_factor(ks);
   // dk / dx* = -h (x* - x) t: the mean's gradient carries -1, the variance's -2 * -1
   hipLaunchKernelGGL(pred_grad_sum_kernel, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, s, part, pred_grad_stripes(n_pad), d, m_pad, m,
                      variance ? 2.0 : -1.0, iso, is_ard(ks.id) ? 1 : 0, make_deriv_spec(ks), out);

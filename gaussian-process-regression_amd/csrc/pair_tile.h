@@ -6,6 +6,7 @@
 // sets go through LDS PT_D = 16 coordinates at a time (As[r][i] coordinate-major for the 16-byte row reads, Bs[j][r] padded by one for
 // the column broadcasts); the squared distance of a lane's 32 pairs accumulates in s0[16] / s1[16]; a per-kernel epilogue follows.
 // What is here: the tile shape, the staging loop, the distance loop of the contraction kernels, the wave and four-wave sums, R's `^`,
+// the weight h of a pair in dk / dx* (pair_weight) with the factor it leaves to the tail (deriv_tail_factor),
 // and for the host the derived constants of the contraction kernels, the set of kernels with an exact gradient and the dispatcher
 // from a run-time kernel id to a template instantiation.
 //
@@ -14,7 +15,8 @@
 //     subtract: the two round differently, the fill is tied to the oracle at 1e-13 and the gradients to their own references, and
 //     both stay as they are.
 //   * the kernel value and its intermediates per kernel (u, log for gammaexp; x, q, log1p for ratquad).  kernels_grad.hip forms
-//     (m * exp(-u)) * u and m * exp(-alpha log1p x), kernels_pgrad.hip exp(-u) * u / s and exp(-alpha log1p x) / (1 + x), the fill
+//     (m * exp(-u)) * u and m * exp(-alpha log1p x), pair_weight below (the gradients with respect to a point: kernels_pgrad.hip and
+//     the sample paths' gradient product of kernels_paths.hip) exp(-u) * u / s and exp(-alpha log1p x) / (1 + x), the fill
 //     its measured fast paths (finish<KID>): a shared function would fix one order of multiplications for all three.
 #pragma once
 #include <string>
@@ -73,6 +75,21 @@ inline KernelSpec make_deriv_spec(const KernelSpec& ks) {
   return g;
 }
 
+// the factor of dk / dx*_c that pair_weight leaves out, without its sign and, for ARD, without the second 1 / l_c (the tail kernels
+// multiply by the deriv spec's p[c]; sqrexp_ard's 1.0 * p[c] is p[c] exactly): ks is the caller's spec, not the derived one
+inline double deriv_tail_factor(const KernelSpec& ks) {
+  const double il2 = 1.0 / (ks.p[0] * ks.p[0]);
+  switch (ks.id) {
+    case GPRC_GAMMAEXP: return ks.p[1];
+    case GPRC_SQREXP_ARD: return 1.0;
+    case GPRC_MATERN32: return 3.0 * il2;
+    case GPRC_MATERN52: return 5.0 / 3.0 * il2;
+    case GPRC_MATERN32_ARD: return 3.0;
+    case GPRC_MATERN52_ARD: return 5.0 / 3.0;
+    default: return il2;
+  }
+}
+
 // ---- device --------------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -127,6 +144,26 @@ __device__ __forceinline__ double weighted_sqdiff(const double (&As)[PT_D][PT_R]
     acc = fma(w1[c], t1 * t1, acc);
   }
   return acc;
+}
+
+// h of dk(x*, x_j) / dx*_c = -h (x*_c - x_jc) t_c from the squared distance s, WITHOUT the factor that does not depend on the pair
+// (deriv_tail_factor): the weight of kernels_pgrad.hip's contraction and of kernels_paths.hip's gradient product
+template <int KID>
+__device__ __forceinline__ double pair_weight(double s, const KernelSpec& ks) {
+  if constexpr (KID == GPRC_SQREXP) return exp(-s * ks.p[1]);        // p[1] = 1 / (2 l^2)
+  else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);   // s is the scaled distance
+  else if constexpr (is_matern(KID)) {                               // p[1] = 3 / l^2 or 5 / l^2; ARD: s is the scaled distance
+    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
+    if constexpr (is_matern32(KID)) return e;
+    else return fma(a, e, e);
+  } else if constexpr (KID == GPRC_GAMMAEXP) {
+    if (!(s > 0.0)) return 0.0;                                      // the limit for gamma > 1, the convention for gamma <= 1
+    const double u = exp(ks.p[3] * log(s * ks.p[2]));                // p[2] = 1 / l^2, p[3] = gamma / 2
+    return exp(-u) * u / s;
+  } else {                                                           // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
+    const double x = s * ks.p[2];
+    return exp(-ks.p[1] * log1p(x)) / (1.0 + x);
+  }
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

@@ -229,6 +229,15 @@ class GPR:
         e = np.asfortranarray(np.asarray(e, dtype=np.float64).reshape(n, S))
         return SamplePaths(self._model, d, nu, phase, w, e)
 
+    def thompson_batch(self, q, lower, upper, n_features=1024, n_starts=16, rng=None, **kw):
+        """One Thompson-sampling batch: q posterior sample paths are drawn (sample_paths), each is maximised over the box [lower, upper]
+        (SamplePaths.maximize: a multi-start ascent on the device with the paths' exact gradients; **kw goes to it), the paths are
+        released.  Returns the d x q arg-maxima, one per column, ready for add_data.  `rng` draws the paths first, then the starts.
+        Refuses what sample_paths refuses, with its texts."""
+        rng = rng if rng is not None else np.random.default_rng()
+        with self.sample_paths(q, n_features, rng=rng) as sp:
+            return sp.maximize(lower, upper, n_starts=n_starts, rng=rng, **kw).x_best
+
     def posterior_draws(self, n=5, limits=None, length_out=200, *, z=None, rng=None):
         """The data behind GPR$plot_posterior_draws(n = 5, limits = expand_range(X), length.out = 200)  --
         R/GPRclass.R:190-199 (one-dimensional inputs only, :192-195): test points, cbind(mean, diag(cov)) and n draws

@@ -10,12 +10,13 @@ defined); what is pinned is L %*% t(L) = covariance (projected on the PSD cone) 
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _native as nat
 
-__all__ = ["multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "spectral_frequencies", "SamplePaths"]
+__all__ = ["multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "spectral_frequencies", "SamplePaths", "PathMaxima", "maximize_paths"]
 
 
 def _sq(cov, what="covariance"):
@@ -124,11 +125,123 @@ def spectral_frequencies(k, d, D, rng):
     return np.asfortranarray(omega.T / (2.0 * np.pi))
 
 
+class PathMaxima(NamedTuple):
+    """what maximize_paths returns"""
+    x_best: np.ndarray    # d x n_paths: the best point of every path
+    f_best: np.ndarray    # n_paths: its value, as the evaluator returned it at exactly that point
+    x: np.ndarray         # d x (n_paths n_starts): all candidates; candidate q belongs to path q mod n_paths
+    f: np.ndarray         # their values under their own path
+    pg: np.ndarray        # their projected-gradient norms  max_c |clip(x + g)_c - x_c|
+    n_evals: int          # calls of the evaluator
+
+
+def maximize_paths(eval_grad, lower, upper, n_paths, *, n_starts=16, max_iter=200, gtol=1e-8, x0=None, rng=None):
+    """Maximise n_paths functions over the box [lower, upper] (each of length d) by a batched multi-start projected gradient ascent.
+
+    `eval_grad(X)` takes d x m points (Fortran order) and returns (F m x n_paths, dF m x n_paths x d): SamplePaths.paths_grad, or any
+    function of that shape (the tests run it on the numpy reference).  There are n_paths * n_starts candidates, candidate q belongs to
+    path q mod n_paths, and every iteration is ONE eval_grad call on all candidates, of which each candidate uses its own column.
+
+    Starts: x0 (d x n_paths n_starts) when given; else uniform in the box from `rng`, candidate by candidate.  The first call has then
+    evaluated every draw under every path, so a path keeps the better half of its own draws and takes the best other draws under it for
+    the rest: no further evaluation, and a path's starts no longer depend on its own luck alone.
+    Step: x+ = clip(x + a g) with a Barzilai-Borwein step a = -s.s / s.y where the curvature along the last step is negative (else four
+    times the last step), safeguarded by Armijo's condition f+ >= f_ref + 1e-4 g.(x+ - x) up to the rounding of f, with f_ref the
+    smallest of the candidate's last five accepted values (Barzilai-Borwein steps are not monotone; against f itself the d = 2 problem
+    of the tests left 100 of 256 candidates unconverged after 200 iterations, this way all converge within 90): a rejected candidate
+    keeps its point and quarters its step.  A candidate stops when its projected-gradient norm max_c |clip(x + g)_c - x_c| <= gtol;
+    one that has not converged at max_iter returns the best point it visited.
+    Deterministic for a given rng (or x0).  Returns a PathMaxima."""
+    lower = np.atleast_1d(np.asarray(lower, dtype=np.float64)).ravel()
+    upper = np.atleast_1d(np.asarray(upper, dtype=np.float64)).ravel()
+    d, S, T = lower.size, int(n_paths), int(n_starts)
+    if upper.size != d or not (np.isfinite(lower).all() and np.isfinite(upper).all() and (lower < upper).all()):
+        raise ValueError("lower and upper must be finite, of one length, lower < upper")
+    if S < 1 or T < 1 or int(max_iter) < 0:
+        raise ValueError("n_paths >= 1, n_starts >= 1, max_iter >= 0 are not all TRUE")
+    Q = S * T
+    lo, hi = lower[:, None], upper[:, None]
+    qi = np.arange(Q)
+    path = qi % S
+
+    def clip(x):
+        return np.minimum(np.maximum(x, lo), hi)
+
+    def own(x):
+        F, dF = eval_grad(np.asfortranarray(x))
+        F, dF = np.asarray(F), np.asarray(dF)
+        if F.shape != (Q, S) or dF.shape != (Q, S, d):
+            raise ValueError("eval_grad must return (m x n_paths, m x n_paths x d)")
+        return F, dF
+
+    if x0 is not None:
+        x = clip(np.array(x0, dtype=np.float64).reshape(d, Q))
+        F, dF = own(x)
+        f, g = F[qi, path].copy(), dF[qi, path, :].T.copy()
+    else:
+        rng = rng if rng is not None else np.random.default_rng()
+        draws = clip(lo + (hi - lo) * rng.random((Q, d)).T)
+        F, dF = own(draws)
+        pick = qi.copy()                                             # the draw candidate q starts from
+        keep = T - T // 2
+        for s in range(S):
+            mine = qi[path == s]
+            mine = mine[np.argsort(-F[mine, s], kind="stable")]      # this path's own draws, best first
+            rest = np.argsort(-F[:, s], kind="stable")
+            rest = rest[path[rest] != s][:T - keep]                  # the best draws of the other paths under this one
+            pick[qi[path == s]] = np.concatenate([mine[:keep], rest, mine[keep:]])[:T]   # (one path: there are no other draws)
+        x = draws[:, pick]
+        f, g = F[pick, path].copy(), dF[pick, path, :].T.copy()
+    n_evals = 1
+
+    def pgnorm(x, g):
+        return np.abs(clip(x + g) - x).max(axis=0)
+
+    width = float((upper - lower).min())
+    pg = pgnorm(x, g)
+    step = 0.05 * width / np.maximum(np.abs(g).max(axis=0), 1e-300)  # the first move is a twentieth of the box
+    active = pg > gtol
+    eps = 4.0 * np.finfo(np.float64).eps
+    hist = np.repeat(f[None, :], 5, axis=0)                          # the last five accepted values: Armijo against their minimum
+    xb, fb, gb = x.copy(), f.copy(), g.copy()                        # the best point a candidate has visited
+    for _ in range(int(max_iter)):
+        if not active.any():
+            break
+        xt = np.where(active[None, :], clip(x + step[None, :] * g), x)
+        F, dF = own(xt)
+        n_evals += 1
+        ft, gt = F[qi, path], dF[qi, path, :].T
+        sv = xt - x
+        gain = (g * sv).sum(axis=0)
+        fref = hist.min(axis=0)
+        ok = active & (ft >= fref + 1e-4 * gain - eps * np.maximum(1.0, np.abs(fref)))
+        hist[:, ok] = np.vstack([hist[1:, ok], ft[None, ok]])
+        yv = gt - g
+        ss, sy = (sv * sv).sum(axis=0), (sv * yv).sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            bb = np.where(sy < 0.0, -ss / sy, 4.0 * step)
+        step = np.where(ok, bb, np.where(active, 0.25 * step, step))
+        x = np.where(ok[None, :], xt, x)
+        g = np.where(ok[None, :], gt, g)
+        f = np.where(ok, ft, f)
+        up = f > fb
+        xb, gb, fb = np.where(up[None, :], x, xb), np.where(up[None, :], g, gb), np.where(up, f, fb)
+        pg = pgnorm(x, g)
+        moved = step * np.abs(g).max(axis=0) > 1e-17 * width        # a step below the spacing of the coordinates cannot move the point
+        active = active & (pg > gtol) & moved
+    back = (pg > gtol) & (fb > f)                                    # not converged and below an earlier point: that point is returned
+    x, g, f = np.where(back[None, :], xb, x), np.where(back[None, :], gb, g), np.where(back, fb, f)
+    pg = pgnorm(x, g)
+    best = np.array([qi[path == s][np.argmax(f[path == s])] for s in range(S)])
+    return PathMaxima(np.asfortranarray(x[:, best]), f[best].copy(), np.asfortranarray(x), f, pg, n_evals)
+
+
 class SamplePaths:
     """Posterior sample paths of a fitted GPR (GPR.sample_paths; gprc_gpr_paths_*): n_paths functions that can be evaluated at any points,
     again and again.  They describe the posterior at creation and stay valid after GPR.add_data or GPR.close.  `paths(X_star)` returns
-    the n* x n_paths array of their values; `.weights` the n x n_paths matrix U of the update term; `.close()` releases the device memory
-    (also a context manager)."""
+    the n* x n_paths array of their values; `paths_grad(X_star)` the values and their gradients with respect to the points;
+    `maximize(lower, upper)` every path's maximiser over a box (maximize_paths); `.weights` the n x n_paths matrix U of the update term;
+    `.close()` releases the device memory (also a context manager)."""
 
     def __init__(self, model_handle, d, nu, phase, w, e):
         self._h = C.c_void_p()
@@ -145,6 +258,13 @@ class SamplePaths:
 
     def paths(self, X_star):
         """f_s(X_star[, i]) as an n* x n_paths array; X_star as GPR.predict takes it"""
+        Xs = self._points(X_star)
+        ns = Xs.shape[1]
+        out = np.empty((ns, self.n_paths), order="F")
+        nat.check(nat.lib().gprc_gpr_paths_eval(self._handle(), Xs.ctypes.data, ns, out.ctypes.data, ns))
+        return out
+
+    def _points(self, X_star):
         from .covfunc import as_points
         d = self._d
         Xs = np.asarray(X_star)
@@ -153,10 +273,21 @@ class SamplePaths:
         Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
         if Xs.shape[0] != d:
             raise ValueError("X_star must have nrow(X) rows")
+        return Xs
+
+    def paths_grad(self, X_star):
+        """(F, dF): the values f_s(X_star[, i]) as `paths` returns them (the same bits), n* x n_paths, and their gradients with respect
+        to the point, dF[i, s, c] = d f_s / d x_c, n* x n_paths x d; both in Fortran order (gprc_gpr_paths_eval_grad)"""
+        Xs = self._points(X_star)
         ns = Xs.shape[1]
-        out = np.empty((ns, self.n_paths), order="F")
-        nat.check(nat.lib().gprc_gpr_paths_eval(self._handle(), Xs.ctypes.data, ns, out.ctypes.data, ns))
-        return out
+        F = np.empty((ns, self.n_paths), order="F")
+        dF = np.empty((ns, self.n_paths, self._d), order="F")
+        nat.check(nat.lib().gprc_gpr_paths_eval_grad(self._handle(), Xs.ctypes.data, ns, F.ctypes.data, ns, dF.ctypes.data, ns))
+        return F, dF
+
+    def maximize(self, lower, upper, **kw):
+        """maximize_paths over these paths on the device: every iteration is one paths_grad call on all candidates"""
+        return maximize_paths(self.paths_grad, lower, upper, self.n_paths, **kw)
 
     @property
     def weights(self):

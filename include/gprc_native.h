@@ -233,6 +233,18 @@ typedef struct gprc_paths gprc_paths;
 GPRC_API int gprc_gpr_paths_create(gprc_model* model, const double* Nu, const double* phase, int64_t D, const double* W, const double* E,
                                    int64_t S, gprc_paths** paths_out);
 GPRC_API int gprc_gpr_paths_eval(gprc_paths* paths, const double* X_star, int64_t n_star, double* out, int64_t ld_out);
+/* The gradient of every path with respect to the test point, and optionally the values with it:
+ *   dout[i + ld_dout (s + S c)] = d f_s / d x_c at X_star[, i]
+ *     = -2 pi sqrt(2 / D) sum_k Nu[c, k] sin 2 pi(nu_k . x + u_k) W[k, s]  -  t_c sum_j h(x, x_j) (x_c - x_jc) U[j, s]
+ * n_star x S x d, the coordinate slowest; h and t_c as for gprc_gpr_predict_grad (gammaexp: h = 0 at a training point; Matern: finite
+ * there).  out: NULL, or n_star x S with the bits of gprc_gpr_paths_eval (its launches with its arguments).  Host or device pointers.
+ * Both terms are generated-operand products as in eval, one operand per coordinate: the weight of a pair is formed once, the direct
+ * difference x_c - x_jc is taken per coordinate.  Chunked over the test points: rows x S x d x stripes doubles of workspace per chunk
+ * (at most 1 GiB or the context's chunk budget, never below 128 rows); the same bits under every chunking and for a point alone.
+ * GPRC_ERR_ARG, each with text: a null paths object, X_star or dout; n_star < 1; ld_dout < n_star; out given and ld_out < n_star;
+ * a paths object whose context has been destroyed. */
+GPRC_API int gprc_gpr_paths_eval_grad(gprc_paths* paths, const double* X_star, int64_t n_star, double* out, int64_t ld_out, double* dout,
+                                      int64_t ld_dout);
 GPRC_API int gprc_gpr_paths_get_weights(gprc_paths* paths, double* U_out);
 GPRC_API int gprc_gpr_paths_dims(const gprc_paths* paths, int64_t* n_out, int64_t* d_out, int64_t* D_out, int64_t* S_out);
 GPRC_API int gprc_gpr_paths_free(gprc_paths* paths);
@@ -480,6 +492,14 @@ GPRC_API int gprc_dev_feature_gemm(gprc_ctx* ctx, const double* Nu, const double
                                    const double* W, int64_t ldw, int64_t S, double scale, double* out, int64_t ld);
 GPRC_API int gprc_dev_kernel_gemm(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* A, int64_t rows,
                                   const double* Bpts, int64_t cols, int64_t d, const double* U, int64_t ldu, int64_t S, double* out, int64_t ld);
+/* Their gradients with respect to the row points (DEVICE pointers, synchronous), arguments as above and the d-fold output:
+ *   dout[i + ld (s + S c)] = d out[i + s ld] / d a_i[c],   c < d:   rows x S x d, pitch ld >= rows
+ * feature_gemm_grad: -2 pi scale sum_j Nu[c, j] sin 2 pi(t_ij) B[j + s ldw];  kernel_gemm_grad: -t_c sum_j h(a_i, b_j) (a_ic - b_jc) B[j + s ldu].
+ * The same stripes and order of summation per (c, s, i) as the value products. */
+GPRC_API int gprc_dev_feature_gemm_grad(gprc_ctx* ctx, const double* Nu, const double* phase, int64_t D, const double* A, int64_t rows, int64_t d,
+                                        const double* W, int64_t ldw, int64_t S, double scale, double* dout, int64_t ld);
+GPRC_API int gprc_dev_kernel_gemm_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* A, int64_t rows,
+                                       const double* Bpts, int64_t cols, int64_t d, const double* U, int64_t ldu, int64_t S, double* dout, int64_t ld);
 
 /* ---- multi-GPU from ONE process (SURVEY 8b "Threading", 8e): the form the R `.Call` boundary can use ------------ *
  * The reference's host is a single R process; it cannot be forked per GPU.  A gprc_mgpu drives G ranks -- one per
@@ -568,7 +588,7 @@ GPRC_API int gprc_combine_all(gprc_ctx* ctx, const double* axis_values, const in
  * left-looking update, 12 trailing left-looking update, 13 fused panel factorisation, 14 fused in-panel solve of the predict, 15 inverse GEMM
  * (-L^-T L^-1, lower), 16 gradient contraction (gprc_gpr_logp_grad), 17 Laplace gradient contraction (gprc_gpc_logq_grad),
  * 18 factor reversal, 19 prediction-gradient contraction (gprc_gpr_predict_grad; the sample paths'
- * generated-operand products are counted here too).  gprc_gpr_loo_grad adds no kind: its n^3 product is
+ * generated-operand products and their gradient products are counted here too).  gprc_gpr_loo_grad adds no kind: its n^3 product is
  * counted under 8, its contraction under 17 and the builder of its scaled full inverse under 18.  flops/bytes are the ALGORITHMIC
  * figures of DESIGN.md for the launches seen, not counter readings. */
 GPRC_API int gprc_prof_enable(int on);
