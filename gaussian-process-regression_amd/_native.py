@@ -157,6 +157,12 @@ PROTOTYPES = {
     "gprc_dev_kernel_gemm": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64]),
     "gprc_dev_feature_gemm_grad": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_double, _vp, _i64]),
     "gprc_dev_kernel_gemm_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64]),
+    "gprc_igpr_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_int, _i64, C.POINTER(_vp)]),
+    "gprc_igpr_solve": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.POINTER(C.c_int), _dp]),
+    "gprc_igpr_predict": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gprc_igpr_get_alpha": (C.c_int, [_vp, _vp]),
+    "gprc_igpr_stats": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "gprc_dev_pivoted_cholesky": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.POINTER(_i64)]),
 }
 
 _lib = None

@@ -39,7 +39,7 @@ struct gprc_ctx {
   size_t pool_cap = (size_t)16 << 30;     // GPRC_POOL_BYTES; blocks larger than the cap are never kept
 };
 
-enum ModelType { MODEL_GPR = 1, MODEL_GPC = 2, MODEL_SGPR = 3 };
+enum ModelType { MODEL_GPR = 1, MODEL_GPC = 2, MODEL_SGPR = 3, MODEL_IGPR = 4 };
 
 struct gprc_model {
   gprc_ctx* ctx = nullptr;
@@ -65,6 +65,13 @@ struct gprc_model {
   double* winv_b = nullptr;
   double elbo = 0.0, trace = 0.0, jitter = 0.0;
   int64_t n_train = 0;
+  // MODEL_IGPR (gprc_iter.hip): X, y, alpha = K_y^-1 y by conjugate gradients and noise as a GPR model's; no factor (packed, winv and work
+  // stay null).  pq = Q (n x rank, pitch n) of the preconditioner (I - Q Q^T) / noise, null at rank 0; the solver's settings and what the
+  // fit's own solve reported:
+  double* pq = nullptr;
+  int64_t rank = 0;
+  double cg_tol = 0.0, cg_relres = 0.0, cg_relres_true = 0.0;
+  int cg_max_iter = 0, cg_iters = 0;
 };
 
 namespace gprc {
@@ -181,5 +188,16 @@ void free_model(gprc_model* m);
 struct ModelFree { void operator()(gprc_model* m) const { free_model(m); } };
 using ModelPtr = std::unique_ptr<gprc_model, ModelFree>;   // owns a model: every return frees it unless release() has handed it on
 int ensure_reversed_factor(gprc_model* m);   // packed_rev / winv_rev of a model that owns its buffers, built once and kept
+
+// ---- gprc_paths.hip ----------------------------------------------------------------------------------
+// out (rows x S, pitch ld) = [out +] scale * G(A, Bp) B, the generated-operand product over all rows in chunks (launch_gen_gemm's arguments)
+int gen_gemm(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows, int64_t d,
+             const double* B, int64_t ldb, int64_t S, double scale, bool accumulate, double* out, int64_t ld);
+
+// ---- gprc_iter.hip -----------------------------------------------------------------------------------
+// X (n x S, pitch ldx) = K_y^-1 B (pitch ldb) of a MODEL_IGPR by preconditioned conjugate gradients, DEVICE pointers, asynchronous past
+// the last block's statistics.  iters, relres, relres_true: S host entries each or null.  Returns 0, GPRC_ERR_MAXITER (every output
+// written from the last iterate) or GPRC_ERR_NOT_PD.
+int igpr_solve_dev(gprc_model* m, const double* B, int64_t ldb, int64_t S, double* X, int64_t ldx, int* iters, double* relres, double* relres_true);
 
 }  // namespace gprc

@@ -7,6 +7,7 @@
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
 //   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound and its gradient, predict) and its entry points
 //   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create, eval and eval_grad) and their entry points
+//   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict)
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
@@ -178,6 +179,31 @@ int launch_paths_residual(hipStream_t s, const double* y, const double* F, int64
                           int64_t scur, int64_t n, int64_t m_pad, int64_t n_pad, double* vt, int64_t ldv);
 // U[j + (s0 + s) ldu] = vt[s + (n_pad - 1 - j) ldv], s < scur, j < n: out of the column-reversed solved chunk
 int launch_paths_weights(hipStream_t s, const double* vt, int64_t ldv, int64_t n_pad, int64_t s0, int64_t scur, int64_t n, double* U, int64_t ldu);
+
+// ---- launchers (kernels_cg.hip: the iterative exact GPR) ------------------------------------------
+// A block of right-hand sides of the conjugate-gradient loop is at most CG_SB columns (the product's sample block); its scalars live in
+// `sc`, CG_ROWS rows of CG_SB doubles: |b|^2, the stop threshold tol^2 |b|^2, r^T z, |r|^2 (what the host reads; -1: p^T A p was not
+// finite or not positive) and 1 / 0 for running / frozen.  Buffers are n x S with pitch n.  Order of summation: kernels_cg.hip.
+constexpr int CG_SB = 64;
+enum CgRow { CG_BB = 0, CG_THR2 = 1, CG_RZ = 2, CG_RR = 3, CG_ACT = 4, CG_ROWS = 5 };
+// The partial pivoted Cholesky of K(X, X) (k(x, x) = 1: the kernels of with_gradient_kernel), matrix-free, r <= n steps: L (n x r, pitch
+// ldl; the columns from the rank on are zero), piv (r), and state[0] = -1 after a full sweep, else the rank at which the largest
+// remaining diagonal was <= n 2^-52.  pval (r), dg (n): work.  2 r launches, no host synchronisation.
+int launch_pivoted_cholesky(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, int64_t r, double* L, int64_t ldl, int64_t* piv,
+                            double* pval, double* dg, int* state);
+int launch_copy_scaled(hipStream_t s, const double* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int64_t cols, double div);   // dst = src / div
+// Z = (V - Q (Q^T V)) / noise: Q n x r, V and Z n x S, T r x S work, all with pitch = rows.  Profiled as PK_ROWREDUCE.
+int launch_apply_precond(hipStream_t s, const double* Q, int64_t r, const double* V, int64_t n, int64_t S, double noise, double* T, double* Z);
+int launch_cg_init(hipStream_t s, const double* B, int64_t ldb, int64_t n, int64_t S, double tol, double* R, double* X, double* sc);   // r = b, x = 0
+// AP = K P on entry: AP += noise P, alpha, x += alpha p, r -= alpha Ap, |r|^2, freeze
+int launch_cg_step(hipStream_t s, const double* P, double* AP, double* X, double* R, int64_t n, int64_t S, double noise, double* sc);
+int launch_cg_direction(hipStream_t s, const double* R, const double* Z, double* P, int64_t n, int64_t S, bool first, double* sc);   // beta, p = z + beta p
+// AX = K X on entry: out[s] = |b_s - (K + noise I) x_s| / |b_s|
+int launch_cg_residual(hipStream_t s, const double* B, int64_t ldb, const double* AX, const double* X, int64_t n, int64_t S, double noise, const double* sc,
+                       double* out);
+int launch_cg_var(hipStream_t s, const double* A, const double* W, int64_t n, int64_t S, double* out);   // out[s] = 1 - a_s . w_s
+// F = (y 1^T - F) - sqn E in place: the right-hand sides of the sample paths from the prior term
+int launch_paths_rhs(hipStream_t s, const double* y, double* F, int64_t ldf, const double* E, int64_t lde, double sqn, int64_t n, int64_t S);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

@@ -59,6 +59,7 @@ void free_model(gprc_model* m) {
   if (m->winv_rev) pool_release(m->ctx, m->winv_rev, sizeof(double) * (size_t)gprc_winv_size(m->n_pad));
   if (m->packed_b) pool_release(m->ctx, m->packed_b, sizeof(double) * (size_t)gprc_packed_size(m->n_pad));         // a sparse model's factor of B
   if (m->winv_b) pool_release(m->ctx, m->winv_b, sizeof(double) * (size_t)gprc_winv_size(m->n_pad));
+  if (m->pq) pool_release(m->ctx, m->pq, sizeof(double) * (size_t)(m->n * m->rank));                                  // an iterative model's Q
   delete m;
 }
 
@@ -834,6 +835,7 @@ int gprc_model_dims(const gprc_model* m, int64_t* n_out, int64_t* d_out) {
 int gprc_model_get_L(gprc_model* m, double* L_out, int64_t ld_out) {
   if (!m || !L_out || ld_out < m->n) { set_error("get_L: bad arguments"); return GPRC_ERR_ARG; }
   if (m->type == MODEL_SGPR) { set_error("get_L: a sparse model holds two factors of inducing-point size, not the factor of K + noise I"); return GPRC_ERR_ARG; }
+  if (m->type == MODEL_IGPR) { set_error("get_L: an iterative model holds no factor"); return GPRC_ERR_ARG; }
   GPRC_TRY(use_device(m->ctx));
   hipStream_t s = m->ctx->stream;
   const int64_t n = m->n;

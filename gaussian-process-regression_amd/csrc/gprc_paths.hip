@@ -7,7 +7,8 @@
 //
 // create: the prior term at the training points goes into U's own buffer (n x S); S rows at a time (the chunk workspace's rows, S padded to
 // 128) the residual is laid out as the rows of a solve chunk, R L^-T by solve_rows, then columns reversed and solve_rows with the reversed
-// factor as predict_chunk's variance gradient does: (R L^-T L^-1) J, which paths_weights_kernel reads back into U.
+// factor as predict_chunk's variance gradient does: (R L^-T L^-1) J, which paths_weights_kernel reads back into U.  An iterative model
+// (MODEL_IGPR, gprc_iter.hip) has no factor: the residual stays n x S and U is its conjugate-gradient solve.
 // eval: two products into the caller's array, the prior term first, the update added to it; rows in chunks sized by the context's
 // chunk budget.  Memory: rows x S x (1 + stripes) doubles per chunk; no n* x n and no n* x n* buffer.
 // eval_grad: the same two products differentiated with respect to the test point (gen_gemm_grad; the values, when asked for, by eval's
@@ -53,6 +54,8 @@ void free_paths(gprc_paths* p) {
 }
 struct PathsFree { void operator()(gprc_paths* p) const { free_paths(p); } };
 
+}  // namespace
+
 // One generated-operand product over all rows, in chunks: a chunk's partials are rows x S x stripes doubles, sized by the context's chunk
 // budget (at most 1 GiB).  Results do not depend on the chunking, bit for bit (kernels_paths.hip).
 int gen_gemm(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const double* phase, int64_t cols, const double* A, int64_t rows, int64_t d,
@@ -69,6 +72,8 @@ int gen_gemm(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const double
   }
   return 0;
 }
+
+namespace {
 
 // Its gradient with respect to the rows' points: dout is rows x (S d), pitch ld.  A chunk's partials are rows x S x d x stripes doubles
 // inside the same budget, a chunk is never below one row tile, and the bits do not depend on the chunking either.
@@ -102,7 +107,11 @@ extern "C" {
 
 int gprc_gpr_paths_create(gprc_model* m, const double* Nu, const double* phase, int64_t D, const double* W, const double* E, int64_t S,
                           gprc_paths** paths_out) {
-  if (!m || m->type != MODEL_GPR) { set_error("paths_create: not a GPR model (paths of a GPC or a sparse model are not defined here)"); return GPRC_ERR_ARG; }
+  if (!m || (m->type != MODEL_GPR && m->type != MODEL_IGPR)) {
+    set_error("paths_create: not a GPR model (paths of a GPC or a sparse model are not defined here)");
+    return GPRC_ERR_ARG;
+  }
+  const bool iterative = m->type == MODEL_IGPR;   // U by conjugate gradients: no factor, no reversed factor
   if (m->borrowed) {
     set_error("paths_create: the model borrows its buffers (gprc_gpr_model_from_device / gprc_mgpu_model_rank) and cannot own a reversed factor");
     return GPRC_ERR_ARG;
@@ -131,9 +140,19 @@ int gprc_gpr_paths_create(gprc_model* m, const double* Nu, const double* phase, 
   GPRC_HIP(hipMemcpyAsync(p->Nu, nu.dev, sizeof(double) * d * D, hipMemcpyDeviceToDevice, s));
   GPRC_HIP(hipMemcpyAsync(p->phase, ph.dev, sizeof(double) * D, hipMemcpyDeviceToDevice, s));
   GPRC_HIP(hipMemcpyAsync(p->W, w.dev, sizeof(double) * D * S, hipMemcpyDeviceToDevice, s));
-  GPRC_TRY(ensure_reversed_factor(m));
+  if (!iterative) GPRC_TRY(ensure_reversed_factor(m));
   // the prior term at the training points, sqrt(2 / D) Phi(X) W, into U's buffer
   GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu, p->phase, D, p->X, n, d, p->W, D, S, std::sqrt(2.0 / (double)D), false, p->U, n));
+  if (iterative) {   // U = K_y^-1 (y - prior - sqrt(noise) E) in blocks of right-hand sides (gprc_iter.hip)
+    DevMem rhs;
+    GPRC_TRY(rhs.alloc(n * S));
+    GPRC_HIP(hipMemcpyAsync(rhs.p, p->U, sizeof(double) * n * S, hipMemcpyDeviceToDevice, s));
+    GPRC_TRY(launch_paths_rhs(s, m->y, rhs.p, n, e.dev, n, std::sqrt(m->noise), n, S));
+    GPRC_TRY(igpr_solve_dev(m, rhs.p, n, S, p->U, n, nullptr, nullptr, nullptr));
+    GPRC_HIP(hipStreamSynchronize(s));
+    *paths_out = p.release();
+    return 0;
+  }
   int64_t rows = 0;
   double *vt = nullptr, *part = nullptr, *unused = nullptr;
   GPRC_TRY(chunk_workspace(ctx, n_pad, S, false, &rows, &vt, &part, &unused));

@@ -60,23 +60,6 @@ struct GenArgs {
   KernelSpec ks;         // derived constants, see make_deriv_spec (kernel generators only)
 };
 
-// k from the squared distance s (ARD: the scaled one)
-template <int KID>
-__device__ __forceinline__ double kernel_value(double s, const KernelSpec& ks) {
-  if constexpr (KID == GPRC_SQREXP) return exp(-s * ks.p[1]);        // p[1] = 1 / (2 l^2)
-  else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);
-  else if constexpr (is_matern(KID)) {                               // p[1] = 3 / l^2 or 5 / l^2
-    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
-    if constexpr (is_matern32(KID)) return fma(a, e, e);
-    else return fma(a * a, 1.0 / 3.0, 1.0 + a) * e;
-  } else if constexpr (KID == GPRC_GAMMAEXP) {
-    if (!(s > 0.0)) return 1.0;
-    return exp(-exp(ks.p[3] * log(s * ks.p[2])));                    // p[2] = 1 / l^2, p[3] = gamma / 2
-  } else {                                                           // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
-    return exp(-ks.p[1] * log1p(s * ks.p[2]));
-  }
-}
-
 template <int GEN>
 __global__ __launch_bounds__(256) void gen_gemm_kernel(GenArgs a) {
   __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];

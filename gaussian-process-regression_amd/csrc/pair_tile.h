@@ -17,7 +17,9 @@
 //   * the kernel value and its intermediates per kernel (u, log for gammaexp; x, q, log1p for ratquad).  kernels_grad.hip forms
 //     (m * exp(-u)) * u and m * exp(-alpha log1p x), pair_weight below (the gradients with respect to a point: kernels_pgrad.hip and
 //     the sample paths' gradient product of kernels_paths.hip) exp(-u) * u / s and exp(-alpha log1p x) / (1 + x), the fill
-//     its measured fast paths (finish<KID>): a shared function would fix one order of multiplications for all three.
+//     its measured fast paths (finish<KID>): a shared function would fix one order of multiplications for all three.  kernel_value
+//     below is a fourth form and belongs to the generated-operand products (kernels_paths.hip) and the pivoted Cholesky that
+//     preconditions them (kernels_cg.hip): those two must see the same matrix, nobody else uses it.
 #pragma once
 #include <string>
 #include <type_traits>
@@ -163,6 +165,24 @@ __device__ __forceinline__ double pair_weight(double s, const KernelSpec& ks) {
   } else {                                                           // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
     const double x = s * ks.p[2];
     return exp(-ks.p[1] * log1p(x)) / (1.0 + x);
+  }
+}
+
+// k from the squared distance s (ARD: the scaled one), constants from make_deriv_spec: the value of the generated-operand products
+// (kernels_paths.hip) and of the pivoted Cholesky's columns (kernels_cg.hip); not the fill's finish<KID>, see the head of this file
+template <int KID>
+__device__ __forceinline__ double kernel_value(double s, const KernelSpec& ks) {
+  if constexpr (KID == GPRC_SQREXP) return exp(-s * ks.p[1]);        // p[1] = 1 / (2 l^2)
+  else if constexpr (KID == GPRC_SQREXP_ARD) return exp(-0.5 * s);
+  else if constexpr (is_matern(KID)) {                               // p[1] = 3 / l^2 or 5 / l^2
+    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
+    if constexpr (is_matern32(KID)) return fma(a, e, e);
+    else return fma(a * a, 1.0 / 3.0, 1.0 + a) * e;
+  } else if constexpr (KID == GPRC_GAMMAEXP) {
+    if (!(s > 0.0)) return 1.0;
+    return exp(-exp(ks.p[3] * log(s * ks.p[2])));                    // p[2] = 1 / l^2, p[3] = gamma / 2
+  } else {                                                           // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
+    return exp(-ks.p[1] * log1p(s * ks.p[2]));
   }
 }
 

@@ -318,6 +318,38 @@ GPRC_API int gprc_sgpr_get_elbo(gprc_model* model, double* elbo_out, double* tra
 /* c = L_B^-1 V^T y / sigma^2 (m doubles, host or device): the vector the predictive mean is a product with */
 GPRC_API int gprc_sgpr_get_c(gprc_model* model, double* c_out);
 
+/* ---- L2: iterative exact GPR (preconditioned conjugate gradients, matrix-free; no reference counterpart) ---------- *
+ * The exact model without its n x n factor: every solve with K_y = K(X, X) + noise I is a conjugate-gradient loop on the generated-
+ * operand product of gprc_dev_kernel_gemm, which stores no kernel value ("Iterative GPR").  Kernels: those of
+ * gprc_gpr_paths_create (stationary, k(x, x) = 1); any other id: GPRC_ERR_ARG.  noise = sigma^2, finite and > 0; tol > 0.
+ * MEMORY: 5 n x 64 doubles for a block of right-hand sides, the product's partials (at most 1 GiB), n x rank for the preconditioner,
+ * and X, y, alpha.  FLOP per iteration: one n x n generated product (n^2 (3 d + 40) + 2 n^2 S) and 4 n rank S for the preconditioner.
+ * Preconditioner: precond_rank steps of the pivoted Cholesky of K (gprc_dev_pivoted_cholesky) give L (n x rank); P = L L^T + noise I is
+ * applied as P^-1 V = (V - Q (Q^T V)) / noise, Q formed once per model.  precond_rank = 0: none; clipped to n; < 0 or > 1024: GPRC_ERR_ARG.
+ * Loop: right-hand sides in blocks of 64 columns; a column stops when its recurrence residual has |r| <= tol |b| (tested as
+ * |r|^2 <= tol^2 |b|^2) and is then frozen; a zero column returns x = 0 after 0 iterations; max_iter <= 0 selects 1000.
+ * After the loop one more product gives the TRUE residual |b - K_y x| / |b| of every column: that is what is reported, the recurrence
+ * drifts from it.  A column's bits are the same alone or in any batch, on every call, and from host or device pointers.
+ * GPRC_ERR_MAXITER: a column did not meet tol within max_iter; gprc_igpr_solve and gprc_igpr_predict have then written every output
+ * from the last iterate, gprc_igpr_fit returns no model.  GPRC_ERR_NOT_PD: p^T K_y p was not finite or not positive.
+ * fit: alpha = K_y^-1 y.  The model holds X, y, alpha, Q and the statistics of that solve; it answers gprc_model_dims with (n, d), is
+ * released by gprc_model_free and is accepted by gprc_gpr_paths_create (U is then the conjugate-gradient solve of the paths' right-hand
+ * sides; no reversed factor).  Every other gprc_gpr_*, gprc_sgpr_*, gprc_gpc_* call and gprc_model_get_L return GPRC_ERR_ARG for it, as
+ * the gprc_igpr_* calls do for any other model.
+ * solve: Xout (n x S, pitch ldx >= n) = K_y^-1 B (n x S, pitch ldb >= n), host or device; iters_out, relres_true_out: S entries each in
+ * HOST memory, or NULL.
+ * predict: mean_i = sum_j k(x*_i, x_j) alpha_j through the product; var may be NULL, else var_i = 1 - k*_i^T K_y^-1 k*_i, the latent
+ * variance as gprc_gpr_predict(pointwise = 1).  THE VARIANCE COSTS A FULL CONJUGATE-GRADIENT SOLVE PER 64 TEST POINTS: it is meant for
+ * a modest n_star.  With var = NULL the mean has the same bits.
+ * stats: of the fit's solve -- iterations, recurrence and true relative residual -- and the preconditioner's rank; each may be NULL. */
+GPRC_API int gprc_igpr_fit(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                           const double* y, double noise, double tol, int max_iter, int64_t precond_rank, gprc_model** model_out);
+GPRC_API int gprc_igpr_solve(gprc_model* model, const double* B, int64_t ldb, int64_t S, double* Xout, int64_t ldx, int* iters_out,
+                             double* relres_true_out);
+GPRC_API int gprc_igpr_predict(gprc_model* model, const double* X_star, int64_t n_star, double* mean, double* var);
+GPRC_API int gprc_igpr_get_alpha(gprc_model* model, double* alpha_out);
+GPRC_API int gprc_igpr_stats(gprc_model* model, int* iterations_out, double* relres_recurrence_out, double* relres_true_out, int64_t* rank_out);
+
 /* ---- L2: GPC ------------------------------------------------------------------------------ */
 /* GPC$initialize (R/GPCclass.R:66-107): Laplace mode by Newton/IRLS; y in {-1,+1}.
  * max_iter <= 0 selects 1000.  *iters_out = the "Convergence after %s iterations" count (:98).
@@ -500,6 +532,14 @@ GPRC_API int gprc_dev_feature_gemm_grad(gprc_ctx* ctx, const double* Nu, const d
                                         const double* W, int64_t ldw, int64_t S, double scale, double* dout, int64_t ld);
 GPRC_API int gprc_dev_kernel_gemm_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* A, int64_t rows,
                                        const double* Bpts, int64_t cols, int64_t d, const double* U, int64_t ldu, int64_t S, double* dout, int64_t ld);
+/* The partial pivoted Cholesky of K(X, X), matrix-free (kernels as gprc_igpr_fit: k(x, x) = 1): from dg = 1, for j = 0 .. r - 1: p = the
+ * lowest index among the maxima of dg over the points not yet chosen; stop when dg_p <= n 2^-52; L[p, j] = sqrt(dg_p);
+ * L[i, j] = (k(x_i, x_p) - sum_{t < j} L[i, t] L[p, t]) / L[p, j] (t ascending) for every point not yet chosen, 0 for the earlier pivots;
+ * dg_i = max(dg_i - L[i, j]^2, 0).  L: n x r column-major, pitch ldl >= n; piv_out: r indices; *rank_out (HOST): the steps taken.
+ * From the rank on the columns of L are zero and piv_out is -1.  X, L, piv_out host or device.  1 <= r <= min(n, 1024).  n r^2 / 2
+ * flop in 2 r small launches; fixed order, no atomics: two calls give the same bits.  Synchronous. */
+GPRC_API int gprc_dev_pivoted_cholesky(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                                       int64_t r, double* L, int64_t ldl, int64_t* piv_out, int64_t* rank_out);
 
 /* ---- multi-GPU from ONE process (SURVEY 8b "Threading", 8e): the form the R `.Call` boundary can use ------------ *
  * The reference's host is a single R process; it cannot be forked per GPU.  A gprc_mgpu drives G ranks -- one per
