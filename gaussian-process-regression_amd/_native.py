@@ -162,6 +162,9 @@ PROTOTYPES = {
     "gprc_igpr_predict": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "gprc_igpr_get_alpha": (C.c_int, [_vp, _vp]),
     "gprc_igpr_stats": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "gprc_igpr_probes": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64]),
+    "gprc_igpr_logp_grad": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dp, _dp, _vp, _vp]),
+    "gprc_dev_lowrank_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "gprc_dev_pivoted_cholesky": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.POINTER(_i64)]),
 }
 

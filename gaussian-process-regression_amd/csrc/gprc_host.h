@@ -66,9 +66,12 @@ struct gprc_model {
   double elbo = 0.0, trace = 0.0, jitter = 0.0;
   int64_t n_train = 0;
   // MODEL_IGPR (gprc_iter.hip): X, y, alpha = K_y^-1 y by conjugate gradients and noise as a GPR model's; no factor (packed, winv and work
-  // stay null).  pq = Q (n x rank, pitch n) of the preconditioner (I - Q Q^T) / noise, null at rank 0; the solver's settings and what the
-  // fit's own solve reported:
+  // stay null).  pq = Q (n x rank, pitch n) of the preconditioner (I - Q Q^T) / noise, null at rank 0; pl = L (the same shape) of
+  // P = L L^T + noise I, for the probes of gprc_igpr_logp_grad, and logdet_p = log det P (0 at rank 0, where P = I there); the solver's
+  // settings and what the fit's own solve reported:
   double* pq = nullptr;
+  double* pl = nullptr;
+  double logdet_p = 0.0;
   int64_t rank = 0;
   double cg_tol = 0.0, cg_relres = 0.0, cg_relres_true = 0.0;
   int cg_max_iter = 0, cg_iters = 0;
@@ -198,6 +201,9 @@ int gen_gemm(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const double
 // X (n x S, pitch ldx) = K_y^-1 B (pitch ldb) of a MODEL_IGPR by preconditioned conjugate gradients, DEVICE pointers, asynchronous past
 // the last block's statistics.  iters, relres, relres_true: S host entries each or null.  Returns 0, GPRC_ERR_MAXITER (every output
 // written from the last iterate) or GPRC_ERR_NOT_PD.
-int igpr_solve_dev(gprc_model* m, const double* B, int64_t ldb, int64_t S, double* X, int64_t ldx, int* iters, double* relres, double* relres_true);
+// hist: null, or per column the host vector that receives its conjugate-gradient coefficients, alpha_0, beta_0, alpha_1, beta_1, ...:
+// 2 iters[s] entries, the last beta unused (S vectors; iters must then be given).  The bits of every other output do not depend on it.
+int igpr_solve_dev(gprc_model* m, const double* B, int64_t ldb, int64_t S, double* X, int64_t ldx, int* iters, double* relres, double* relres_true,
+                   std::vector<double>* hist = nullptr);
 
 }  // namespace gprc

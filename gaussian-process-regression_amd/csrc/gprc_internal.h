@@ -7,7 +7,8 @@
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
 //   gprc_sparse.hip the sparse GPR with inducing points (fit pass, collapsed bound and its gradient, predict) and its entry points
 //   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create, eval and eval_grad) and their entry points
-//   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict)
+//   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict, and
+//                   the stochastic log evidence with its gradient)
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
@@ -195,15 +196,34 @@ int launch_copy_scaled(hipStream_t s, const double* src, int64_t lds, double* ds
 // Z = (V - Q (Q^T V)) / noise: Q n x r, V and Z n x S, T r x S work, all with pitch = rows.  Profiled as PK_ROWREDUCE.
 int launch_apply_precond(hipStream_t s, const double* Q, int64_t r, const double* V, int64_t n, int64_t S, double noise, double* T, double* Z);
 int launch_cg_init(hipStream_t s, const double* B, int64_t ldb, int64_t n, int64_t S, double tol, double* R, double* X, double* sc);   // r = b, x = 0
-// AP = K P on entry: AP += noise P, alpha, x += alpha p, r -= alpha Ap, |r|^2, freeze
-int launch_cg_step(hipStream_t s, const double* P, double* AP, double* X, double* R, int64_t n, int64_t S, double noise, double* sc);
-int launch_cg_direction(hipStream_t s, const double* R, const double* Z, double* P, int64_t n, int64_t S, bool first, double* sc);   // beta, p = z + beta p
+// AP = K P on entry: AP += noise P, alpha, x += alpha p, r -= alpha Ap, |r|^2, freeze.  hist: null, or max_iter x CG_SB x 2 doubles that
+// get every running column's coefficients, alpha of step it (from 0) at hist[(it CG_SB + s) 2] (cg_step) and the beta that follows it at
+// hist[(it CG_SB + s) 2 + 1] (cg_direction, not `first`); x, r, p and the scalars have the same bits with and without it.
+int launch_cg_step(hipStream_t s, const double* P, double* AP, double* X, double* R, int64_t n, int64_t S, double noise, double* sc, double* hist = nullptr,
+                   int it = 0);
+int launch_cg_direction(hipStream_t s, const double* R, const double* Z, double* P, int64_t n, int64_t S, bool first, double* sc, double* hist = nullptr,
+                        int it = 0);   // beta, p = z + beta p
 // AX = K X on entry: out[s] = |b_s - (K + noise I) x_s| / |b_s|
 int launch_cg_residual(hipStream_t s, const double* B, int64_t ldb, const double* AX, const double* X, int64_t n, int64_t S, double noise, const double* sc,
                        double* out);
 int launch_cg_var(hipStream_t s, const double* A, const double* W, int64_t n, int64_t S, double* out);   // out[s] = 1 - a_s . w_s
 // F = (y 1^T - F) - sqn E in place: the right-hand sides of the sample paths from the prior term
 int launch_paths_rhs(hipStream_t s, const double* y, double* F, int64_t ldf, const double* E, int64_t lde, double sqn, int64_t n, int64_t S);
+
+// ---- launchers (kernels_igrad.hip: the iterative GPR's evidence gradient) -------------------------
+// the low-rank-weighted contraction: per workgroup (stripe of 64-row tiles x 64-column tile) `part` gets the ks.n_params sums
+//   sum_ij (sum_{r < R} A[i + r lda] B[j + r ldb]) (integrand of theta_k at (x_i, x_j)),   i, j < n,   1 <= R <= IG_RMAX,
+// without the factors that do not depend on (i, j) -- those of cross_grad_finish; lowrank_grad_wgs(n) rows of n_params, to be added in
+// order.  The weight is formed on the f64 MFMA and never stored.  Kernels: those of with_gradient_kernel.  Profiled as PK_GRAD_CONTRACT.
+constexpr int IG_RMAX = 64;
+int64_t lowrank_grad_wgs(int64_t n);
+int launch_lowrank_grad(hipStream_t s, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* A, int64_t lda, const double* B,
+                        int64_t ldb, int64_t R, double* part);
+// out[s] = sum_i U[i + s ldu] V[i + s ldv], s < S: one workgroup a column, kernels_cg.hip's order of summation
+int launch_col_dots(hipStream_t s, const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t n, int64_t S, double* out);
+// Z[i + s ldz] = fma(sigma, G2[i + s ldg2], sum_{a < r} L[i + a n] G1[a + s ldg1]) (a ascending), i < n, s < T; r = 0: Z = G2
+int launch_igpr_probes(hipStream_t s, const double* L, int64_t r, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, double sigma,
+                       int64_t n, int64_t T, double* Z, int64_t ldz);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

@@ -9,6 +9,11 @@
 //                    |r|^2 and nothing else.  A column stops at |r|^2 <= tol^2 |b|^2 -- the doubles the device compares, so host and device
 //                    agree on which columns run -- and is frozen: no kernel writes its x, r or p again.
 //   after the loop   one more product: the TRUE residual |b - K_y x| / |b| per column; the recurrence drifts from it.
+//   evidence         gprc_igpr_logp_grad ("Iterative GPR evidence"): probes z = L g1 + sigma g2 ~ N(0, P), w = P^-1 z, u = K_y^-1 z
+//                    by the loop above, which then also stores every column's alpha_j and beta_j; per probe the Lanczos tridiagonal of
+//                    P^-1/2 K_y P^-1/2 from those coefficients and its Gauss quadrature of log on the host (host_quadrature.h); the
+//                    gradient's n x n weight 1/2 alpha alpha^T - 1/(2T) sum u w^T as two n x (T + 1) factors, contracted with dK / dtheta
+//                    by kernels_igrad.hip without being formed.  The model keeps L beside Q and log det P for it.
 // Invariance: a column's bits are the same alone or in any batch, on every call, from host and from device pointers -- each (s, i)
 // accumulator of the product is its own chain, every vector step has one workgroup and one set of scalars per column.
 #include <algorithm>
@@ -17,6 +22,7 @@
 #include <vector>
 
 #include "gprc_host.h"
+#include "host_quadrature.h"
 #include "pair_tile.h"
 
 namespace gprc {
@@ -61,6 +67,8 @@ int build_preconditioner(gprc_model* m, int64_t r) {
   int64_t rank = 0;
   GPRC_TRY(pivoted_cholesky(ctx, m->ks, m->X, m->d, n, r, vt.p, ld, reinterpret_cast<int64_t*>(piv.p), &rank));
   m->rank = rank;
+  GPRC_TRY(pool_alloc(ctx, sizeof(double) * (size_t)(n * rank), (void**)&m->pl));   // L itself: the probes z = L g1 + sigma g2 of the evidence
+  GPRC_TRY(launch_copy_scaled(s, vt.p, ld, m->pl, n, n, rank, 1.0));
   auto form_b = [&]() -> int {   // B = I + L^T L / noise, packed
     GPRC_HIP(hipMemsetAsync(packed.p, 0, packed.bytes, s));
     GPRC_TRY(launch_gram_rows(s, vt.p, ld, rows, r_pad, packed.p));
@@ -70,18 +78,24 @@ int build_preconditioner(gprc_model* m, int64_t r) {
   int info = 0;
   GPRC_TRY(factor_all_or_refill(ctx, packed.p, r_pad, winv.p, &info, nullptr, form_b));
   if (info != 0) { set_error("igpr_fit: the preconditioner's I + L^T L / noise is not positive definite (leading minor of order " + std::to_string(info) + ")"); return GPRC_ERR_NOT_PD; }
+  // log det P = n log noise + log det B = n log noise + 2 sum log diag(C); the columns from the rank on are zero, their diagonal is 1
+  double half_logdet_b = 0.0;
+  GPRC_TRY(launch_diag_log_sum(s, packed.p, r_pad, r, ctx->scal_dev));
+  GPRC_HIP(hipMemcpyAsync(&half_logdet_b, ctx->scal_dev, sizeof(double), hipMemcpyDeviceToHost, s));
   GPRC_TRY(solve_rows(ctx, packed.p, winv.p, r_pad, vt.p, ld, rows));   // L C^-T
   GPRC_TRY(pool_alloc(ctx, sizeof(double) * (size_t)(n * rank), (void**)&m->pq));
   GPRC_TRY(launch_copy_scaled(s, vt.p, ld, m->pq, n, n, rank, std::sqrt(m->noise)));
   GPRC_HIP(hipStreamSynchronize(s));   // the workspaces go out of scope
+  m->logdet_p = (double)n * std::log(m->noise) + 2.0 * half_logdet_b;
   return 0;
 }
 
 // one block of S <= CG_SB right-hand sides; the five n x S buffers and the scalars are the caller's
-struct CgWork { double *x, *r, *z, *p, *ap, *t, *sc, *res; };
+// hist: null, or cg_max_iter x CG_SB x 2 doubles for the coefficients (launch_cg_step)
+struct CgWork { double *x, *r, *z, *p, *ap, *t, *sc, *res, *hist; };
 
 int cg_block(gprc_model* m, const CgWork& w, const double* B, int64_t ldb, int64_t S, double* X, int64_t ldx, int* iters, double* relres,
-             double* relres_true, bool* maxiter_hit) {
+             double* relres_true, bool* maxiter_hit, std::vector<double>* hist_out) {
   gprc_ctx* ctx = m->ctx;
   hipStream_t s = ctx->stream;
   const int64_t n = m->n;
@@ -103,9 +117,9 @@ int cg_block(gprc_model* m, const CgWork& w, const double* B, int64_t ldb, int64
   int64_t bad = -1;
   while (running > 0 && it < m->cg_max_iter) {
     GPRC_TRY(product(w.p, w.ap));
-    GPRC_TRY(launch_cg_step(s, w.p, w.ap, w.x, w.r, n, S, m->noise, w.sc));
+    GPRC_TRY(launch_cg_step(s, w.p, w.ap, w.x, w.r, n, S, m->noise, w.sc, w.hist, it));
     GPRC_TRY(precondition());
-    GPRC_TRY(launch_cg_direction(s, w.r, z, w.p, n, S, false, w.sc));
+    GPRC_TRY(launch_cg_direction(s, w.r, z, w.p, n, S, false, w.sc, w.hist, it));
     GPRC_HIP(hipMemcpyAsync(rr, w.sc + CG_RR * CG_SB, sizeof(double) * S, hipMemcpyDeviceToHost, s));
     GPRC_HIP(hipStreamSynchronize(s));
     ++it;
@@ -123,6 +137,18 @@ int cg_block(gprc_model* m, const CgWork& w, const double* B, int64_t ldb, int64
     return GPRC_ERR_NOT_PD;
   }
   if (running > 0) *maxiter_hit = true;
+  if (w.hist && hist_out && it > 0) {   // a column's own steps: those it ran before it froze
+    std::vector<double> h((size_t)it * CG_SB * 2);
+    GPRC_HIP(hipMemcpyAsync(h.data(), w.hist, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    GPRC_HIP(hipStreamSynchronize(s));
+    for (int64_t c = 0; c < S; ++c) {
+      hist_out[c].resize((size_t)it_of[c] * 2);
+      for (int j = 0; j < it_of[c]; ++j) {
+        hist_out[c][2 * j] = h[((size_t)j * CG_SB + c) * 2];
+        hist_out[c][2 * j + 1] = j + 1 < it_of[c] ? h[((size_t)j * CG_SB + c) * 2 + 1] : 0.0;
+      }
+    }
+  }
   GPRC_TRY(product(w.x, w.ap));
   GPRC_TRY(launch_cg_residual(s, B, ldb, w.ap, w.x, n, S, m->noise, w.sc, w.res));
   GPRC_HIP(hipMemcpy2DAsync(X, sizeof(double) * ldx, w.x, sizeof(double) * n, sizeof(double) * n, (size_t)S, hipMemcpyDeviceToDevice, s));
@@ -137,21 +163,57 @@ int cg_block(gprc_model* m, const CgWork& w, const double* B, int64_t ldb, int64
   return 0;
 }
 
+// acc[k] += sum_ij (A B^T)_ij (integrand of theta_k), DEVICE pointers, any R: blocks of IG_RMAX columns, one launch each, the partials of
+// a launch added in workgroup order and the blocks in order, in long double; synchronises
+int lowrank_grad_dev(gprc_ctx* ctx, const KernelSpec& ks, const double* X, int64_t d, int64_t n, const double* A, int64_t lda, const double* B,
+                     int64_t ldb, int64_t R, long double* acc) {
+  hipStream_t s = ctx->stream;
+  const int64_t wgs = lowrank_grad_wgs(n);
+  DevMem part;
+  GPRC_TRY(part.alloc(wgs * ks.n_params));
+  std::vector<double> hp((size_t)(wgs * ks.n_params));
+  for (int64_t r0 = 0; r0 < R; r0 += IG_RMAX) {
+    GPRC_TRY(launch_lowrank_grad(s, ks, X, d, n, A + r0 * lda, lda, B + r0 * ldb, ldb, std::min<int64_t>(IG_RMAX, R - r0), part.p));
+    GPRC_HIP(hipMemcpyAsync(hp.data(), part.p, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, s));
+    GPRC_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < ks.n_params; ++k) {
+      long double sum = 0.0L;
+      for (int64_t g = 0; g < wgs; ++g) sum += (long double)hp[(size_t)(g * ks.n_params + k)];
+      acc[k] += sum;
+    }
+  }
+  return 0;
+}
+
+// Z (n x T, pitch ldz, DEVICE) from DEVICE G1 and G2
+int igpr_probes_dev(gprc_model* m, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T, double* Z, int64_t ldz) {
+  return launch_igpr_probes(m->ctx->stream, m->pl, m->rank, G1, ldg1, G2, ldg2, std::sqrt(m->noise), m->n, T, Z, ldz);
+}
+
+int check_probe_args(const char* who, const gprc_model* m, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T) {
+  if (T < 1 || T > 65535) { set_error(std::string(who) + ": the number of probes T must be between 1 and 65535"); return GPRC_ERR_ARG; }
+  if (!G2 || ldg2 < m->n) { set_error(std::string(who) + ": G2 must be non-null with ldg2 >= n"); return GPRC_ERR_ARG; }
+  if (m->rank > 0 && (!G1 || ldg1 < m->rank)) { set_error(std::string(who) + ": G1 must be non-null with ldg1 >= the preconditioner's rank"); return GPRC_ERR_ARG; }
+  return 0;
+}
+
 }  // namespace
 
-int igpr_solve_dev(gprc_model* m, const double* B, int64_t ldb, int64_t S, double* X, int64_t ldx, int* iters, double* relres, double* relres_true) {
+int igpr_solve_dev(gprc_model* m, const double* B, int64_t ldb, int64_t S, double* X, int64_t ldx, int* iters, double* relres, double* relres_true,
+                   std::vector<double>* hist) {
   const int64_t n = m->n, sb = std::min<int64_t>(S, CG_SB);
-  DevMem vec, small;
+  DevMem vec, small, hbuf;
+  if (hist) GPRC_TRY(hbuf.alloc((int64_t)m->cg_max_iter * CG_SB * 2));
   GPRC_TRY(vec.alloc((m->pq ? 5 : 4) * n * sb));
   GPRC_TRY(small.alloc(std::max<int64_t>(m->rank, 1) * sb + (CG_ROWS + 1) * CG_SB));
   CgWork w{};
   w.x = vec.p; w.r = w.x + n * sb; w.p = w.r + n * sb; w.ap = w.p + n * sb; w.z = m->pq ? w.ap + n * sb : nullptr;
-  w.t = small.p; w.sc = w.t + std::max<int64_t>(m->rank, 1) * sb; w.res = w.sc + CG_ROWS * CG_SB;
+  w.t = small.p; w.sc = w.t + std::max<int64_t>(m->rank, 1) * sb; w.res = w.sc + CG_ROWS * CG_SB; w.hist = hbuf.p;
   bool maxiter_hit = false;
   for (int64_t s0 = 0; s0 < S; s0 += CG_SB) {
     const int64_t scur = std::min<int64_t>(CG_SB, S - s0);
     GPRC_TRY(cg_block(m, w, B + s0 * ldb, ldb, scur, X + s0 * ldx, ldx, iters ? iters + s0 : nullptr, relres ? relres + s0 : nullptr,
-                      relres_true ? relres_true + s0 : nullptr, &maxiter_hit));
+                      relres_true ? relres_true + s0 : nullptr, &maxiter_hit, hist ? hist + s0 : nullptr));
   }
   if (maxiter_hit) {
     GPRC_HIP(hipStreamSynchronize(m->ctx->stream));   // the outputs of the last iterate are complete when the caller sees the status
@@ -263,6 +325,119 @@ int gprc_igpr_stats(gprc_model* m, int* iterations_out, double* relres_recurrenc
   if (relres_recurrence_out) *relres_recurrence_out = m->cg_relres;
   if (relres_true_out) *relres_true_out = m->cg_relres_true;
   if (rank_out) *rank_out = m->rank;
+  return 0;
+}
+
+int gprc_igpr_probes(gprc_model* m, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T, double* Z_out, int64_t ldz) {
+  GPRC_TRY(igpr_usable("igpr_probes", m));
+  GPRC_TRY(check_probe_args("igpr_probes", m, G1, ldg1, G2, ldg2, T));
+  if (!Z_out || ldz < m->n) { set_error("igpr_probes: Z_out must be non-null with ldz >= n"); return GPRC_ERR_ARG; }
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  In g1, g2;
+  Out o;
+  if (m->rank > 0) GPRC_TRY(g1.set(s, G1, ldg1 * (T - 1) + m->rank));
+  GPRC_TRY(g2.set(s, G2, ldg2 * (T - 1) + m->n));
+  GPRC_TRY(o.set(Z_out, ldz, m->n, T));
+  GPRC_TRY(igpr_probes_dev(m, g1.dev, ldg1, g2.dev, ldg2, T, o.dev, o.ld));
+  return finish_sync(s, o);
+}
+
+int gprc_igpr_logp_grad(gprc_model* m, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T, double* logp_out, double* se_out,
+                        double* grad_out, double* terms_out) {
+  GPRC_TRY(igpr_usable("igpr_logp_grad", m));
+  GPRC_TRY(check_probe_args("igpr_logp_grad", m, G1, ldg1, G2, ldg2, T));
+  if (!logp_out || !grad_out) { set_error("igpr_logp_grad: null logp_out or grad_out"); return GPRC_ERR_ARG; }
+  if (se_out && T < 2) { set_error("igpr_logp_grad: the standard error needs T >= 2 probes"); return GPRC_ERR_ARG; }
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n, R = T + 1;
+  const int np = m->ks.n_params;
+  In g1, g2;
+  if (m->rank > 0) GPRC_TRY(g1.set(s, G1, ldg1 * (T - 1) + m->rank));
+  GPRC_TRY(g2.set(s, G2, ldg2 * (T - 1) + n));
+  // A = [alpha, u_1 .. u_T], B = [alpha / 2, -w_1 / (2 T) .. -w_T / (2 T)]: G = A B^T (never formed); z and w = P^-1 z beside them
+  DevMem za, zb, zz, zw, tq, dots;
+  GPRC_TRY(za.alloc(n * R));
+  GPRC_TRY(zb.alloc(n * R));
+  GPRC_TRY(zz.alloc(n * T));
+  if (m->pq) GPRC_TRY(zw.alloc(n * T));
+  GPRC_TRY(tq.alloc(std::max<int64_t>(m->rank, 1) * CG_SB));
+  GPRC_TRY(dots.alloc(2 * T + 2));
+  double *U = za.p + n, *Z = zz.p, *W = m->pq ? zw.p : zz.p;   // rank 0: P = I, w = z
+  GPRC_TRY(igpr_probes_dev(m, g1.dev, ldg1, g2.dev, ldg2, T, Z, n));
+  if (m->pq)
+    for (int64_t s0 = 0; s0 < T; s0 += CG_SB)   // the blocks of the loop: w is what the loop's first preconditioned residual is
+      GPRC_TRY(launch_apply_precond(s, m->pq, m->rank, Z + s0 * n, n, std::min<int64_t>(CG_SB, T - s0), m->noise, tq.p, W + s0 * n));
+  std::vector<int> iters((size_t)T);
+  std::vector<std::vector<double>> hist((size_t)T);
+  const int rc = igpr_solve_dev(m, Z, n, T, U, n, iters.data(), nullptr, nullptr, hist.data());
+  if (rc != 0 && rc != GPRC_ERR_MAXITER) return rc;
+  const std::string maxiter_msg = rc != 0 ? gprc_last_error() : "";
+  GPRC_HIP(hipMemcpyAsync(za.p, m->alpha, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  GPRC_TRY(launch_copy_scaled(s, m->alpha, n, zb.p, n, n, 1, 2.0));
+  GPRC_TRY(launch_copy_scaled(s, W, n, zb.p + n, n, n, T, -2.0 * (double)T));
+  GPRC_TRY(launch_col_dots(s, Z, n, W, n, n, T, dots.p));             // z^T P^-1 z
+  GPRC_TRY(launch_col_dots(s, U, n, W, n, n, T, dots.p + T));         // u^T w
+  GPRC_TRY(launch_col_dots(s, m->y, n, m->alpha, n, n, 1, dots.p + 2 * T));
+  GPRC_TRY(launch_col_dots(s, m->alpha, n, m->alpha, n, n, 1, dots.p + 2 * T + 1));
+  std::vector<double> hd((size_t)(2 * T + 2));
+  GPRC_HIP(hipMemcpyAsync(hd.data(), dots.p, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, s));
+  std::vector<long double> acc((size_t)np, 0.0L);
+  GPRC_TRY(lowrank_grad_dev(ctx, m->ks, m->X, m->d, n, za.p, n, zb.p, n, R, acc.data()));   // synchronises
+  cross_grad_finish(m->ks, acc.data(), grad_out);
+  // the quadrature: q_s = (z^T P^-1 z) e_1^T log(T_s) e_1 from the column's own coefficients
+  std::vector<double> q((size_t)T), al, be, dg, of;
+  long double qsum = 0.0L, uw = 0.0L;
+  for (int64_t c = 0; c < T; ++c) {
+    const int mm = iters[(size_t)c];
+    double quad = 0.0;
+    if (mm > 0) {
+      al.resize((size_t)mm); be.resize((size_t)mm); dg.resize((size_t)mm); of.resize((size_t)mm);
+      for (int j = 0; j < mm; ++j) { al[j] = hist[(size_t)c][2 * j]; be[j] = hist[(size_t)c][2 * j + 1]; }
+      cg_tridiagonal(mm, al.data(), be.data(), dg.data(), of.data());
+      const int qrc = tridiag_log_quadrature(mm, dg.data(), of.data(), &quad);
+      if (qrc != QUAD_OK) {
+        set_error("igpr_logp_grad: the Lanczos tridiagonal of probe " + std::to_string(c) + (qrc == QUAD_NOT_POSITIVE ? " has a non-positive eigenvalue" : " did not yield its eigenvalues") +
+                  ": the preconditioned matrix is not positive definite in floating point");
+        return GPRC_ERR_NOT_PD;
+      }
+    }
+    q[(size_t)c] = hd[(size_t)c] * quad;
+    qsum += (long double)q[(size_t)c];
+    uw += (long double)hd[(size_t)(T + c)];
+  }
+  const long double mean_q = qsum / (long double)T;
+  const double two_pi = 6.283185307179586476925286766559;
+  *logp_out = (double)(-0.5L * (long double)hd[(size_t)(2 * T)] - 0.5L * ((long double)m->logdet_p + mean_q) - 0.5L * (long double)n * (long double)std::log(two_pi));
+  grad_out[np] = (double)(0.5L * (long double)hd[(size_t)(2 * T + 1)] - uw / (2.0L * (long double)T));
+  if (se_out) {
+    long double ss = 0.0L;
+    for (int64_t c = 0; c < T; ++c) { const long double dq = (long double)q[(size_t)c] - mean_q; ss += dq * dq; }
+    *se_out = (double)(0.5L * std::sqrt(ss / (long double)(T - 1)) / std::sqrt((long double)T));
+  }
+  if (terms_out) for (int64_t c = 0; c < T; ++c) terms_out[c] = q[(size_t)c];
+  if (rc != 0) set_error(maxiter_msg);
+  return rc;
+}
+
+int gprc_dev_lowrank_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n, const double* A,
+                          int64_t lda, const double* B, int64_t ldb, int64_t R, double* grad_out) {
+  GPRC_TRY(use_device_unless(ctx, !X || !A || !B || !grad_out || d < 1 || n < 1 || R < 1 || lda < n || ldb < n,
+                             "dev_lowrank_grad: bad arguments (non-null pointers, d, n, R >= 1, lda >= n, ldb >= n)"));
+  GPRC_TRY(check_grad_kernel("dev_lowrank_grad", kernel));
+  KernelSpec ks;
+  GPRC_TRY(make_spec(kernel, params, n_params, d, &ks));
+  hipStream_t s = ctx->stream;
+  In x, a, b;
+  GPRC_TRY(x.set(s, X, d * n));
+  GPRC_TRY(a.set(s, A, lda * (R - 1) + n));
+  GPRC_TRY(b.set(s, B, ldb * (R - 1) + n));
+  std::vector<long double> acc((size_t)ks.n_params, 0.0L);
+  GPRC_TRY(lowrank_grad_dev(ctx, ks, x.dev, d, n, a.dev, lda, b.dev, ldb, R, acc.data()));
+  cross_grad_finish(ks, acc.data(), grad_out);
   return 0;
 }
 

@@ -60,6 +60,7 @@ void free_model(gprc_model* m) {
   if (m->packed_b) pool_release(m->ctx, m->packed_b, sizeof(double) * (size_t)gprc_packed_size(m->n_pad));         // a sparse model's factor of B
   if (m->winv_b) pool_release(m->ctx, m->winv_b, sizeof(double) * (size_t)gprc_winv_size(m->n_pad));
   if (m->pq) pool_release(m->ctx, m->pq, sizeof(double) * (size_t)(m->n * m->rank));                                  // an iterative model's Q
+  if (m->pl) pool_release(m->ctx, m->pl, sizeof(double) * (size_t)(m->n * m->rank));                                  // ... and its L
   delete m;
 }
 

@@ -188,7 +188,9 @@ __global__ __launch_bounds__(256) void cg_init_kernel(const double* B, int64_t l
 
 // Ap += noise p;  alpha = r^T z / p^T A p;  x += alpha p;  r -= alpha Ap;  rr = |r|^2;  frozen when rr <= thr2.
 // p^T A p not finite or not positive: the column is frozen and its rr reads -1 (the host's GPRC_ERR_NOT_PD).  A frozen column is skipped.
-__global__ __launch_bounds__(256) void cg_step_kernel(const double* P, double* AP, double* X, double* R, int64_t n, double noise, double* sc) {
+// hist != nullptr: alpha of this step (it, from 0) goes to hist[(it CG_SB + s) 2]; x, r and the scalars have the same bits either way.
+__global__ __launch_bounds__(256) void cg_step_kernel(const double* P, double* AP, double* X, double* R, int64_t n, double noise, double* sc, double* hist,
+                                                      int it) {
   __shared__ double red[4];
   const int64_t s = blockIdx.x;
   if (sc[CG_ACT * CG_SB + s] == 0.0) return;   // workgroup-uniform
@@ -207,6 +209,7 @@ __global__ __launch_bounds__(256) void cg_step_kernel(const double* P, double* A
     return;
   }
   const double alpha = rz / pap;
+  if (hist && threadIdx.x == 0) hist[((int64_t)it * CG_SB + s) * 2] = alpha;
   acc = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) {   // a thread reads back the Ap it wrote itself
     x[i] = fma(alpha, p[i], x[i]);
@@ -222,7 +225,9 @@ __global__ __launch_bounds__(256) void cg_step_kernel(const double* P, double* A
 }
 
 // rz' = r^T z;  beta = rz' / rz (first: 0);  p = z + beta p.  A frozen column is skipped (first: its p is zero).
-__global__ __launch_bounds__(256) void cg_direction_kernel(const double* R, const double* Z, double* P, int64_t n, int first, double* sc) {
+// hist != nullptr and not first: beta, which follows step `it`, goes to hist[(it CG_SB + s) 2 + 1].
+__global__ __launch_bounds__(256) void cg_direction_kernel(const double* R, const double* Z, double* P, int64_t n, int first, double* sc, double* hist,
+                                                           int it) {
   __shared__ double red[4];
   const int64_t s = blockIdx.x;
   const double *r = R + s * n, *z = Z + s * n;
@@ -237,6 +242,7 @@ __global__ __launch_bounds__(256) void cg_direction_kernel(const double* R, cons
   for (int64_t i = threadIdx.x; i < n; i += 256) acc = fma(r[i], z[i], acc);
   const double rz = block_sum(acc, red);   // (its barriers order every thread's read of rz_old before the write below)
   const double beta = first ? 0.0 : rz / rz_old;
+  if (hist && !first && threadIdx.x == 0) hist[((int64_t)it * CG_SB + s) * 2 + 1] = beta;
   for (int64_t i = threadIdx.x; i < n; i += 256) p[i] = first ? z[i] : fma(beta, p[i], z[i]);
   if (threadIdx.x == 0) sc[CG_RZ * CG_SB + s] = rz;
 }
@@ -321,14 +327,14 @@ int launch_cg_init(hipStream_t s, const double* B, int64_t ldb, int64_t n, int64
   return 0;
 }
 
-int launch_cg_step(hipStream_t s, const double* P, double* AP, double* X, double* R, int64_t n, int64_t S, double noise, double* sc) {
-  hipLaunchKernelGGL(cg_step_kernel, dim3((unsigned)S), dim3(256), 0, s, P, AP, X, R, n, noise, sc);
+int launch_cg_step(hipStream_t s, const double* P, double* AP, double* X, double* R, int64_t n, int64_t S, double noise, double* sc, double* hist, int it) {
+  hipLaunchKernelGGL(cg_step_kernel, dim3((unsigned)S), dim3(256), 0, s, P, AP, X, R, n, noise, sc, hist, it);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_cg_direction(hipStream_t s, const double* R, const double* Z, double* P, int64_t n, int64_t S, bool first, double* sc) {
-  hipLaunchKernelGGL(cg_direction_kernel, dim3((unsigned)S), dim3(256), 0, s, R, Z, P, n, first ? 1 : 0, sc);
+int launch_cg_direction(hipStream_t s, const double* R, const double* Z, double* P, int64_t n, int64_t S, bool first, double* sc, double* hist, int it) {
+  hipLaunchKernelGGL(cg_direction_kernel, dim3((unsigned)S), dim3(256), 0, s, R, Z, P, n, first ? 1 : 0, sc, hist, it);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

@@ -58,28 +58,6 @@ struct SgradArgs {
   KernelSpec ks;      // derived constants, see make_deriv_spec
 };
 
-struct PairW { double h, hs, h2; };   // the weight, the first theta integrand (isotropic kernels), the second (gammaexp, ratquad)
-
-template <int KID>
-__device__ __forceinline__ PairW cross_weight(double s, const KernelSpec& ks) {
-  if constexpr (KID == GPRC_SQREXP) {
-    const double h = exp(-s * ks.p[1]);                               // p[1] = 1 / (2 l^2)
-    return {h, h * s, 0.0};
-  } else if constexpr (KID == GPRC_SQREXP_ARD) {
-    return {exp(-0.5 * s), 0.0, 0.0};                                 // s is the scaled distance
-  } else if constexpr (is_matern(KID)) {                              // p[1] = 3 / l^2 or 5 / l^2; ARD: s is the scaled distance
-    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
-    const double h = is_matern32(KID) ? e : fma(a, e, e);
-    return {h, h * s, 0.0};
-  } else if constexpr (KID == GPRC_GAMMAEXP) {                        // s > 0 (the caller skips s = 0: the limit for gamma > 1, the convention for gamma <= 1)
-    const double lg = log(s * ks.p[2]), u = exp(ks.p[3] * lg), ku = exp(-u) * u;   // p[2] = 1 / l^2, p[3] = gamma / 2
-    return {ku / s, ku, ku * lg};
-  } else {                                                            // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
-    const double x = s * ks.p[2], q = 1.0 + x, lq = log1p(x), h = exp(-ks.p[1] * lq) / q;
-    return {h, h * s, h * (x - q * lq)};
-  }
-}
-
 template <int KID, bool WITH_Z>
 __global__ __launch_bounds__(256) void cross_grad_kernel(SgradArgs a) {
   __shared__ __attribute__((aligned(16))) double As[PT_D][PT_R];

@@ -1,12 +1,14 @@
 // pair_tile.h -- the pairwise-tile core of the covariance side for gfx950 (MI355X), shared by kernels_fill.hip (the fills),
-// kernels_grad.hip (the contractions of both exact evidence gradients), kernels_pgrad.hip (the prediction gradients' contraction) and
-// kernels_sgrad.hip (the sparse bound gradient's contraction; its weight per pair is its own, for the reasons below).
+// kernels_grad.hip (the contractions of both exact evidence gradients), kernels_pgrad.hip (the prediction gradients' contraction),
+// kernels_sgrad.hip (the sparse bound gradient's contraction; its weight per pair, cross_weight, is its own, for the reasons below) and
+// kernels_igrad.hip (the iterative GPR's evidence gradient: cross_weight and the staging; its lane layout is the f64 MFMA accumulator's).
 //
 // One tile of point pairs: PT_R x PT_C = 128 x 64 per 256-thread workgroup, two consecutive rows x 16 columns per lane.  Both point
 // sets go through LDS PT_D = 16 coordinates at a time (As[r][i] coordinate-major for the 16-byte row reads, Bs[j][r] padded by one for
 // the column broadcasts); the squared distance of a lane's 32 pairs accumulates in s0[16] / s1[16]; a per-kernel epilogue follows.
 // What is here: the tile shape, the staging loop, the distance loop of the contraction kernels, the wave and four-wave sums, R's `^`,
-// the weight h of a pair in dk / dx* (pair_weight) with the factor it leaves to the tail (deriv_tail_factor),
+// the weight h of a pair in dk / dx* (pair_weight) with the factor it leaves to the tail (deriv_tail_factor), the weight and theta
+// integrands of a pair in dk / dtheta for a general weight matrix (cross_weight),
 // and for the host the derived constants of the contraction kernels, the set of kernels with an exact gradient and the dispatcher
 // from a run-time kernel id to a template instantiation.
 //
@@ -183,6 +185,31 @@ __device__ __forceinline__ double kernel_value(double s, const KernelSpec& ks) {
     return exp(-exp(ks.p[3] * log(s * ks.p[2])));                    // p[2] = 1 / l^2, p[3] = gamma / 2
   } else {                                                           // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
     return exp(-ks.p[1] * log1p(s * ks.p[2]));
+  }
+}
+
+// the weight of a pair in dk / dtheta and in dk / dz, with the theta integrands that hang on it, WITHOUT the factors that do not depend on
+// the pair (the table at the head of kernels_sgrad.hip): kernels_sgrad.hip's contraction over a stored G and kernels_igrad.hip's over a
+// low-rank one
+struct PairW { double h, hs, h2; };   // the weight, the first theta integrand (isotropic kernels), the second (gammaexp, ratquad)
+
+template <int KID>
+__device__ __forceinline__ PairW cross_weight(double s, const KernelSpec& ks) {
+  if constexpr (KID == GPRC_SQREXP) {
+    const double h = exp(-s * ks.p[1]);                               // p[1] = 1 / (2 l^2)
+    return {h, h * s, 0.0};
+  } else if constexpr (KID == GPRC_SQREXP_ARD) {
+    return {exp(-0.5 * s), 0.0, 0.0};                                 // s is the scaled distance
+  } else if constexpr (is_matern(KID)) {                              // p[1] = 3 / l^2 or 5 / l^2; ARD: s is the scaled distance
+    const double a = sqrt(is_ard(KID) ? (is_matern32(KID) ? 3.0 : 5.0) * s : s * ks.p[1]), e = exp(-a);
+    const double h = is_matern32(KID) ? e : fma(a, e, e);
+    return {h, h * s, 0.0};
+  } else if constexpr (KID == GPRC_GAMMAEXP) {                        // s > 0 (the caller skips s = 0: the limit for gamma > 1, the convention for gamma <= 1)
+    const double lg = log(s * ks.p[2]), u = exp(ks.p[3] * lg), ku = exp(-u) * u;   // p[2] = 1 / l^2, p[3] = gamma / 2
+    return {ku / s, ku, ku * lg};
+  } else {                                                            // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
+    const double x = s * ks.p[2], q = 1.0 + x, lq = log1p(x), h = exp(-ks.p[1] * lq) / q;
+    return {h, h * s, h * (x - q * lq)};
   }
 }
 

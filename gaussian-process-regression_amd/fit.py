@@ -328,6 +328,77 @@ def optimize_sparse(X, y, noise, name, Z, start=None, *, optimize_noise=True, op
             "func": _func_of(name, par)}
 
 
+def iter_logp_grad(X, y, noise, name, v, *, g1, g2, tol=1e-8, max_iter=1000, precond_rank=128, ctx=None):
+    """(logp, se, grad) of IterativeGPR(X, y, noise, name(v), tol, max_iter, precond_rank): the stochastic estimate of the log marginal
+    likelihood, its standard error over the probes and the estimate of its gradient (iterative.IterativeGPR.logp_grad;
+    gprc_igpr_logp_grad), a deterministic function of the standard normals g2 (n x T) and g1 (precond_rank x T; rows beyond the rank the
+    pivoted Cholesky reached are not used, and g1 may be None at precond_rank 0).  `v` in the order `dens` takes it; grad has len(v) + 1
+    entries, d logp / d noise last.  Raises GprcError (ERR_MAXITER, ERR_NOT_PD) as the model does."""
+    from .iterative import IterativeGPR
+    with IterativeGPR(X, y, noise, _func_of(name, np.atleast_1d(np.asarray(v, dtype=np.float64))), tol=tol, max_iter=max_iter,
+                      precond_rank=precond_rank, ctx=ctx) as model:
+        r, T = model.stats.rank, np.asarray(g2).reshape(model.X.shape[1], -1).shape[1]
+        if r > 0:
+            g1 = np.asarray(g1, dtype=np.float64).reshape(-1, T)[:r]
+        est = model.logp_grad(g1=g1 if r > 0 else None, g2=g2)
+    return est.value, est.se, est.grad
+
+
+def optimize_iterative(X, y, noise, name, start=None, *, n_probes=31, rng=None, tol=1e-8, max_iter=1000, precond_rank=128, optimize_noise=True,
+                       maxit=100, value_and_grad=None, ctx=None):
+    """`optimize` for the iterative exact GPR (iterative.IterativeGPR), at n where no n x n factor fits: maximise the stochastic estimate of
+    the log marginal likelihood (`iter_logp_grad`) of kernel `name` over its parameters, and over the noise when `optimize_noise`, with
+    vmmin on z = log(theta).  The standard normals behind the estimate -- g2 (n x n_probes), then g1 (precond_rank x n_probes), from rng
+    -- are drawn ONCE and reused at every evaluation (common random numbers), so vmmin sees a deterministic objective.  value_and_grad(theta,
+    noise) -> (logp, grad) or (logp, grad, se) replaces the native objective.  An evaluation that fails (the conjugate-gradient loop at
+    its iteration cap, a matrix not positive definite in floating point, a parameter over- or underflowing) counts as the sentinel
+    -10000.  Returns `optimize`'s dict(par, noise, value, counts, convergence, func) and `se`, the standard error of `value` (nan when
+    the hook gives none): IterativeGPR(X, y, r["noise"], r["func"]) is the fitted model."""
+    func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient, as `optimize`)
+    Xm = as_points(X)
+    d, n = Xm.shape
+    if start is None:
+        start = _default_start(name, d)
+    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
+    npar = theta0.size
+    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
+        raise ValueError("optimize_iterative: start values must be finite and > 0")
+    if not (noise > 0 and math.isfinite(noise)):
+        raise ValueError("optimize_iterative: noise must be finite and > 0")
+    with_noise = bool(optimize_noise)
+    if value_and_grad is None:
+        if int(n_probes) < 2:
+            raise ValueError("optimize_iterative: n_probes >= 2 is not TRUE")
+        ctx = ctx or nat.default_context()
+        rng = rng if rng is not None else np.random.default_rng()
+        g2 = np.asfortranarray(rng.standard_normal((n, int(n_probes))))
+        g1 = np.asfortranarray(rng.standard_normal((min(int(precond_rank), n), int(n_probes))))
+
+        def value_and_grad(theta, nz):
+            try:
+                val, se, g = iter_logp_grad(Xm, y, nz, name, theta, g1=g1, g2=g2, tol=tol, max_iter=max_iter, precond_rank=precond_rank, ctx=ctx)
+            except nat.GprcError as e:
+                if e.status in (nat.ERR_MAXITER, nat.ERR_NOT_PD):
+                    raise ArithmeticError("the conjugate-gradient loop did not converge") from e
+                raise
+            return val, g, se
+
+    z0 = np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0)
+    se_of = {}
+
+    def vg(t):
+        out = value_and_grad(t[:npar].copy(), float(t[npar]) if with_noise else float(noise))
+        g = np.asarray(out[1], dtype=np.float64)
+        se_of[float(out[0])] = float(out[2]) if len(out) > 2 else float("nan")   # by value: vmmin returns the value it accepted
+        return out[0], (g if with_noise else g[:npar])
+
+    z, fmin, fncount, grcount, fail = _maximise_over_log(z0, vg, maxit)
+    t = np.exp(z)
+    par = tuple(float(v) for v in t[:npar])
+    return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
+            "convergence": fail, "func": _func_of(name, par), "se": se_of.get(-fmin, float("nan"))}
+
+
 def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_grad=None, ctx=None):
     """Maximise the Laplace log evidence of GP classification (y in {-1, +1}) over the parameters of kernel `name` ("sqrexp",
     "gammaexp", "rationalquadratic", "sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard") with vmmin on z = log(theta), exactly as `optimize` does for regression.

@@ -7,8 +7,12 @@ all posterior sample paths and Thompson sampling are available at n where no fac
     var(x*) = 1 - k*^T K_y^-1 k*            (a full solve per 64 test points)
     preconditioner  P = L L^T + noise I,    L = precond_rank steps of the pivoted Cholesky of K
 
+    logp ~ -1/2 y^T alpha - 1/2 (log det P + mean_s q_s) - n/2 log 2 pi        (logp_grad: stochastic Lanczos quadrature on the
+    d logp / d theta ~ sum_ij (1/2 alpha alpha^T - 1/(2T) sum_s u_s w_s^T)_ij dK_ij   loop's own coefficients, Hutchinson probes z ~ N(0, P))
+
 Kernels: the stationary ones with k(x, x) = 1 -- sqrexp, sqrexp_ard, gammaexp, rationalquadratic and the four Matern kernels.
-Out of scope here: the log marginal likelihood and its gradient, add_data, several devices.
+fit.optimize_iterative maximises logp_grad's estimate over the kernel's parameters and the noise.
+Out of scope here: add_data, several devices.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import numpy as np
 from . import _native as nat
 from .covfunc import as_points, require_tagged
 
-__all__ = ["IterativeGPR", "SolveStats"]
+__all__ = ["IterativeGPR", "SolveStats", "EvidenceEstimate"]
 
 
 class SolveStats(NamedTuple):
@@ -29,6 +33,14 @@ class SolveStats(NamedTuple):
     relres_recurrence: float    # |r| / |y| of the loop's recurrence residual at the stop
     relres_true: float          # |y - K_y alpha| / |y| from one more product: the figure to trust
     rank: int                   # columns of the preconditioner's L (below precond_rank when the pivoted Cholesky ran out of diagonal)
+
+
+class EvidenceEstimate(NamedTuple):
+    """what IterativeGPR.logp_grad returns"""
+    value: float                # the estimate of the log marginal likelihood
+    se: float                   # its standard error over the probes, 1/2 std(terms, ddof = 1) / sqrt(T); nan for one probe
+    grad: np.ndarray            # d value / d (parameters, noise): len(parameters) + 1 entries, the order of fit.logp_grad
+    terms: np.ndarray           # the T quadrature terms q_s, E q_s = log det K_y - log det P
 
 
 class IterativeGPR:
@@ -92,6 +104,50 @@ class IterativeGPR:
         nat.check(nat.lib().gprc_igpr_solve(self._handle(), Bm.ctypes.data, n, S, out.ctypes.data, n, iters, res.ctypes.data_as(C.POINTER(C.c_double))))
         out = out[:, 0] if vector else out
         return (out, np.array(iters[:]), res) if with_stats else out
+
+    def _normals(self, g1, g2):
+        """(g1 rank x T or empty, g2 n x T, T) as Fortran arrays; g1 is not looked at without a preconditioner"""
+        n, r = self._X.shape[1], self._stats.rank
+        g2 = np.asfortranarray(np.asarray(g2, dtype=np.float64).reshape(n, -1))
+        T = g2.shape[1]
+        if T < 1:
+            raise ValueError("ncol(g2) >= 1 is not TRUE")
+        if r == 0:
+            return np.zeros((0, T), order="F"), g2, T
+        if g1 is None:
+            raise ValueError("g1 (stats.rank x T) is needed: the model has a preconditioner")
+        g1 = np.asfortranarray(np.asarray(g1, dtype=np.float64).reshape(-1, T))
+        if g1.shape[0] < r:
+            raise ValueError("nrow(g1) >= stats.rank is not TRUE")
+        return g1, g2, T
+
+    def probes(self, g1, g2):
+        """Z = L g1 + sqrt(noise) g2 (n x T), the probe vectors logp_grad draws its estimates from: z ~ N(0, P) for standard normal g1
+        (stats.rank x T) and g2 (n x T).  Without a preconditioner (rank 0) Z = g2 and g1 is ignored."""
+        g1, g2, T = self._normals(g1, g2)
+        n = self._X.shape[1]
+        Z = np.empty((n, T), order="F")
+        nat.check(nat.lib().gprc_igpr_probes(self._handle(), g1.ctypes.data if g1.size else None, max(g1.shape[0], 1), g2.ctypes.data, n, T,
+                                             Z.ctypes.data, n))
+        return Z
+
+    def logp_grad(self, n_probes=31, *, rng=None, g1=None, g2=None):
+        """EvidenceEstimate(value, se, grad, terms): the log marginal likelihood and its gradient with respect to (parameters, noise),
+        estimated from n_probes probe vectors through the conjugate-gradient loop (gprc_igpr_logp_grad).  A deterministic function of
+        the standard normals g1 (stats.rank x T) and g2 (n x T); drawn from rng (g2 first, then g1) when not given."""
+        n = self._X.shape[1]
+        if g2 is None:
+            if int(n_probes) < 1:
+                raise ValueError("n_probes >= 1 is not TRUE")
+            rng = rng if rng is not None else np.random.default_rng()
+            g2 = rng.standard_normal((n, int(n_probes)))
+            g1 = rng.standard_normal((self._stats.rank, int(n_probes)))
+        g1, g2, T = self._normals(g1, g2)
+        value, se = C.c_double(), C.c_double(float("nan"))
+        grad, terms = np.empty(len(self._k.native_params(self._X.shape[0])) + 1), np.empty(T)
+        nat.check(nat.lib().gprc_igpr_logp_grad(self._handle(), g1.ctypes.data if g1.size else None, max(g1.shape[0], 1), g2.ctypes.data, n, T,
+                                                C.byref(value), C.byref(se) if T >= 2 else None, grad.ctypes.data, terms.ctypes.data))
+        return EvidenceEstimate(value.value, se.value, grad, terms)
 
     def sample_paths(self, n_paths, n_features=1024, *, rng=None, nu=None, phase=None, w=None, e=None):
         """GPR.sample_paths with its arguments and its order of draws; the update term's weights come from the conjugate-gradient solve of

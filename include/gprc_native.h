@@ -322,8 +322,8 @@ GPRC_API int gprc_sgpr_get_c(gprc_model* model, double* c_out);
  * The exact model without its n x n factor: every solve with K_y = K(X, X) + noise I is a conjugate-gradient loop on the generated-
  * operand product of gprc_dev_kernel_gemm, which stores no kernel value ("Iterative GPR").  Kernels: those of
  * gprc_gpr_paths_create (stationary, k(x, x) = 1); any other id: GPRC_ERR_ARG.  noise = sigma^2, finite and > 0; tol > 0.
- * MEMORY: 5 n x 64 doubles for a block of right-hand sides, the product's partials (at most 1 GiB), n x rank for the preconditioner,
- * and X, y, alpha.  FLOP per iteration: one n x n generated product (n^2 (3 d + 40) + 2 n^2 S) and 4 n rank S for the preconditioner.
+ * MEMORY: 5 n x 64 doubles for a block of right-hand sides, the product's partials (at most 1 GiB), 2 n x rank for the preconditioner
+ * (Q, and L for the probes of gprc_igpr_logp_grad), and X, y, alpha.  FLOP per iteration: one n x n generated product (n^2 (3 d + 40) + 2 n^2 S) and 4 n rank S for the preconditioner.
  * Preconditioner: precond_rank steps of the pivoted Cholesky of K (gprc_dev_pivoted_cholesky) give L (n x rank); P = L L^T + noise I is
  * applied as P^-1 V = (V - Q (Q^T V)) / noise, Q formed once per model.  precond_rank = 0: none; clipped to n; < 0 or > 1024: GPRC_ERR_ARG.
  * Loop: right-hand sides in blocks of 64 columns; a column stops when its recurrence residual has |r| <= tol |b| (tested as
@@ -332,7 +332,7 @@ GPRC_API int gprc_sgpr_get_c(gprc_model* model, double* c_out);
  * drifts from it.  A column's bits are the same alone or in any batch, on every call, and from host or device pointers.
  * GPRC_ERR_MAXITER: a column did not meet tol within max_iter; gprc_igpr_solve and gprc_igpr_predict have then written every output
  * from the last iterate, gprc_igpr_fit returns no model.  GPRC_ERR_NOT_PD: p^T K_y p was not finite or not positive.
- * fit: alpha = K_y^-1 y.  The model holds X, y, alpha, Q and the statistics of that solve; it answers gprc_model_dims with (n, d), is
+ * fit: alpha = K_y^-1 y.  The model holds X, y, alpha, Q, L, log det P and the statistics of that solve; it answers gprc_model_dims with (n, d), is
  * released by gprc_model_free and is accepted by gprc_gpr_paths_create (U is then the conjugate-gradient solve of the paths' right-hand
  * sides; no reversed factor).  Every other gprc_gpr_*, gprc_sgpr_*, gprc_gpc_* call and gprc_model_get_L return GPRC_ERR_ARG for it, as
  * the gprc_igpr_* calls do for any other model.
@@ -349,6 +349,31 @@ GPRC_API int gprc_igpr_solve(gprc_model* model, const double* B, int64_t ldb, in
 GPRC_API int gprc_igpr_predict(gprc_model* model, const double* X_star, int64_t n_star, double* mean, double* var);
 GPRC_API int gprc_igpr_get_alpha(gprc_model* model, double* alpha_out);
 GPRC_API int gprc_igpr_stats(gprc_model* model, int* iterations_out, double* relres_recurrence_out, double* relres_true_out, int64_t* rank_out);
+/* The log marginal likelihood of an iterative model and its gradient, from the conjugate-gradient loop itself (DESIGN.md section 7,
+ * "Iterative GPR evidence"): stochastic Lanczos quadrature for log det K_y and a Hutchinson estimate of the trace in the gradient, both
+ * DETERMINISTIC functions of caller-supplied standard normals G1 (rank x T, pitch ldg1 >= rank; rank = gprc_igpr_stats' rank_out, ignored
+ * and may be NULL at rank 0) and G2 (n x T, pitch ldg2 >= n), host or device.  With P = L L^T + noise I the model's preconditioner (at
+ * rank 0: P = I) and sigma = sqrt(noise):
+ *   probes  z_s = L g1_s + sigma g2_s ~ N(0, P) (rank 0: z_s = g2_s);  w_s = P^-1 z_s;  u_s = K_y^-1 z_s by the model's loop, 64 columns a block
+ *   q_s     = (z_s^T w_s) e_1^T log(T_s) e_1,  T_s the Lanczos tridiagonal of P^-1/2 K_y P^-1/2 from the coefficients of the column's own
+ *           m = iterations steps: T[0,0] = 1 / alpha_0, T[j,j] = 1 / alpha_j + beta_{j-1} / alpha_{j-1}, T[j,j+1] = sqrt(beta_j) / alpha_j;
+ *           E q_s = log det K_y - log det P, and log det P = n log noise + 2 sum log diag(C), C the factor of I + L^T L / noise (rank 0: 0)
+ *   logp    = -1/2 y^T alpha - 1/2 (log det P + mean_s q_s) - n/2 log 2 pi;   se = 1/2 std(q, ddof = 1) / sqrt(T)
+ *   grad_k  = sum_ij G_ij dk(x_i, x_j) / dtheta_k,  G = 1/2 alpha alpha^T - 1/(2T) sum_s u_s w_s^T, never formed (gprc_dev_lowrank_grad);
+ *   d / d noise = 1/2 alpha^T alpha - 1/(2T) sum_s u_s^T w_s, last: the order of gprc_gpr_logp_grad.
+ * probes: Z_out (n x T, pitch ldz >= n, host or device) = the z_s alone.
+ * logp_grad: T >= 1; logp_out and grad_out (n_params + 1 doubles) on the HOST; se_out (host) may be NULL and needs T >= 2; terms_out (host,
+ * T doubles: the q_s) may be NULL.  Other arguments out of range, a model that is not iterative or whose context is gone: GPRC_ERR_ARG.
+ * GPRC_ERR_MAXITER as gprc_igpr_solve: every output is written, from the last iterates.  GPRC_ERR_NOT_PD as gprc_igpr_solve, and when a
+ * tridiagonal has an eigenvalue <= 0.  A second call gives the same bits, host and device pointers give the same bits, and q_s does not
+ * depend on which other probes are in the call.  The model is not changed.
+ * MEMORY: beside the solve's, 4 n (T + 1) doubles (z, w, u and the scaled copies) and max_iter x 128 doubles of coefficients; the model
+ * itself keeps L beside Q from the fit on, another n x rank doubles.  FLOP: T / 64 blocks of the solve, and the contraction below with
+ * R = T + 1. */
+GPRC_API int gprc_igpr_probes(gprc_model* model, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T, double* Z_out,
+                              int64_t ldz);
+GPRC_API int gprc_igpr_logp_grad(gprc_model* model, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T, double* logp_out,
+                                 double* se_out, double* grad_out, double* terms_out);
 
 /* ---- L2: GPC ------------------------------------------------------------------------------ */
 /* GPC$initialize (R/GPCclass.R:66-107): Laplace mode by Newton/IRLS; y in {-1,+1}.
@@ -532,6 +557,12 @@ GPRC_API int gprc_dev_feature_gemm_grad(gprc_ctx* ctx, const double* Nu, const d
                                         const double* W, int64_t ldw, int64_t S, double scale, double* dout, int64_t ld);
 GPRC_API int gprc_dev_kernel_gemm_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* A, int64_t rows,
                                        const double* Bpts, int64_t cols, int64_t d, const double* U, int64_t ldu, int64_t S, double* dout, int64_t ld);
+/* The low-rank-weighted contraction alone: grad_out[k] = sum_{i,j<n} (sum_{r<R} A[i + r lda] B[j + r ldb]) dk(x_i, x_j) / dtheta_k, k <
+ * n_params, in O(n^2 (R + d)) flop and O(n R) memory: the weight is formed tile by tile on the f64 matrix cores and never stored.  X (d x
+ * n), A and B (n x R, pitches lda, ldb >= n): host or device; grad_out: n_params doubles on the HOST; synchronous.  Kernels: those of
+ * gprc_igpr_fit, ARD with d <= 256.  R > 64 runs in blocks of 64 columns that are added in order.  No atomics: the same bits on every call. */
+GPRC_API int gprc_dev_lowrank_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                                   const double* A, int64_t lda, const double* B, int64_t ldb, int64_t R, double* grad_out);
 /* The partial pivoted Cholesky of K(X, X), matrix-free (kernels as gprc_igpr_fit: k(x, x) = 1): from dg = 1, for j = 0 .. r - 1: p = the
  * lowest index among the maxima of dg over the points not yet chosen; stop when dg_p <= n 2^-52; L[p, j] = sqrt(dg_p);
  * L[i, j] = (k(x_i, x_p) - sum_{t < j} L[i, t] L[p, t]) / L[p, j] (t ascending) for every point not yet chosen, 0 for the earlier pivots;
