@@ -34,7 +34,9 @@ struct FillArgs {
 // per-coordinate accumulation term (its ARD form rounds differently from the contraction kernels' staged a * sig - b * sig: pair_tile.h)
 template <int KID>
 __device__ __forceinline__ double accum(double s, double a, double b, double sig) {
-  if constexpr (KID == GPRC_LINEAR) return fma(sig * a, b, s);  // colSums(sigma * x * y)
+  // colSums(sigma * x * y) as sigma * (x * y): x * y rounds the same way for (x, y) and (y, x), so K(A, A) is symmetric bit for bit, which
+  // (sigma * x) * y is not (tests/test_gpu_fill.py)
+  if constexpr (KID == GPRC_LINEAR) return fma(sig, a * b, s);
   else if constexpr (KID == GPRC_POLYNOMIAL) return fma(a, b, s);  // colSums(x * y)
   else if constexpr (KID == GPRC_CONSTANT) return s;
   else if constexpr (is_ard(KID)) {
