@@ -348,7 +348,8 @@ int launch_loo_q(hipStream_t s, const double* negP, const double* sc, int64_t n_
 int launch_loo_noise_terms(hipStream_t s, const double* u, const double* alpha, const double* S, int64_t ld, int64_t n, double* out);
 // sampling support (kernels_eig.hip)
 int launch_pack_dense(hipStream_t s, const double* A, int64_t lda, int64_t m, int64_t n_pad, double* packed);
-int launch_sym_copy(hipStream_t s, const double* A, int64_t lda, int64_t m, double* W, double* V);
+int launch_sym_absmax(hipStream_t s, const double* A, int64_t lda, int m, double* mx);
+int launch_sym_copy(hipStream_t s, const double* A, int64_t lda, int64_t m, double scale, double* W, double* V);
 int launch_jacobi_sweep(hipStream_t s, double* W, double* V, int m, double* cs);
 int launch_jacobi_offnorm(hipStream_t s, const double* W, int m, double* off, double* dg);
 int launch_gather_scale_cols(hipStream_t s, const double* V, int m, const int* perm, const double* scale, double* out, int64_t ldo);

@@ -162,24 +162,33 @@ int sym_eigen_dev(gprc_ctx* ctx, const double* A_dev, int64_t lda, int64_t m, do
   GPRC_TRY(W.alloc(m * m));
   GPRC_TRY(cs.alloc(m + 2));
   GPRC_TRY(od.alloc(2 * m));
-  GPRC_TRY(launch_sym_copy(s, A_dev, lda, m, W.p, V_dev));
   std::vector<double> h(2 * m);
+  // The sweeps run on W = 2^-e A with max|W| in [1, 2): the stop rule squares the entries, and the squares of an A below 2^-511 or
+  // above 2^511 leave the double range.  A power of two changes no bit of a rotation, so the vectors are those of A and the values
+  // are scaled back exactly.
+  GPRC_TRY(launch_sym_absmax(s, A_dev, lda, (int)m, od.p));
+  GPRC_HIP(hipMemcpyAsync(h.data(), od.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  double amax = 0.0;
+  for (int64_t j = 0; j < m; ++j) amax = h[j] > amax ? h[j] : amax;
+  if (!std::isfinite(amax)) { set_error("eigen: matrix has non-finite entries"); return GPRC_ERR_ARG; }
+  const int e = amax > 0.0 ? std::min(std::max(std::ilogb(amax), -1022), 1022) : 0;
+  GPRC_TRY(launch_sym_copy(s, A_dev, lda, m, std::ldexp(1.0, -e), W.p, V_dev));
   int sweeps = 0;
   for (;; ++sweeps) {
     GPRC_TRY(launch_jacobi_offnorm(s, W.p, (int)m, od.p, od.p + m));
     GPRC_HIP(hipMemcpyAsync(h.data(), od.p, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, s));
     GPRC_HIP(hipStreamSynchronize(s));
     long double off2 = 0.0L, dg2 = 0.0L;
-    bool finite = true;
-    for (int64_t j = 0; j < m; ++j) { off2 += h[j]; dg2 += (long double)h[m + j] * h[m + j]; finite = finite && std::isfinite(h[j]) && std::isfinite(h[m + j]); }
-    if (!finite) { set_error("eigen: matrix has non-finite entries"); return GPRC_ERR_ARG; }
+    for (int64_t j = 0; j < m; ++j) { off2 += h[j]; dg2 += (long double)h[m + j] * h[m + j]; }
     // ||off||_F <= max(1e-15, m eps) ||A||_F: below m*eps the off-diagonal part is rounding noise of the rotations
     // themselves (a rank-deficient covariance keeps ~m^2 such entries alive in its null space) and never shrinks
     const long double rel = std::max(1e-15L, (long double)m * 2.220446049250313e-16L);
     if (off2 <= rel * rel * (off2 + dg2) || sweeps >= 40) break;
     if (m > 1) GPRC_TRY(launch_jacobi_sweep(s, W.p, V_dev, (int)m, cs.p));
   }
-  values.assign(h.begin() + m, h.end());
+  values.resize(m);
+  for (int64_t j = 0; j < m; ++j) values[j] = std::ldexp(h[m + j], e);
   perm.resize(m);
   for (int64_t j = 0; j < m; ++j) perm[j] = (int)j;
   std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return values[a] > values[b]; });

@@ -27,12 +27,30 @@ __global__ __launch_bounds__(256) void pack_dense_kernel(const double* A, int64_
   }
 }
 
-// W = symmetric copy of A's lower triangle (what eigen(symmetric = TRUE) / dsyevr('L') reads); V = I
-__global__ __launch_bounds__(256) void sym_copy_kernel(const double* A, int64_t lda, int64_t m, double* W, double* V) {
+// per column j: mx[j] = max_{i >= j} |A[i,j]| over the lower triangle, +Inf where an entry is NaN or Inf
+__global__ __launch_bounds__(256) void sym_absmax_kernel(const double* A, int64_t lda, int m, double* mx) {
+  const int j = blockIdx.x;
+  const double* col = A + (int64_t)j * lda;
+  double a = 0.0;
+  for (int i = j + threadIdx.x; i < m; i += 256) {
+    const double v = fabs(col[i]);
+    a = fmax(a, v <= 1.79769313486231570815e308 ? v : HUGE_VAL);  // the comparison is false for NaN
+  }
+  __shared__ double red[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a = fmax(a, __shfl_down(a, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) mx[j] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+// W = scale * (symmetric copy of A's lower triangle: what eigen(symmetric = TRUE) / dsyevr('L') reads); V = I.
+// scale is a power of two: the product is exact unless it falls below 2^-1022
+__global__ __launch_bounds__(256) void sym_copy_kernel(const double* A, int64_t lda, int64_t m, double scale, double* W, double* V) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= m) return;
   for (int64_t j = blockIdx.y; j < m; j += gridDim.y) {
-    W[i + j * m] = (i >= j) ? A[i + j * lda] : A[j + i * lda];
+    W[i + j * m] = scale * ((i >= j) ? A[i + j * lda] : A[j + i * lda]);
     V[i + j * m] = (i == j) ? 1.0 : 0.0;
   }
 }
@@ -166,9 +184,15 @@ int launch_pack_dense(hipStream_t s, const double* A, int64_t lda, int64_t m, in
   return 0;
 }
 
-int launch_sym_copy(hipStream_t s, const double* A, int64_t lda, int64_t m, double* W, double* V) {
+int launch_sym_absmax(hipStream_t s, const double* A, int64_t lda, int m, double* mx) {
+  hipLaunchKernelGGL(sym_absmax_kernel, dim3((unsigned)m), dim3(256), 0, s, A, lda, m, mx);
+  GPRC_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_sym_copy(hipStream_t s, const double* A, int64_t lda, int64_t m, double scale, double* W, double* V) {
   const unsigned gy = (unsigned)(m < 16384 ? m : 16384);
-  hipLaunchKernelGGL(sym_copy_kernel, dim3(blocks(m, 256), gy), dim3(256), 0, s, A, lda, m, W, V);
+  hipLaunchKernelGGL(sym_copy_kernel, dim3(blocks(m, 256), gy), dim3(256), 0, s, A, lda, m, scale, W, V);
   GPRC_LAUNCH_CHECK();
   return 0;
 }

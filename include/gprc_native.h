@@ -644,7 +644,11 @@ GPRC_API int gprc_mvn_sample(gprc_ctx* ctx, const double* cov, int64_t ld, int64
                     int64_t n_draws, double* out, int* method_out);
 /* eigen(A, symmetric = TRUE): eigenvalues in decreasing order and orthonormal eigenvectors (columns, m x m, may be
  * NULL); only the lower triangle of A is read (LAPACK dsyevr 'L', as R calls it).  Cyclic two-sided Jacobi with a
- * round-robin pair order on the device, m <= 16384; *sweeps_out = sweeps used. */
+ * round-robin pair order on the device, m <= 16384; *sweeps_out = sweeps used (at most 40).
+ * Range: the sweeps run on 2^-e A, 2^e <= max|A| < 2^(e+1), and the values are scaled back, so any finite A is accepted and
+ * 2^s A returns the vectors of A bit for bit and 2^s times its values, as long as those stay between 2^-1022 and 2^1024 in
+ * magnitude: a value beyond the double range comes back as +-Inf, one below 2^-1022 loses its low bits, and entries below
+ * 2^-1022 max|A| are read as less than they are.  A NaN or Inf in the lower triangle is GPRC_ERR_ARG. */
 GPRC_API int gprc_sym_eigen(gprc_ctx* ctx, const double* A, int64_t lda, int64_t m, double* values_out, double* vectors_out,
                    int* sweeps_out);
 
