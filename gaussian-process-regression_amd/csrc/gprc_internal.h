@@ -225,6 +225,30 @@ int launch_col_dots(hipStream_t s, const double* U, int64_t ldu, const double* V
 int launch_igpr_probes(hipStream_t s, const double* L, int64_t r, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, double sigma,
                        int64_t n, int64_t T, double* Z, int64_t ldz);
 
+// ---- launchers (kernels_batch.hip: small GPs in batches) -------------------------------------------
+// One model of n_b <= GPRC_BATCH_MAX_N points per workgroup: fill, factor, solve and (want_grad) the gradient's sums in one launch of
+// `models` <= GPRC_BATCH_LAUNCH workgroups; workgroup g handles model b0 + g.  Per model b (all DEVICE memory):
+//   prm + b prm_stride   np_store doubles of make_deriv_spec(ks).p, then the noise, then n_b as a double
+//   X + b x_stride, y + b y_stride   its points (point-major, d coordinates each) and targets; entries from n_b on are never read
+//   out + b out_stride   logp, then (want_grad) the n_params sums WITHOUT the factors that do not depend on (i, j) -- the host halves
+//                        them and applies cross_grad_finish -- and sum_i M_ii
+//   alpha + b 128        alpha, zero from n_b on;   info + b: 0 or the first non-positive pivot, 1-based (zeroed by the caller)
+// slab: batch_scratch_doubles(models) doubles, L and L^-1 of workgroup g at slab + g 2 128^2.  Kernels: those of with_gradient_kernel.
+constexpr int GPRC_BATCH_LAUNCH = 256;
+struct BatchArgs {
+  const double* X;
+  const double* y;
+  const double* prm;
+  double* slab;
+  double* out;
+  double* alpha;
+  int* info;
+  int64_t x_stride, y_stride, d, b0;
+  int prm_stride, np_store, n_params, out_stride, want_grad;
+};
+size_t batch_scratch_doubles(int64_t models);
+int launch_batch_logp_grad(hipStream_t s, int kernel, const BatchArgs& a, int64_t models);
+
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),
 // k and its derivatives recomputed from the row points A (d x rows) and the column points Z (d x cols); rows >= rows and columns >= cols

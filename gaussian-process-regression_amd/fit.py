@@ -21,6 +21,9 @@ Beside the reference-faithful fit() stands an EXACT path (no reference counterpa
 likelihood and its true gradient in one native call (gprc_gpr_logp_grad: the noisy K_y = K + noise I, a trace, every
 parameter and the noise), and `optimize` maximises it over log(theta) (and log(noise)) with the same vmmin.  It is what
 makes gammaexp / rationalquadratic searches move and what the d length scales of `sqrexp_ard`, `matern32_ard` and `matern52_ard` need.
+Small models come in batches: `logp_grad_batch` is `logp_grad` for B models of at most 128 points in one native call
+(gprc_gpr_batch_logp_grad: one model per workgroup), and `optimize_multistart` runs one `vmmin_steps` -- vmmin as a generator -- per
+start value in lockstep on it, every start exactly as `optimize` would run it.
 Classification has the same pair: `logq_grad` is the Laplace log evidence of GPC and its exact gradient (gprc_gpc_logq_grad: the
 mode search of GPC$new, then one contraction), `optimize_gpc` maximises it over log(theta).
 The sparse GPR has it too: `elbo_grad` is Titsias' collapsed bound and its exact gradient with respect to the kernel parameters, the
@@ -42,7 +45,7 @@ from . import _native as nat
 from .covfunc import (CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
                       matern32_ard, matern52_ard)
 
-__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "loo_grad", "optimize", "logq_grad", "optimize_gpc", "elbo", "elbo_grad", "optimize_sparse",
+__all__ = ["fit", "dens", "dens_deriv", "logp_grad", "logp_grad_batch", "loo_grad", "optimize", "optimize_multistart", "vmmin_steps", "logq_grad", "optimize_gpc", "elbo", "elbo_grad", "optimize_sparse",
            "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
@@ -277,6 +280,144 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
             "convergence": fail, "func": _func_of(name, par)}
 
 
+BATCH_MAX_N = 128   # include/gprc_native.h GPRC_BATCH_MAX_N: the points of one batched model
+
+
+def logp_grad_batch(X, y, noise, name, thetas, ctx=None):
+    """`logp_grad` for B small models in ONE native call (gprc_gpr_batch_logp_grad: a model of at most 128 points per workgroup):
+    (logp[B], grad[B, p + 1], info[B]).  thetas: B x p, a parameter vector per row in the order `dens` takes it (a vector is one
+    model); noise: a scalar or B values; X, y: one data set shared by every model, or lists of B data sets, which may differ in n
+    (they are padded into one strided array; the padding is never read).  grad's last column is d logp / d noise.  A model whose
+    K + noise I is not positive definite does not raise: info[b] > 0 is the leading minor that failed, and its logp and grad are
+    NaN.  More than 128 points: ValueError -- that is what `logp_grad` is for."""
+    func = grad_dict[name]
+    thetas = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))
+    B, p = thetas.shape
+    noises = np.ascontiguousarray(np.broadcast_to(np.asarray(noise, dtype=np.float64), (B,)))
+    shared = not isinstance(X, (list, tuple))
+    if shared:
+        Xm = as_points(X)
+        yb = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+        d, n_max = Xm.shape
+        if yb.size != n_max:
+            raise ValueError("length(y) == ncol(X) is not TRUE")
+        Xb, x_stride, y_stride, n_each = Xm, 0, 0, None
+    else:
+        if len(X) != B or len(y) != B:
+            raise ValueError("logp_grad_batch: one data set per row of thetas")
+        pts = [as_points(x) for x in X]
+        d = pts[0].shape[0]
+        n_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
+        n_max = int(n_each.max())
+        Xb, yb = np.zeros((B, d * n_max)), np.zeros((B, n_max))
+        for b, (q, yy) in enumerate(zip(pts, y)):
+            yy = np.asarray(yy, dtype=np.float64).ravel()
+            if q.shape[0] != d or yy.size != q.shape[1]:
+                raise ValueError("logp_grad_batch: every data set needs the same nrow(X) and length(y) == ncol(X)")
+            Xb[b, :q.size] = q.ravel(order="F")
+            yb[b, :yy.size] = yy
+        x_stride, y_stride = d * n_max, n_max
+    if n_max > BATCH_MAX_N:
+        raise ValueError("logp_grad_batch: at most %d points a model; logp_grad takes larger ones" % BATCH_MAX_N)
+    logp, grad, info = np.empty(B), np.empty((B, p + 1)), np.zeros(B, dtype=np.intc)
+    if B == 0:
+        return logp, grad, info
+    ctx = ctx or nat.default_context()
+    nat.check(nat.lib().gprc_gpr_batch_logp_grad(ctx.handle, func.kernel_id, B, thetas.ctypes.data, p, p, noises.ctypes.data, Xb.ctypes.data, d,
+                                                 n_max, x_stride, yb.ctypes.data, y_stride, None if n_each is None else n_each.ctypes.data,
+                                                 logp.ctypes.data, grad.ctypes.data, None, info.ctypes.data))
+    return logp, grad, info
+
+
+def optimize_multistart(X, y, noise, name, starts=None, *, n_starts=8, rng=None, optimize_noise=True, maxit=100, value_and_grad_batch=None,
+                        ctx=None):
+    """`optimize` from several start values at about the wall time of one: one `vmmin_steps` instance per start on z = log(theta) (and
+    log(noise), as `optimize`), in lockstep.  Every round collects the points the live instances wait on and evaluates them in ONE
+    `logp_grad_batch` call (at most 128 points: the batched objective's limit); value and gradient come together and are kept per
+    instance, so the gradient vmmin asks for at the point it has just accepted costs nothing; an instance that has finished drops out
+    of the batch.  A model that is not positive definite (info > 0) or whose exp(z) over- or underflows is the sentinel -10000 for
+    that instance only; at an instance's FIRST point it raises (NotPositiveDefinite / ArithmeticError), as `optimize` does there.
+    starts: S x p start values; default: `optimize`'s default start, then n_starts - 1 copies of it multiplied entry by entry by
+    log-uniform factors in [1/8, 8] from rng.  value_and_grad_batch(thetas, noises) -> (values, grads, infos) replaces the native
+    objective (thetas m x p, noises m; grads m x (p + 1), noise last).  Each instance runs exactly what `optimize` runs from its
+    start.  Returns `optimize`'s dict of the best start (the first maximum) with "all", the dict of every start in order, and
+    "best_index"."""
+    func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient, as `optimize`)
+    shared = not isinstance(X, (list, tuple))
+    d = as_points(X).shape[0] if shared else as_points(X[0]).shape[0]
+    if starts is None:
+        base = np.atleast_1d(np.asarray(_default_start(name, d), dtype=np.float64)).ravel()
+        rng = rng if rng is not None else np.random.default_rng()
+        extra = np.exp(rng.uniform(math.log(1.0 / 8.0), math.log(8.0), (max(int(n_starts) - 1, 0), base.size)))
+        starts = np.vstack([base[None, :], base[None, :] * extra])
+    starts = np.atleast_2d(np.asarray(starts, dtype=np.float64))
+    S, npar = starts.shape
+    if S < 1 or not (np.all(np.isfinite(starts)) and np.all(starts > 0)):
+        raise ValueError("optimize_multistart: start values must be finite and > 0")
+    with_noise = bool(optimize_noise) and noise > 0
+    if value_and_grad_batch is None:
+        ctx = ctx or nat.default_context()
+        value_and_grad_batch = lambda thetas, noises: logp_grad_batch(X, y, noises, name, thetas, ctx)   # noqa: E731
+
+    class _Instance:   # one vmmin with _maximise_over_log's cache: the last evaluated point, its value and chained gradient
+        def __init__(self, theta0):
+            self.steps = vmmin_steps(np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0), maxit)
+            self.key = self.val = self.grad = self.result = None
+            self.first = True
+            self.want = next(self.steps)
+
+        def advance(self, answer):
+            try:
+                self.want = self.steps.send(answer)
+            except StopIteration as stop:
+                self.want, self.result = None, stop.value
+
+        def run_on_cache(self):
+            """answers from the cache until the instance finishes or waits on a point that has to be evaluated"""
+            while self.want is not None and self.want[1].tobytes() == self.key:
+                self.advance(-self.val if self.want[0] == "f" else -self.grad)
+
+    inst = [_Instance(starts[s]) for s in range(S)]
+    while True:
+        for it in inst:
+            it.run_on_cache()
+        live = [it for it in inst if it.want is not None]
+        if not live:
+            break
+        with np.errstate(over="ignore"):
+            T = np.array([np.exp(it.want[1]) for it in live])
+        in_range = np.all(np.isfinite(T), axis=1) & np.all(T > 0, axis=1)
+        rows = np.flatnonzero(in_range)
+        vals = grads = infos = None
+        if rows.size:
+            vals, grads, infos = value_and_grad_batch(T[rows, :npar].copy(), T[rows, npar].copy() if with_noise else np.full(rows.size, float(noise)))
+            grads = np.asarray(grads, dtype=np.float64)
+        where = {int(r): k for k, r in enumerate(rows)}
+        for i, it in enumerate(live):
+            k = where.get(i)
+            failed = k is None or int(infos[k]) > 0
+            if failed:
+                if it.first or it.want[0] == "g":   # vmmin has no gradient to go on: what `optimize` raises from its gradient call
+                    raise (ArithmeticError("parameter out of range") if k is None else nat.NotPositiveDefinite(int(infos[k])))
+                it.first = False
+                it.advance(-SENTINEL)
+                continue
+            g = grads[k] if with_noise else grads[k][:npar]
+            it.key, it.val, it.grad = it.want[1].tobytes(), float(vals[k]), g * T[i]
+            it.first = False
+            it.advance(-it.val if it.want[0] == "f" else -it.grad)
+
+    results = []
+    for it in inst:
+        z, fmin, fncount, grcount, fail = it.result
+        t = np.exp(z)
+        par = tuple(float(v) for v in t[:npar])
+        results.append({"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
+                        "convergence": fail, "func": _func_of(name, par)})
+    best = int(np.argmax([r["value"] for r in results]))
+    return dict(results[best], all=results, best_index=best)
+
+
 def optimize_sparse(X, y, noise, name, Z, start=None, *, optimize_noise=True, optimize_Z=True, jitter=1e-6, maxit=100, value_and_grad=None,
                     ctx=None):
     """Maximise the collapsed bound of the sparse GPR (sparse.SparseGPR) of kernel `name` (a key of grad_dict) over its parameters, over the
@@ -434,20 +575,35 @@ def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_
 def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):
     """R's optim(method = "BFGS") core: Nash's variable-metric minimiser (Compact Numerical Methods, Algorithm 21)
     with R's constants (stepredn 0.2, acctol 1e-4, reltest 10).  Minimises fn; returns (par, value, fncount, grcount,
-    fail).  Restated from the published algorithm; control flow details that matter for the reference's behaviour:
-    a non-finite initial value is an error; a search direction that is not downhill (including a NaN gradient
-    projection) resets B once and then terminates."""
+    fail).  The algorithm is `vmmin_steps`; this is its driver for one instance: every value it asks for is fn's, every
+    gradient gr's."""
+    steps = vmmin_steps(b0, maxit, abstol, reltol)
+    try:
+        kind, point = next(steps)
+        while True:
+            kind, point = steps.send(fn(point) if kind == "f" else gr(point))
+    except StopIteration as stop:
+        return stop.value
+
+
+def vmmin_steps(b0, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):
+    """`vmmin` as a generator, so that several instances can run in lockstep on one batched objective (`optimize_multistart`): it
+    yields ("f", point) when it wants the value at `point` and ("g", point) when it wants the gradient there, is sent the answer, and
+    returns vmmin's tuple (par, value, fncount, grcount, fail) as the value of its StopIteration.  `point` is the instance's own
+    working vector: it is valid until the answer is sent.  Restated from the published algorithm; control flow details that matter
+    for the reference's behaviour: a non-finite initial value is an error (ArithmeticError, raised into whoever drives the
+    generator); a search direction that is not downhill (including a NaN gradient projection) resets B once and then terminates."""
     stepredn, acctol, reltest = 0.2, 1e-4, 10.0
     b = np.array(b0, dtype=np.float64)
     n = b.size
     if maxit <= 0:
-        return b, float(fn(b)), 0, 0, 0
-    f = float(fn(b))
+        return b, float((yield ("f", b))), 0, 0, 0
+    f = float((yield ("f", b)))
     if not math.isfinite(f):
         raise ArithmeticError("initial value in 'vmmin' is not finite")
     fmin = f
     funcount = gradcount = 1
-    g = np.array(gr(b), dtype=np.float64)
+    g = np.array((yield ("g", b)), dtype=np.float64)
     it = 1
     ilast = gradcount
     B = np.zeros((n, n))
@@ -477,7 +633,7 @@ def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(flo
                     if reltest + X[i] == reltest + b[i]:
                         count += 1
                 if count < n:
-                    f = float(fn(b))
+                    f = float((yield ("f", b)))
                     funcount += 1
                     accpoint = math.isfinite(f) and f <= fmin + gradproj * steplength * acctol
                     if not accpoint:
@@ -490,7 +646,7 @@ def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(flo
                 fmin = f
             if count < n:  # making progress
                 fmin = f
-                g = np.array(gr(b), dtype=np.float64)
+                g = np.array((yield ("g", b)), dtype=np.float64)
                 gradcount += 1
                 it += 1
                 D1 = 0.0

@@ -163,6 +163,30 @@ GPRC_API int gprc_fit_gradient(gprc_ctx* ctx, int kernel, const double* params, 
  * Other kernel ids: GPRC_ERR_ARG. */
 GPRC_API int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,
                                 int64_t n, const double* y, double noise, double* logp_out, double* grad_out);
+/* gprc_gpr_logp_grad for B small models in one call ("Small models in batches"): one model of at most
+ * GPRC_BATCH_MAX_N points per workgroup -- fill, factorisation, alpha, logp and the gradient's contraction without leaving the CU -- so a
+ * multi-start search, many outputs over the same inputs or many local models cost one launch per 256 models, not a few per model.
+ *   params   HOST: model b's n_params parameters (the ABI's order) at params + b * ld_params, ld_params >= n_params
+ *   noise    HOST: B values, each finite and >= 0
+ *   X        host or device: model b's points (d x n_max, one point per column, as everywhere) at X + b * x_stride; x_stride = 0: every
+ *            model shares one data set; otherwise x_stride >= d * n_max
+ *   y        likewise: n_max values at y + b * y_stride; y_stride = 0 (shared) or >= n_max
+ *   n_each   HOST, may be NULL (every model has n_max points): 1 <= n_each[b] <= n_max; what lies behind a model's n_each[b] points in
+ *            its part of X and y is never read
+ *   logp_out HOST, B;   grad_out HOST, B x (n_params + 1), d / d noise last, or NULL (values only);   alpha_out HOST, B x n_max, zero
+ *            beyond n_each[b], or NULL;   info_out HOST, B: 0 or the leading minor that is not positive definite
+ * A model that is not positive definite does not fail the call: the call returns GPRC_OK, info_out[b] > 0 and that model's logp, gradient
+ * and alpha are NaN; no jitter is added.  A model's outputs are the same bits alone (B = 1) and anywhere in any batch, with shared and
+ * with strided data, from host and from device pointers, with and without grad_out / alpha_out.  Against gprc_gpr_logp_grad they
+ * agree to rounding, not to the bit (another order of multiplications in the kernel value).  Kernels: those of gprc_gpr_logp_grad, any
+ * other id is GPRC_ERR_ARG; so are n_max > GPRC_BATCH_MAX_N (use the single-model entry points), an n_each outside 1 .. n_max, a noise
+ * that is negative or not finite, a stride that is neither 0 nor at least one model's extent, null params, noise, X, y, logp_out or
+ * info_out.  B = 0 returns GPRC_OK.  MEMORY: 2 * 128^2 doubles per model of a launch, at most 64 MiB, from the context's pool. */
+#define GPRC_BATCH_MAX_N 128
+GPRC_API int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params,
+                                      const double* noise, const double* X, int64_t d, int64_t n_max, int64_t x_stride, const double* y,
+                                      int64_t y_stride, const int64_t* n_each, double* logp_out, double* grad_out, double* alpha_out,
+                                      int* info_out);
 /* Leave-one-out cross-validation of a fitted GPR model in closed form (Rasmussen & Williams 5.4.2; no reference counterpart).  With
  * K_y = K + noise * I, P = K_y^-1, alpha = P y and p_i = P_ii, the prediction of y_i from the other n - 1 observations is
  *   mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i,     logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log(2 pi),
