@@ -1,0 +1,105 @@
+"""A fitted batch of small GPs (include/gprc_native.h gprc_gpr_batch_fit / gprc_gpr_batch_predict; DESIGN.md section 7, "Batched
+predict"): B models of at most 128 points each fitted in one native call and kept on the device, and the posterior mean and
+variance of all of them at their test points in one more.  The input conventions are `fit.logp_grad_batch`'s.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import importlib
+
+import numpy as np
+
+from . import _native as nat
+from .covfunc import as_points
+
+_fit = importlib.import_module(__package__ + ".fit")   # (the package's attribute `fit` is the function)
+
+
+class BatchGPR:
+    """B small GPR models, one per row of `thetas` (B x p, the order `dens` takes them; a vector is one model), fitted together.
+    X, y: one data set shared by every model (d x n, n values), or lists of B data sets, which may differ in n (they are padded into
+    one strided array; the padding is never read); noise: a scalar or B values; name: a kernel of `fit.grad_dict`.  At most 128
+    points a model (ValueError beyond: `GPR` takes larger ones).
+
+    .logp[B], .info[B]: the log evidence and 0, or the leading minor that is not positive definite -- such a model does not raise,
+    its logp, alpha and predictions are NaN; both are bit for bit `logp_grad_batch`'s.  .alpha[B, n_max] (read from the device when
+    asked for, zero behind a model's points).  The object holds 128 KiB of device memory a model until .close() (or its collection)."""
+
+    def __init__(self, X, y, noise, name, thetas, ctx=None):
+        func = _fit.grad_dict[name]
+        thetas = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))
+        B, p = thetas.shape
+        if B < 1:
+            raise ValueError("BatchGPR: at least one model")
+        noises = np.ascontiguousarray(np.broadcast_to(np.asarray(noise, dtype=np.float64), (B,)))
+        Xb, yb, d, n_max, x_stride, y_stride, n_each = _fit.batch_layout(X, y, B, "BatchGPR")
+        self.name, self.thetas, self.noise = name, thetas, noises
+        self.B, self.d, self.n_max = B, d, n_max
+        self.n_each = np.full(B, n_max, dtype=np.int64) if n_each is None else n_each
+        self.logp, self.info = np.empty(B), np.zeros(B, dtype=np.intc)
+        self._ctx = ctx or nat.default_context()
+        self._model = C.c_void_p()
+        nat.check(nat.lib().gprc_gpr_batch_fit(self._ctx.handle, func.kernel_id, B, thetas.ctypes.data, p, p, noises.ctypes.data, Xb.ctypes.data, d,
+                                               n_max, x_stride, yb.ctypes.data, y_stride, None if n_each is None else n_each.ctypes.data,
+                                               C.byref(self._model), self.logp.ctypes.data, self.info.ctypes.data))
+
+    @property
+    def handle(self):
+        if not self._model:
+            raise nat.GprcError(nat.ERR_ARG, "the batch has been closed")
+        return self._model
+
+    @property
+    def alpha(self):
+        out = np.empty((self.B, self.n_max))
+        nat.check(nat.lib().gprc_gpr_batch_get_alpha(self.handle, out.ctypes.data))
+        return out
+
+    def predict(self, X_star, var=True):
+        """Posterior mean and latent variance k(x*, x*) - |L^-1 k*|^2 of every model.  X_star: a d x n* array of test points shared by
+        every model -> (mean[B, n*], var[B, n*]); or a list of B arrays (d x n*_b, which may differ in n*_b) -> (list of B means,
+        list of B variances).  var=False: the variance is not computed and None stands in its place."""
+        B, d = self.B, self.d
+        shared = not isinstance(X_star, (list, tuple))
+        if shared:
+            Xs = as_points(X_star, d, "X_star")
+            if Xs.shape[0] != d or Xs.shape[1] < 1:
+                raise ValueError("BatchGPR.predict: X_star must be d x n* with n* >= 1")
+            ns_max, xs_stride, ns_each = Xs.shape[1], 0, None
+            Xsb = np.ascontiguousarray(Xs.ravel(order="F"))
+        else:
+            if len(X_star) != B:
+                raise ValueError("BatchGPR.predict: one set of test points per model")
+            pts = [as_points(x, d, "X_star") for x in X_star]
+            if any(q.shape[0] != d or q.shape[1] < 1 for q in pts):
+                raise ValueError("BatchGPR.predict: every set of test points must be d x n* with n* >= 1")
+            ns_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
+            ns_max = int(ns_each.max())
+            xs_stride = d * ns_max
+            Xsb = np.zeros((B, xs_stride))
+            for b, q in enumerate(pts):
+                Xsb[b, :q.size] = q.ravel(order="F")
+        mean = np.full((B, ns_max), np.nan)
+        v = np.full((B, ns_max), np.nan) if var else None
+        nat.check(nat.lib().gprc_gpr_batch_predict(self.handle, Xsb.ctypes.data, ns_max, xs_stride, None if ns_each is None else ns_each.ctypes.data,
+                                                   mean.ctypes.data, None if v is None else v.ctypes.data, ns_max))
+        if shared:
+            return mean, v
+        return [mean[b, :n] for b, n in enumerate(ns_each)], (None if v is None else [v[b, :n] for b, n in enumerate(ns_each)])
+
+    def close(self):
+        if getattr(self, "_model", None):
+            nat.lib().gprc_batch_model_free(self._model)
+            self._model = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

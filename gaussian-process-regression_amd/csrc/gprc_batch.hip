@@ -1,8 +1,11 @@
-// gprc_batch.hip -- small GPs in batches ("Small models in batches"): the host side of gprc_gpr_batch_logp_grad.
+// gprc_batch.hip -- small GPs in batches ("Small models in batches" and "Batched predict"): the host side of
+// gprc_gpr_batch_logp_grad, gprc_gpr_batch_fit and gprc_gpr_batch_predict.
 // The argument checks, one record of derived constants per model (make_deriv_spec, once per model), the staging of host arrays, the
 // launches of kernels_batch.hip -- at most GPRC_BATCH_LAUNCH models each, on one set of scratch slabs from the context's pool -- and the
 // tail every exact gradient has: the sums that the device leaves get 1/2 and the factors of cross_grad_finish, a model that is not
 // positive definite gets NaN.  A model's record, its launch and its tail do not look at any other model: its bits do not depend on the batch.
+// The two fitting entry points share every step up to the launches (batch_checks, batch_records, batch_launches): the fitted batch differs
+// only in where the buffers live -- the gprc_batch_model owns them -- and in where the kernel puts W = L^-1 (BatchArgs::w).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -15,9 +18,113 @@ using namespace gprc;
 
 static_assert(GPRC_BATCH_MAX_N == NBI, "a batched model is one LDS-resident diagonal block");
 
+// A fitted batch: what gprc_gpr_batch_predict reads again, all in device memory from the context's pool.
+struct gprc_batch_model {
+  gprc_ctx* ctx = nullptr;
+  uint64_t ctx_id = 0;
+  int kernel = 0, n_params = 0, np_store = 0, prm_stride = 0;
+  int64_t B = 0, d = 0, n_max = 0, x_stride = 0;
+  DevMem X;       // the points: d * n_max doubles (shared) or B strides of the caller's x_stride
+  DevMem alpha;   // B x 128, zero from n_b on
+  DevMem W;       // B x 128^2: L^-1 of every model (BatchArgs::w)
+  DevMem prm;     // B records: the derived constants, the noise, n_b
+  DevMem info;    // B ints
+};
+
 namespace {
 
-int bad(const std::string& msg) { set_error("batch_logp_grad: " + msg); return GPRC_ERR_ARG; }
+int bad(const char* who, const std::string& msg) { set_error(std::string(who) + ": " + msg); return GPRC_ERR_ARG; }
+
+// the checks both fitting entry points make, in one order; *empty: B = 0, nothing to do
+int batch_checks(const char* who, gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params, const double* noise,
+                 const double* X, int64_t d, int64_t n_max, int64_t x_stride, const double* y, int64_t y_stride, const int64_t* n_each,
+                 const void* out0, const double* logp_out, const int* info_out, const char* outputs, bool* empty) {
+  *empty = false;
+  if (!ctx) return bad(who, "null context");
+  GPRC_TRY(check_grad_kernel(who, kernel));
+  if (B < 0) return bad(who, "B < 0");
+  if (B == 0) { *empty = true; return 0; }
+  if (n_max > GPRC_BATCH_MAX_N)
+    return bad(who, "n_max = " + std::to_string(n_max) + " > " + std::to_string(GPRC_BATCH_MAX_N) +
+                        ": a batched model is at most 128 points, use the single-model entry points (gprc_gpr_logp_grad) for larger ones");
+  if (n_max < 1 || d < 1) return bad(who, "n_max < 1 or d < 1");
+  if (!params || !noise || !X || !y) return bad(who, "null input pointer (params, noise, X, y)");
+  if (!out0 || !logp_out || !info_out) return bad(who, std::string("null output pointer (") + outputs + ")");
+  if (n_params < 1 || ld_params < n_params) return bad(who, "n_params < 1 or ld_params < n_params");
+  if (x_stride != 0 && x_stride < d * n_max) return bad(who, "x_stride must be 0 (shared) or >= d * n_max");
+  if (y_stride != 0 && y_stride < n_max) return bad(who, "y_stride must be 0 (shared) or >= n_max");
+  for (int64_t b = 0; b < B; ++b) {
+    if (!(noise[b] >= 0.0) || !std::isfinite(noise[b])) return bad(who, "noise of model " + std::to_string(b) + " must be finite and >= 0");
+    if (n_each && (n_each[b] < 1 || n_each[b] > n_max)) return bad(who, "n_each of model " + std::to_string(b) + " is outside 1 .. n_max");
+  }
+  return 0;
+}
+
+// one record per model: the derived constants, the noise, n_b
+struct BatchRecords {
+  int np_store = 0, prm_stride = 0, out_stride = 0;
+  std::vector<double> hprm;
+  std::vector<KernelSpec> specs;   // the callers' specs, kept for the gradient's tail
+};
+
+int batch_records(int kernel, int64_t B, const double* params, int n_params, int64_t ld_params, const double* noise, int64_t d, int64_t n_max,
+                  const int64_t* n_each, bool keep_specs, BatchRecords* r) {
+  r->np_store = std::max(n_params, 4);   // gammaexp's derived constants are p[2], p[3]
+  r->prm_stride = r->np_store + 2;
+  r->out_stride = n_params + 2;
+  r->hprm.resize((size_t)(B * r->prm_stride));
+  if (keep_specs) r->specs.resize((size_t)B);
+  KernelSpec ks;
+  for (int64_t b = 0; b < B; ++b) {
+    GPRC_TRY(make_spec(kernel, params + b * ld_params, n_params, d, &ks));
+    if (keep_specs) r->specs[(size_t)b] = ks;
+    const KernelSpec g = make_deriv_spec(ks);
+    double* rec = r->hprm.data() + b * r->prm_stride;
+    for (int k = 0; k < r->np_store; ++k) rec[k] = g.p[k];
+    rec[r->np_store] = noise[b];
+    rec[r->np_store + 1] = (double)(n_each ? n_each[b] : n_max);
+  }
+  return 0;
+}
+
+// the records to the device, the info words zeroed, then the launches: at most GPRC_BATCH_LAUNCH models each on one set of slabs.
+// prm, out, alpha, info: allocated here (the caller owns them); w: null, or the fitted batch's store of B x 128^2 doubles
+int batch_launches(const char* who, hipStream_t s, int kernel, int64_t B, const BatchRecords& r, int n_params, const double* xdev, int64_t x_stride,
+                   const double* ydev, int64_t y_stride, int64_t d, bool want_grad, double* w, DevMem& prm, DevMem& out, DevMem& alpha, DevMem& info) {
+  const int64_t launch = std::min<int64_t>(B, GPRC_BATCH_LAUNCH);
+  DevMem slab;
+  GPRC_TRY(prm.alloc(B * r.prm_stride));
+  GPRC_TRY(out.alloc(B * r.out_stride));
+  GPRC_TRY(alpha.alloc(B * NBI));
+  GPRC_TRY(info.alloc((B + 1) / 2));
+  const size_t slab_doubles = batch_scratch_doubles(launch, w != nullptr);
+  if (int rc = slab.alloc((int64_t)slab_doubles)) {
+    if (rc == GPRC_ERR_NOMEM)
+      set_error(std::string(who) + ": the factors of one launch, " + std::to_string((slab_doubles * sizeof(double)) >> 20) +
+                " MiB of device memory, could not be allocated");
+    return rc;
+  }
+  GPRC_HIP(hipMemcpyAsync(prm.p, r.hprm.data(), sizeof(double) * r.hprm.size(), hipMemcpyHostToDevice, s));
+  GPRC_HIP(hipMemsetAsync(info.p, 0, sizeof(int) * (size_t)B, s));
+  BatchArgs a{xdev, ydev, prm.p, slab.p, out.p, alpha.p, reinterpret_cast<int*>(info.p), x_stride, y_stride, d, 0,
+              r.prm_stride, r.np_store, n_params, r.out_stride, want_grad ? 1 : 0};
+  a.w = w;
+  a.w_stride = (int64_t)NBI * NBI;
+  for (int64_t b0 = 0; b0 < B; b0 += launch) {
+    a.b0 = b0;
+    GPRC_TRY(launch_batch_logp_grad(s, kernel, a, std::min<int64_t>(launch, B - b0)));
+  }
+  return 0;
+}
+
+void free_batch_model(gprc_batch_model* m) {
+  if (!m) return;
+  if (m->ctx) (void)hipSetDevice(m->ctx->device);
+  else                                   // the context went first: the buffers go straight back to the driver
+    for (DevMem* q : {&m->X, &m->alpha, &m->W, &m->prm, &m->info}) q->owner = nullptr;
+  delete m;
+}
+struct BatchModelFree { void operator()(gprc_batch_model* m) const { free_batch_model(m); } };
 
 }  // namespace
 
@@ -26,66 +133,22 @@ extern "C" {
 int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params, const double* noise,
                              const double* X, int64_t d, int64_t n_max, int64_t x_stride, const double* y, int64_t y_stride, const int64_t* n_each,
                              double* logp_out, double* grad_out, double* alpha_out, int* info_out) {
-  if (!ctx) return bad("null context");
-  GPRC_TRY(check_grad_kernel("batch_logp_grad", kernel));
-  if (B < 0) return bad("B < 0");
-  if (B == 0) return 0;
-  if (n_max > GPRC_BATCH_MAX_N)
-    return bad("n_max = " + std::to_string(n_max) + " > " + std::to_string(GPRC_BATCH_MAX_N) +
-               ": a batched model is at most 128 points, use the single-model entry points (gprc_gpr_logp_grad) for larger ones");
-  if (n_max < 1 || d < 1) return bad("n_max < 1 or d < 1");
-  if (!params || !noise || !X || !y) return bad("null input pointer (params, noise, X, y)");
-  if (!logp_out || !info_out) return bad("null output pointer (logp_out, info_out)");
-  if (n_params < 1 || ld_params < n_params) return bad("n_params < 1 or ld_params < n_params");
-  if (x_stride != 0 && x_stride < d * n_max) return bad("x_stride must be 0 (shared) or >= d * n_max");
-  if (y_stride != 0 && y_stride < n_max) return bad("y_stride must be 0 (shared) or >= n_max");
-  for (int64_t b = 0; b < B; ++b) {
-    if (!(noise[b] >= 0.0) || !std::isfinite(noise[b])) return bad("noise of model " + std::to_string(b) + " must be finite and >= 0");
-    if (n_each && (n_each[b] < 1 || n_each[b] > n_max)) return bad("n_each of model " + std::to_string(b) + " is outside 1 .. n_max");
-  }
-  // one record per model: the derived constants, the noise, n_b
-  const int np_store = std::max(n_params, 4);   // gammaexp's derived constants are p[2], p[3]
-  const int prm_stride = np_store + 2, out_stride = n_params + 2;
-  std::vector<double> hprm((size_t)(B * prm_stride));
-  std::vector<KernelSpec> specs;
-  if (grad_out) specs.resize((size_t)B);
-  {
-    KernelSpec ks;
-    for (int64_t b = 0; b < B; ++b) {
-      GPRC_TRY(make_spec(kernel, params + b * ld_params, n_params, d, &ks));
-      if (grad_out) specs[(size_t)b] = ks;
-      const KernelSpec g = make_deriv_spec(ks);
-      double* r = hprm.data() + b * prm_stride;
-      for (int k = 0; k < np_store; ++k) r[k] = g.p[k];
-      r[np_store] = noise[b];
-      r[np_store + 1] = (double)(n_each ? n_each[b] : n_max);
-    }
-  }
+  const char* who = "batch_logp_grad";
+  bool empty = false;
+  GPRC_TRY(batch_checks(who, ctx, kernel, B, params, n_params, ld_params, noise, X, d, n_max, x_stride, y, y_stride, n_each, logp_out, logp_out,
+                        info_out, "logp_out, info_out", &empty));
+  if (empty) return 0;
+  BatchRecords r;
+  GPRC_TRY(batch_records(kernel, B, params, n_params, ld_params, noise, d, n_max, n_each, grad_out != nullptr, &r));
+  const std::vector<KernelSpec>& specs = r.specs;
+  const int out_stride = r.out_stride;
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
   In xin, yin;
   GPRC_TRY(xin.set(s, X, (x_stride ? (B - 1) * x_stride : 0) + d * n_max));
   GPRC_TRY(yin.set(s, y, (y_stride ? (B - 1) * y_stride : 0) + n_max));
-  const int64_t launch = std::min<int64_t>(B, GPRC_BATCH_LAUNCH);
-  DevMem prm, out, alpha, info, slab;
-  GPRC_TRY(prm.alloc(B * prm_stride));
-  GPRC_TRY(out.alloc(B * out_stride));
-  GPRC_TRY(alpha.alloc(B * NBI));
-  GPRC_TRY(info.alloc((B + 1) / 2));
-  if (int rc = slab.alloc((int64_t)batch_scratch_doubles(launch))) {
-    if (rc == GPRC_ERR_NOMEM)
-      set_error("batch_logp_grad: the factors of one launch, " + std::to_string((batch_scratch_doubles(launch) * sizeof(double)) >> 20) +
-                " MiB of device memory, could not be allocated");
-    return rc;
-  }
-  GPRC_HIP(hipMemcpyAsync(prm.p, hprm.data(), sizeof(double) * hprm.size(), hipMemcpyHostToDevice, s));
-  GPRC_HIP(hipMemsetAsync(info.p, 0, sizeof(int) * (size_t)B, s));
-  BatchArgs a{xin.dev, yin.dev, prm.p, slab.p, out.p, alpha.p, reinterpret_cast<int*>(info.p), x_stride, y_stride, d, 0,
-              prm_stride, np_store, n_params, out_stride, grad_out ? 1 : 0};
-  for (int64_t b0 = 0; b0 < B; b0 += launch) {
-    a.b0 = b0;
-    GPRC_TRY(launch_batch_logp_grad(s, kernel, a, std::min<int64_t>(launch, B - b0)));
-  }
+  DevMem prm, out, alpha, info;
+  GPRC_TRY(batch_launches(who, s, kernel, B, r, n_params, xin.dev, x_stride, yin.dev, y_stride, d, grad_out != nullptr, nullptr, prm, out, alpha, info));
   std::vector<double> hout((size_t)(B * out_stride)), halpha(alpha_out ? (size_t)(B * NBI) : 0);
   GPRC_HIP(hipMemcpyAsync(hout.data(), out.p, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, s));
   GPRC_HIP(hipMemcpyAsync(info_out, info.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s));
@@ -94,15 +157,15 @@ int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, const double*
   const double qnan = std::numeric_limits<double>::quiet_NaN();
   std::vector<long double> acc((size_t)n_params);
   for (int64_t b = 0; b < B; ++b) {
-    const double* r = hout.data() + b * out_stride;
+    const double* rr = hout.data() + b * out_stride;
     const bool ok = info_out[b] == 0;
-    logp_out[b] = ok ? r[0] : qnan;
+    logp_out[b] = ok ? rr[0] : qnan;
     if (grad_out) {
       double* g = grad_out + b * (n_params + 1);
       if (ok) {
-        for (int k = 0; k < n_params; ++k) acc[(size_t)k] = 0.5L * (long double)r[1 + k];
+        for (int k = 0; k < n_params; ++k) acc[(size_t)k] = 0.5L * (long double)rr[1 + k];
         cross_grad_finish(specs[(size_t)b], acc.data(), g);
-        g[n_params] = (double)(0.5L * (long double)r[1 + n_params]);
+        g[n_params] = (double)(0.5L * (long double)rr[1 + n_params]);
       } else {
         for (int k = 0; k <= n_params; ++k) g[k] = qnan;
       }
@@ -112,6 +175,152 @@ int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, const double*
       for (int64_t i = 0; i < n_max; ++i) alpha_out[b * n_max + i] = ok ? halpha[(size_t)(b * NBI + i)] : (i < nb ? qnan : 0.0);
     }
   }
+  return 0;
+}
+
+int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params, const double* noise,
+                       const double* X, int64_t d, int64_t n_max, int64_t x_stride, const double* y, int64_t y_stride, const int64_t* n_each,
+                       gprc_batch_model** model_out, double* logp_out, int* info_out) {
+  const char* who = "batch_fit";
+  if (model_out) *model_out = nullptr;
+  bool empty = false;
+  GPRC_TRY(batch_checks(who, ctx, kernel, B, params, n_params, ld_params, noise, X, d, n_max, x_stride, y, y_stride, n_each, model_out, logp_out,
+                        info_out, "model_out, logp_out, info_out", &empty));
+  if (empty) return 0;   // no models: no object (*model_out stays NULL, which gprc_batch_model_free accepts)
+  BatchRecords r;
+  GPRC_TRY(batch_records(kernel, B, params, n_params, ld_params, noise, d, n_max, n_each, false, &r));
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  std::unique_ptr<gprc_batch_model, BatchModelFree> m(new gprc_batch_model);
+  m->ctx = ctx;
+  m->ctx_id = ctx->id;
+  m->kernel = kernel;
+  m->n_params = n_params;
+  m->np_store = r.np_store;
+  m->prm_stride = r.prm_stride;
+  m->B = B;
+  m->d = d;
+  m->n_max = n_max;
+  m->x_stride = x_stride;
+  // the model's own copy of the points: the kernel reads it now and gprc_gpr_batch_predict reads it again
+  const int64_t x_count = (x_stride ? (B - 1) * x_stride : 0) + d * n_max;
+  GPRC_TRY(m->X.alloc(x_count));
+  GPRC_HIP(hipMemcpyAsync(m->X.p, X, sizeof(double) * (size_t)x_count, is_device_ptr(X) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  In yin;
+  GPRC_TRY(yin.set(s, y, (y_stride ? (B - 1) * y_stride : 0) + n_max));
+  if (int rc = m->W.alloc(B * (int64_t)NBI * NBI)) {
+    if (rc == GPRC_ERR_NOMEM)
+      set_error(std::string(who) + ": L^-1 of every model, " + std::to_string((B * (int64_t)NBI * NBI * 8) >> 20) + " MiB of device memory, could not be allocated");
+    return rc;
+  }
+  DevMem out;
+  GPRC_TRY(batch_launches(who, s, kernel, B, r, n_params, m->X.p, x_stride, yin.dev, y_stride, d, false, m->W.p, m->prm, out, m->alpha, m->info));
+  std::vector<double> hout((size_t)(B * r.out_stride));
+  GPRC_HIP(hipMemcpyAsync(hout.data(), out.p, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipMemcpyAsync(info_out, m->info.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t b = 0; b < B; ++b) logp_out[b] = info_out[b] == 0 ? hout[(size_t)(b * r.out_stride)] : qnan;
+  *model_out = m.release();
+  return 0;
+}
+
+int gprc_gpr_batch_get_alpha(gprc_batch_model* m, double* alpha_out) {
+  const char* who = "batch_get_alpha";
+  if (!m) return bad(who, "null model");
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  if (!alpha_out) return bad(who, "null output pointer (alpha_out)");
+  GPRC_TRY(use_device(m->ctx));
+  hipStream_t s = m->ctx->stream;
+  std::vector<double> halpha((size_t)(m->B * NBI)), hprm((size_t)(m->B * m->prm_stride));
+  std::vector<int> hinfo((size_t)m->B);
+  GPRC_HIP(hipMemcpyAsync(halpha.data(), m->alpha.p, sizeof(double) * halpha.size(), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipMemcpyAsync(hprm.data(), m->prm.p, sizeof(double) * hprm.size(), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipMemcpyAsync(hinfo.data(), m->info.p, sizeof(int) * hinfo.size(), hipMemcpyDeviceToHost, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t b = 0; b < m->B; ++b) {   // as gprc_gpr_batch_logp_grad's alpha_out: NaN for a flagged model's points, zero behind n_b
+    const int64_t nb = (int64_t)hprm[(size_t)(b * m->prm_stride + m->np_store + 1)];
+    for (int64_t i = 0; i < m->n_max; ++i)
+      alpha_out[b * m->n_max + i] = hinfo[(size_t)b] == 0 ? halpha[(size_t)(b * NBI + i)] : (i < nb ? qnan : 0.0);
+  }
+  return 0;
+}
+
+int gprc_gpr_batch_predict(gprc_batch_model* m, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each, double* mean_out,
+                           double* var_out, int64_t ld_out) {
+  const char* who = "batch_predict";
+  if (!m) return bad(who, "null model");
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  if (!X_star) return bad(who, "null input pointer (X_star)");
+  if (!mean_out && !var_out) return bad(who, "null output pointers (mean_out and var_out: one of them may be NULL, not both)");
+  if (ns_max < 1) return bad(who, "ns_max < 1");
+  if (xs_stride != 0 && xs_stride < m->d * ns_max) return bad(who, "xs_stride must be 0 (shared) or >= d * ns_max");
+  if (ld_out < ns_max) return bad(who, "ld_out < ns_max");
+  const int64_t B = m->B;
+  if (ns_each)
+    for (int64_t b = 0; b < B; ++b)
+      if (ns_each[b] < 1 || ns_each[b] > ns_max) return bad(who, "ns_each of model " + std::to_string(b) + " is outside 1 .. ns_max");
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  In xs;
+  GPRC_TRY(xs.set(s, X_star, (xs_stride ? (B - 1) * xs_stride : 0) + m->d * ns_max));
+  DevMem counts;
+  if (ns_each) {
+    static_assert(sizeof(int64_t) == sizeof(double), "the counts travel in a block of doubles");
+    GPRC_TRY(counts.alloc(B));
+    GPRC_HIP(hipMemcpyAsync(counts.p, ns_each, sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice, s));
+  }
+  // A host output goes through a temporary of the same pitch.  Where the launch does not write every entry of it -- counts, or a pitch
+  // beyond ns_max -- the temporary starts as the caller's array: what lies behind a model's count comes back as it was.
+  const int64_t out_count = (B - 1) * ld_out + ns_max;
+  const bool gaps = ns_each != nullptr || (ld_out > ns_max && B > 1);
+  Out mean, var;
+  auto stage = [&](Out& o, double* p) -> int {
+    if (!p) return 0;
+    GPRC_TRY(o.set(p, out_count));
+    if (o.host && gaps) GPRC_HIP(hipMemcpyAsync(o.dev, p, sizeof(double) * (size_t)out_count, hipMemcpyHostToDevice, s));
+    return 0;
+  };
+  GPRC_TRY(stage(mean, mean_out));
+  GPRC_TRY(stage(var, var_out));
+  // the split: whole turns of a workgroup (BATCH_PREDICT_WAVES tiles) over enough workgroups for every CU, when the batch alone has fewer
+  int cus = 0;
+  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  const int64_t tiles = (ns_max + BATCH_PREDICT_TILE - 1) / BATCH_PREDICT_TILE;
+  const int64_t turns = (tiles + BATCH_PREDICT_WAVES - 1) / BATCH_PREDICT_WAVES;
+  const int split = (int)std::min<int64_t>(std::min<int64_t>(turns, 65535), std::max<int64_t>(1, (cus + B - 1) / B));
+  BatchPredictArgs a{m->X.p, m->prm.p, m->alpha.p, m->W.p, reinterpret_cast<const int*>(m->info.p), xs.dev,
+                     ns_each ? reinterpret_cast<const int64_t*>(counts.p) : nullptr, mean.dev, var.dev, m->x_stride, xs_stride, m->d, ns_max, ld_out, 0,
+                     m->prm_stride, m->np_store, m->n_params};
+  constexpr int64_t GRID_Y = 65535;
+  for (int64_t b0 = 0; b0 < B; b0 += GRID_Y) {
+    a.b0 = b0;
+    GPRC_TRY(launch_batch_predict(s, m->kernel, a, std::min<int64_t>(GRID_Y, B - b0), split));
+  }
+  if (mean_out) GPRC_TRY(mean.finish(s));
+  if (var_out) GPRC_TRY(var.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gprc_batch_model_dims(const gprc_batch_model* m, int64_t* B_out, int64_t* d_out, int64_t* n_max_out) {
+  if (!m) return bad("batch_model_dims", "null model");
+  if (B_out) *B_out = m->B;
+  if (d_out) *d_out = m->d;
+  if (n_max_out) *n_max_out = m->n_max;
+  return 0;
+}
+
+int gprc_batch_model_free(gprc_batch_model* m) {
+  if (!m) return 0;
+  if (m->ctx && !ctx_alive(m->ctx, m->ctx_id)) {   // the context went first: its stream is gone (and was synchronised), its pool too
+    m->ctx = nullptr;
+    (void)hipDeviceSynchronize();
+  }
+  if (m->ctx && m->ctx->stream) (void)hipStreamSynchronize(m->ctx->stream);
+  free_batch_model(m);
   return 0;
 }
 

@@ -9,6 +9,7 @@
 //   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create, eval and eval_grad) and their entry points
 //   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict, and
 //                   the stochastic log evidence with its gradient)
+//   gprc_batch.hip  small GPs in batches: the batched evidence and gradient, the fitted batch (gprc_batch_model) and its predict
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
@@ -245,9 +246,35 @@ struct BatchArgs {
   int* info;
   int64_t x_stride, y_stride, d, b0;
   int prm_stride, np_store, n_params, out_stride, want_grad;
+  // where L^-1 goes: null -- behind L in the slab, as above; else model b's at w + b w_stride (128^2 doubles, column-major, zero above the
+  // diagonal), and the slab is batch_scratch_doubles(models, true) doubles, L of workgroup g at slab + g 128^2.  No output depends on it.
+  double* w = nullptr;
+  int64_t w_stride = 0;
 };
-size_t batch_scratch_doubles(int64_t models);
+size_t batch_scratch_doubles(int64_t models, bool keep_w = false);
 int launch_batch_logp_grad(hipStream_t s, int kernel, const BatchArgs& a, int64_t models);
+
+// ---- launchers (kernels_batch_predict.hip: predictions from a fitted batch) ------------------------
+// Posterior mean and latent variance of `models` fitted small models at their own (or one shared) set of test points, one launch:
+// workgroup (sp, g) of a (split, models) grid handles the 16-point tiles sp 8 + wave, + split 8, ... of model b0 + g.  Per model b (all
+// DEVICE memory): prm, X as BatchArgs'; alpha + b 128; W + b 128^2 (BatchArgs::w's layout); info + b (not 0: NaN is written);
+// Xs + b xs_stride its test points (point-major), ns_each[b] of them (null: ns_max); mean / var + b ld_out (either may be null).
+constexpr int BATCH_PREDICT_TILE = 16;    // test points per wave
+constexpr int BATCH_PREDICT_WAVES = 8;    // waves per workgroup: a workgroup takes 128 points per turn
+struct BatchPredictArgs {
+  const double* X;
+  const double* prm;
+  const double* alpha;
+  const double* W;
+  const int* info;
+  const double* Xs;
+  const int64_t* ns_each;
+  double* mean;
+  double* var;
+  int64_t x_stride, xs_stride, d, ns_max, ld_out, b0;
+  int prm_stride, np_store, n_params;
+};
+int launch_batch_predict(hipStream_t s, int kernel, const BatchPredictArgs& a, int64_t models, int split);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

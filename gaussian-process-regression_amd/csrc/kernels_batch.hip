@@ -7,7 +7,8 @@
 //   fill     K_y = K + noise I straight into the LDS image potf2_blocked_body works on (leading dimension BLD): kernel_value<KID> of the
 //            squared distance, ARD coordinates multiplied by 1 / l_k first, as in the contraction kernels; rows and columns >= n_b are
 //            the identity (they add nothing to the log-determinant), everything above the diagonal is zero;
-//   factor   potf2_blocked_body<8>(preloaded), unchanged: L and W = L^-1 go to the workgroup's slab in device memory (2 x 128^2 doubles),
+//   factor   potf2_blocked_body<8>(preloaded), unchanged: L and W = L^-1 go to the workgroup's slab in device memory (2 x 128^2 doubles;
+//            BatchArgs::w set: W goes to w + b w_stride instead, the store of a fitted batch, and the slab is L's 128^2 alone),
 //            info (first non-positive pivot, 1-based) to the model's own word; a bad model finishes its arithmetic and is only flagged;
 //   solve    z = W y, alpha = W^T z, logp = -1/2 y.alpha - sum log L_ii - n_b / 2 log 2 pi;
 //   gradient (when asked for) M = alpha alpha^T - W^T W, one 16 x 16 block of the lower triangle at a time on v_mfma_f64_16x16x4_f64: the
@@ -54,14 +55,6 @@ static_assert(BT_SMEM_BYTES <= 163840, "the batch kernel's LDS must fit a workgr
 constexpr double LOG_2PI = 1.8378770664093453;
 
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-// a p - b p as the contraction kernels form it from their staged coordinates: two rounded products, then the difference.  Contracted
-// into fma(a, p, -(b p)) the difference of two equal points would be the rounding error of the product, not 0.
-__device__ __forceinline__ double bt_scaled_diff(double a, double b, double p) {
-#pragma clang fp contract(off)
-  const double ap = a * p, bp = b * p;
-  return ap - bp;
-}
 
 // s_ij of points i, j < n_b of the model at X (point-major, d coordinates each); SCALED: the coordinates times p[r] = 1 / l_r first
 template <bool SCALED>
@@ -133,8 +126,9 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
   __syncthreads();
 
   // ---- factor and invert
-  double* slab = a.slab + (int64_t)blockIdx.x * (2 * PB * PB);
-  potf2_blocked_body<8>(sm, slab, PB, slab + PB * PB, a.info + b, 0, nullptr, true);
+  // L goes to the launch's scratch; W beside it, or (a.w: a fitted batch keeps it) to the model's own place in the caller's store
+  double* slab = a.slab + (int64_t)blockIdx.x * (a.w ? PB * PB : 2 * PB * PB);
+  potf2_blocked_body<8>(sm, slab, PB, a.w ? a.w + b * a.w_stride : slab + PB * PB, a.info + b, 0, nullptr, true);
   __syncthreads();
 
   // ---- solve
@@ -277,7 +271,7 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
 
 }  // namespace
 
-size_t batch_scratch_doubles(int64_t models) { return (size_t)models * 2 * PB * PB; }
+size_t batch_scratch_doubles(int64_t models, bool keep_w) { return (size_t)models * (keep_w ? 1 : 2) * PB * PB; }
 
 int launch_batch_logp_grad(hipStream_t s, int kernel, const BatchArgs& a, int64_t models) {
   GPRC_TRY(check_grad_kernel("batch_logp_grad", kernel));

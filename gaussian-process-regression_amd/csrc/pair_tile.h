@@ -105,6 +105,15 @@ __device__ __forceinline__ double r_pow(double x, double y) {
   return pow(x, y);
 }
 
+// a p - b p as the contraction kernels form it from their staged coordinates: two rounded products, then the difference.  Contracted
+// into fma(a, p, -(b p)) the difference of two equal points would be the rounding error of the product, not 0.  (The batched kernels,
+// kernels_batch.hip and kernels_batch_predict.hip, scale their ARD coordinates with it: a test point equal to a training point is s = 0.)
+__device__ __forceinline__ double bt_scaled_diff(double a, double b, double p) {
+#pragma clang fp contract(off)
+  const double ap = a * p, bp = b * p;
+  return ap - bp;
+}
+
 // Coordinates r0 .. r0 + dc - 1 of the points g0 .. g0 + count - 1 of P (point-major, d coordinates each; zero from point npts on),
 // by the 256 threads of the workgroup (t: the thread): store(i, r, value) for point i of the tile and coordinate r of the pass.
 // SCALED: times scale[r0 + r] (ARD in the contraction kernels: the coordinates divided by their length scale).

@@ -283,6 +283,38 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
 BATCH_MAX_N = 128   # include/gprc_native.h GPRC_BATCH_MAX_N: the points of one batched model
 
 
+def batch_layout(X, y, B, who="logp_grad_batch"):
+    """The arrays the batched entry points take, (Xb, yb, d, n_max, x_stride, y_stride, n_each): one data set shared by B models
+    (strides 0, n_each None), or lists of B data sets, which may differ in n, padded with zeros into one strided array each
+    (point-major; the padding is never read).  More than 128 points a model: ValueError."""
+    shared = not isinstance(X, (list, tuple))
+    if shared:
+        Xm = as_points(X)
+        yb = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+        d, n_max = Xm.shape
+        if yb.size != n_max:
+            raise ValueError("length(y) == ncol(X) is not TRUE")
+        Xb, x_stride, y_stride, n_each = Xm, 0, 0, None
+    else:
+        if len(X) != B or len(y) != B:
+            raise ValueError("%s: one data set per row of thetas" % who)
+        pts = [as_points(x) for x in X]
+        d = pts[0].shape[0]
+        n_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
+        n_max = int(n_each.max())
+        Xb, yb = np.zeros((B, d * n_max)), np.zeros((B, n_max))
+        for b, (q, yy) in enumerate(zip(pts, y)):
+            yy = np.asarray(yy, dtype=np.float64).ravel()
+            if q.shape[0] != d or yy.size != q.shape[1]:
+                raise ValueError("%s: every data set needs the same nrow(X) and length(y) == ncol(X)" % who)
+            Xb[b, :q.size] = q.ravel(order="F")
+            yb[b, :yy.size] = yy
+        x_stride, y_stride = d * n_max, n_max
+    if n_max > BATCH_MAX_N:
+        raise ValueError("%s: at most %d points a model; logp_grad takes larger ones" % (who, BATCH_MAX_N))
+    return Xb, yb, d, n_max, x_stride, y_stride, n_each
+
+
 def logp_grad_batch(X, y, noise, name, thetas, ctx=None):
     """`logp_grad` for B small models in ONE native call (gprc_gpr_batch_logp_grad: a model of at most 128 points per workgroup):
     (logp[B], grad[B, p + 1], info[B]).  thetas: B x p, a parameter vector per row in the order `dens` takes it (a vector is one
@@ -294,31 +326,7 @@ def logp_grad_batch(X, y, noise, name, thetas, ctx=None):
     thetas = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))
     B, p = thetas.shape
     noises = np.ascontiguousarray(np.broadcast_to(np.asarray(noise, dtype=np.float64), (B,)))
-    shared = not isinstance(X, (list, tuple))
-    if shared:
-        Xm = as_points(X)
-        yb = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
-        d, n_max = Xm.shape
-        if yb.size != n_max:
-            raise ValueError("length(y) == ncol(X) is not TRUE")
-        Xb, x_stride, y_stride, n_each = Xm, 0, 0, None
-    else:
-        if len(X) != B or len(y) != B:
-            raise ValueError("logp_grad_batch: one data set per row of thetas")
-        pts = [as_points(x) for x in X]
-        d = pts[0].shape[0]
-        n_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
-        n_max = int(n_each.max())
-        Xb, yb = np.zeros((B, d * n_max)), np.zeros((B, n_max))
-        for b, (q, yy) in enumerate(zip(pts, y)):
-            yy = np.asarray(yy, dtype=np.float64).ravel()
-            if q.shape[0] != d or yy.size != q.shape[1]:
-                raise ValueError("logp_grad_batch: every data set needs the same nrow(X) and length(y) == ncol(X)")
-            Xb[b, :q.size] = q.ravel(order="F")
-            yb[b, :yy.size] = yy
-        x_stride, y_stride = d * n_max, n_max
-    if n_max > BATCH_MAX_N:
-        raise ValueError("logp_grad_batch: at most %d points a model; logp_grad takes larger ones" % BATCH_MAX_N)
+    Xb, yb, d, n_max, x_stride, y_stride, n_each = batch_layout(X, y, B)
     logp, grad, info = np.empty(B), np.empty((B, p + 1)), np.zeros(B, dtype=np.intc)
     if B == 0:
         return logp, grad, info

@@ -187,6 +187,38 @@ GPRC_API int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, cons
                                       const double* noise, const double* X, int64_t d, int64_t n_max, int64_t x_stride, const double* y,
                                       int64_t y_stride, const int64_t* n_each, double* logp_out, double* grad_out, double* alpha_out,
                                       int* info_out);
+/* A fitted batch ("Batched predict"): gprc_gpr_batch_logp_grad's models kept as an object that predicts.
+ * gprc_gpr_batch_fit takes gprc_gpr_batch_logp_grad's arguments, layout rules and argument errors (model_out must not be NULL either)
+ * and runs the same kernel without the gradient: logp_out, info_out and gprc_gpr_batch_get_alpha's values are bit for bit what
+ * gprc_gpr_batch_logp_grad returns for the same inputs.  A model that is not positive definite is flagged (info_out[b] > 0, logp NaN)
+ * and does not fail the call.  B = 0 returns GPRC_OK and *model_out = NULL.  The object belongs to ctx and owns device copies of the
+ * points, alpha, L^-1 of every model, the per-model parameter records, the counts and info; the caller's arrays are not referenced again.
+ * MEMORY: 128^2 doubles (128 KiB) per model for L^-1, held until gprc_batch_model_free, plus 128 + d * n_max (or x_stride) + n_params + 6
+ * doubles per model; during the fit another 128^2 doubles per model of a launch, at most 32 MiB, from the context's pool.
+ *
+ * gprc_gpr_batch_predict: the posterior mean and the LATENT variance k(x*, x*) - |L^-1 k*|^2 (unclamped, as gprc_gpr_predict(pointwise = 1))
+ * of every model at its own test points, one launch.
+ *   X_star   host or device: model b's points (d x ns_max, one point per column) at X_star + b * xs_stride; xs_stride = 0: one set shared
+ *            by every model; otherwise xs_stride >= d * ns_max
+ *   ns_each  HOST, may be NULL (every model has ns_max points): 1 <= ns_each[b] <= ns_max; what lies behind a model's count is never read
+ *   mean_out, var_out   host or device, model b's values at [b * ld_out + j], ld_out >= ns_max; either may be NULL, not both (without
+ *            var_out the product with L^-1 is skipped; the mean keeps its bits); entries behind ns_each[b] are left as they were
+ * A flagged model's outputs are NaN, its neighbours are unaffected.  A test point's bits depend on its model and its coordinates alone:
+ * not on the other test points, their number, the batch, strides, host or device pointers, or which outputs are asked for.  Against
+ * gprc_gpr_fit + gprc_gpr_predict they agree to rounding, not to the bit.  GPRC_ERR_ARG: a null model, X_star or both outputs NULL,
+ * ns_max < 1, an ns_each outside 1 .. ns_max, a stride that is neither 0 nor at least one model's extent, ld_out < ns_max, a model whose
+ * context has been destroyed.
+ * gprc_gpr_batch_get_alpha: alpha_out HOST, B x n_max, as gprc_gpr_batch_logp_grad's alpha_out.  gprc_batch_model_dims: each output may
+ * be NULL.  gprc_batch_model_free accepts NULL and a model whose context went first. */
+typedef struct gprc_batch_model gprc_batch_model;
+GPRC_API int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params,
+                                const double* noise, const double* X, int64_t d, int64_t n_max, int64_t x_stride, const double* y,
+                                int64_t y_stride, const int64_t* n_each, gprc_batch_model** model_out, double* logp_out, int* info_out);
+GPRC_API int gprc_gpr_batch_predict(gprc_batch_model* model, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each,
+                                    double* mean_out, double* var_out, int64_t ld_out);
+GPRC_API int gprc_gpr_batch_get_alpha(gprc_batch_model* model, double* alpha_out);
+GPRC_API int gprc_batch_model_dims(const gprc_batch_model* model, int64_t* B_out, int64_t* d_out, int64_t* n_max_out);
+GPRC_API int gprc_batch_model_free(gprc_batch_model* model);
 /* Leave-one-out cross-validation of a fitted GPR model in closed form (Rasmussen & Williams 5.4.2; no reference counterpart).  With
  * K_y = K + noise * I, P = K_y^-1, alpha = P y and p_i = P_ii, the prediction of y_i from the other n - 1 observations is
  *   mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i,     logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log(2 pi),
