@@ -65,6 +65,8 @@ PROTOTYPES = {
     "gprc_gpr_batch_logp_grad": (C.c_int, [_vp, C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gprc_gpr_batch_fit": (C.c_int, [_vp, C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.POINTER(_vp), _vp, _vp]),
     "gprc_gpr_batch_predict": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64]),
+    "gprc_gpr_batch_predict_grad": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64]),
+    "gprc_gpr_batch_loo": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "gprc_gpr_batch_get_alpha": (C.c_int, [_vp, _vp]),
     "gprc_batch_model_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_batch_model_free": (C.c_int, [_vp]),

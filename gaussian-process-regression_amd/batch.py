@@ -1,6 +1,8 @@
-"""A fitted batch of small GPs (include/gprc_native.h gprc_gpr_batch_fit / gprc_gpr_batch_predict; DESIGN.md section 7, "Batched
-predict"): B models of at most 128 points each fitted in one native call and kept on the device, and the posterior mean and
-variance of all of them at their test points in one more.  The input conventions are `fit.logp_grad_batch`'s.
+"""A fitted batch of small GPs (include/gprc_native.h gprc_gpr_batch_fit / gprc_gpr_batch_predict / gprc_gpr_batch_predict_grad /
+gprc_gpr_batch_loo; DESIGN.md section 7, "Batched predict" and "Batched prediction gradients and LOO"): B models of at most 128 points
+each fitted in one native call and kept on the device; the posterior mean and variance of all of them at their test points in one
+more, their gradients with respect to the test points likewise, and the leave-one-out predictions of all of them in one.  The input
+conventions are `fit.logp_grad_batch`'s.
 """
 from __future__ import annotations
 
@@ -55,30 +57,34 @@ class BatchGPR:
         nat.check(nat.lib().gprc_gpr_batch_get_alpha(self.handle, out.ctypes.data))
         return out
 
-    def predict(self, X_star, var=True):
-        """Posterior mean and latent variance k(x*, x*) - |L^-1 k*|^2 of every model.  X_star: a d x n* array of test points shared by
-        every model -> (mean[B, n*], var[B, n*]); or a list of B arrays (d x n*_b, which may differ in n*_b) -> (list of B means,
-        list of B variances).  var=False: the variance is not computed and None stands in its place."""
+    def _test_points(self, X_star, who):
+        """(shared, Xsb, ns_max, xs_stride, ns_each) of one shared d x n* set or a list of B sets, padded into one strided array"""
         B, d = self.B, self.d
         shared = not isinstance(X_star, (list, tuple))
         if shared:
             Xs = as_points(X_star, d, "X_star")
             if Xs.shape[0] != d or Xs.shape[1] < 1:
-                raise ValueError("BatchGPR.predict: X_star must be d x n* with n* >= 1")
-            ns_max, xs_stride, ns_each = Xs.shape[1], 0, None
-            Xsb = np.ascontiguousarray(Xs.ravel(order="F"))
-        else:
-            if len(X_star) != B:
-                raise ValueError("BatchGPR.predict: one set of test points per model")
-            pts = [as_points(x, d, "X_star") for x in X_star]
-            if any(q.shape[0] != d or q.shape[1] < 1 for q in pts):
-                raise ValueError("BatchGPR.predict: every set of test points must be d x n* with n* >= 1")
-            ns_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
-            ns_max = int(ns_each.max())
-            xs_stride = d * ns_max
-            Xsb = np.zeros((B, xs_stride))
-            for b, q in enumerate(pts):
-                Xsb[b, :q.size] = q.ravel(order="F")
+                raise ValueError(who + ": X_star must be d x n* with n* >= 1")
+            return True, np.ascontiguousarray(Xs.ravel(order="F")), Xs.shape[1], 0, None
+        if len(X_star) != B:
+            raise ValueError(who + ": one set of test points per model")
+        pts = [as_points(x, d, "X_star") for x in X_star]
+        if any(q.shape[0] != d or q.shape[1] < 1 for q in pts):
+            raise ValueError(who + ": every set of test points must be d x n* with n* >= 1")
+        ns_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
+        ns_max = int(ns_each.max())
+        xs_stride = d * ns_max
+        Xsb = np.zeros((B, xs_stride))
+        for b, q in enumerate(pts):
+            Xsb[b, :q.size] = q.ravel(order="F")
+        return False, Xsb, ns_max, xs_stride, ns_each
+
+    def predict(self, X_star, var=True):
+        """Posterior mean and latent variance k(x*, x*) - |L^-1 k*|^2 of every model.  X_star: a d x n* array of test points shared by
+        every model -> (mean[B, n*], var[B, n*]); or a list of B arrays (d x n*_b, which may differ in n*_b) -> (list of B means,
+        list of B variances).  var=False: the variance is not computed and None stands in its place."""
+        B = self.B
+        shared, Xsb, ns_max, xs_stride, ns_each = self._test_points(X_star, "BatchGPR.predict")
         mean = np.full((B, ns_max), np.nan)
         v = np.full((B, ns_max), np.nan) if var else None
         nat.check(nat.lib().gprc_gpr_batch_predict(self.handle, Xsb.ctypes.data, ns_max, xs_stride, None if ns_each is None else ns_each.ctypes.data,
@@ -86,6 +92,45 @@ class BatchGPR:
         if shared:
             return mean, v
         return [mean[b, :n] for b, n in enumerate(ns_each)], (None if v is None else [v[b, :n] for b, n in enumerate(ns_each)])
+
+    def predict_grad(self, X_star, var=True):
+        """`predict` with the gradients with respect to the test points (gprc_gpr_batch_predict_grad), one launch.  X_star shared
+        (d x n*) -> (mean[B, n*], var[B, n*], dmean[B, d, n*], dvar[B, d, n*]); a list of B sets -> four lists, model b's gradients
+        d x n*_b, the orientation of `GPR.predict_grad`.  var=False: None stands for var and dvar and the product with L^-T is skipped."""
+        B, d = self.B, self.d
+        shared, Xsb, ns_max, xs_stride, ns_each = self._test_points(X_star, "BatchGPR.predict_grad")
+        mean = np.full((B, ns_max), np.nan)
+        dmean = np.full((B, d * ns_max), np.nan)
+        v = np.full((B, ns_max), np.nan) if var else None
+        dv = np.full((B, d * ns_max), np.nan) if var else None
+        nat.check(nat.lib().gprc_gpr_batch_predict_grad(self.handle, Xsb.ctypes.data, ns_max, xs_stride, None if ns_each is None else ns_each.ctypes.data,
+                                                        mean.ctypes.data, None if v is None else v.ctypes.data, ns_max, dmean.ctypes.data,
+                                                        None if dv is None else dv.ctypes.data, d * ns_max))
+
+        if shared:         # the library's [b][j][c] (X_star's own layout) as B x d x n*
+            return mean, v, dmean.reshape(B, ns_max, d).transpose(0, 2, 1).copy(), None if dv is None else dv.reshape(B, ns_max, d).transpose(0, 2, 1).copy()
+
+        def cut(a, width):
+            return None if a is None else [a[b, :width * n] for b, n in enumerate(ns_each)]
+
+        def by_coordinate(rows):
+            return None if rows is None else [np.ascontiguousarray(r.reshape(-1, d).T) for r in rows]
+
+        return cut(mean, 1), cut(v, 1), by_coordinate(cut(dmean, d)), by_coordinate(cut(dv, d))
+
+    def loo(self):
+        """Leave-one-out cross-validation of every model in closed form (gprc_gpr_batch_loo), one launch: (mean, var, logdens), each
+        B x n_max; var is the variance of the NOISY observation, as `GPR.loo`; entries behind a model's n_b points are NaN."""
+        out = [np.full((self.B, self.n_max), np.nan) for _ in range(3)]
+        nat.check(nat.lib().gprc_gpr_batch_loo(self.handle, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, self.n_max, None))
+        return tuple(out)
+
+    @property
+    def loo_score(self):
+        """the B LOO log predictive probabilities sum_i logdens_i (NaN for a flagged model)"""
+        score = np.full(self.B, np.nan)
+        nat.check(nat.lib().gprc_gpr_batch_loo(self.handle, None, None, None, self.n_max, score.ctypes.data))
+        return score
 
     def close(self):
         if getattr(self, "_model", None):

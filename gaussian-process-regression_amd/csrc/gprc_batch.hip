@@ -1,5 +1,5 @@
 // gprc_batch.hip -- small GPs in batches ("Small models in batches" and "Batched predict"): the host side of
-// gprc_gpr_batch_logp_grad, gprc_gpr_batch_fit and gprc_gpr_batch_predict.
+// gprc_gpr_batch_logp_grad, gprc_gpr_batch_fit, gprc_gpr_batch_predict, gprc_gpr_batch_predict_grad and gprc_gpr_batch_loo.
 // The argument checks, one record of derived constants per model (make_deriv_spec, once per model), the staging of host arrays, the
 // launches of kernels_batch.hip -- at most GPRC_BATCH_LAUNCH models each, on one set of scratch slabs from the context's pool -- and the
 // tail every exact gradient has: the sums that the device leaves get 1/2 and the factors of cross_grad_finish, a model that is not
@@ -18,13 +18,15 @@ using namespace gprc;
 
 static_assert(GPRC_BATCH_MAX_N == NBI, "a batched model is one LDS-resident diagonal block");
 
-// A fitted batch: what gprc_gpr_batch_predict reads again, all in device memory from the context's pool.
+// A fitted batch: what gprc_gpr_batch_predict, _predict_grad and _loo read again, all in device memory from the context's pool.
 struct gprc_batch_model {
   gprc_ctx* ctx = nullptr;
   uint64_t ctx_id = 0;
   int kernel = 0, n_params = 0, np_store = 0, prm_stride = 0;
-  int64_t B = 0, d = 0, n_max = 0, x_stride = 0;
+  int64_t B = 0, d = 0, n_max = 0, x_stride = 0, y_stride = 0;
+  bool uneven = false;   // fitted with n_each: a model may have fewer than n_max points
   DevMem X;       // the points: d * n_max doubles (shared) or B strides of the caller's x_stride
+  DevMem y;       // the targets: n_max doubles (shared) or B strides of the caller's y_stride (gprc_gpr_batch_loo reads them)
   DevMem alpha;   // B x 128, zero from n_b on
   DevMem W;       // B x 128^2: L^-1 of every model (BatchArgs::w)
   DevMem prm;     // B records: the derived constants, the noise, n_b
@@ -121,10 +123,77 @@ void free_batch_model(gprc_batch_model* m) {
   if (!m) return;
   if (m->ctx) (void)hipSetDevice(m->ctx->device);
   else                                   // the context went first: the buffers go straight back to the driver
-    for (DevMem* q : {&m->X, &m->alpha, &m->W, &m->prm, &m->info}) q->owner = nullptr;
+    for (DevMem* q : {&m->X, &m->y, &m->alpha, &m->W, &m->prm, &m->info}) q->owner = nullptr;
   delete m;
 }
 struct BatchModelFree { void operator()(gprc_batch_model* m) const { free_batch_model(m); } };
+
+// gprc_gpr_batch_predict and gprc_gpr_batch_predict_grad: one set of checks, one staging, one split rule; grad: the gradient entry point
+int batch_predict_any(const char* who, bool grad, gprc_batch_model* m, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each,
+                      double* mean_out, double* var_out, int64_t ld_out, double* dmean_out, double* dvar_out, int64_t ld_grad) {
+  if (!m) return bad(who, "null model");
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  if (!X_star) return bad(who, "null input pointer (X_star)");
+  if (!grad && !mean_out && !var_out) return bad(who, "null output pointers (mean_out and var_out: one of them may be NULL, not both)");
+  if (grad && !mean_out && !var_out && !dmean_out && !dvar_out)
+    return bad(who, "null output pointers (mean_out, var_out, dmean_out, dvar_out: not all four may be NULL)");
+  if (ns_max < 1) return bad(who, "ns_max < 1");
+  if (xs_stride != 0 && xs_stride < m->d * ns_max) return bad(who, "xs_stride must be 0 (shared) or >= d * ns_max");
+  if (ld_out < ns_max) return bad(who, "ld_out < ns_max");
+  if ((dmean_out || dvar_out) && ld_grad < m->d * ns_max) return bad(who, "ld_grad < d * ns_max");
+  const int64_t B = m->B;
+  if (ns_each)
+    for (int64_t b = 0; b < B; ++b)
+      if (ns_each[b] < 1 || ns_each[b] > ns_max) return bad(who, "ns_each of model " + std::to_string(b) + " is outside 1 .. ns_max");
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  In xs;
+  GPRC_TRY(xs.set(s, X_star, (xs_stride ? (B - 1) * xs_stride : 0) + m->d * ns_max));
+  DevMem counts;
+  if (ns_each) {
+    static_assert(sizeof(int64_t) == sizeof(double), "the counts travel in a block of doubles");
+    GPRC_TRY(counts.alloc(B));
+    GPRC_HIP(hipMemcpyAsync(counts.p, ns_each, sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice, s));
+  }
+  // A host output goes through a temporary of the same pitch.  Where the launch does not write every entry of it -- counts, or a pitch
+  // beyond ns_max -- the temporary starts as the caller's array: what lies behind a model's count comes back as it was.
+  const int64_t out_count = (B - 1) * ld_out + ns_max;
+  const bool gaps = ns_each != nullptr || (ld_out > ns_max && B > 1);
+  const int64_t grad_count = (B - 1) * ld_grad + m->d * ns_max;
+  const bool grad_gaps = ns_each != nullptr || (ld_grad > m->d * ns_max && B > 1);
+  Out mean, var, dmean, dvar;
+  auto stage = [&](Out& o, double* p, int64_t count, bool some) -> int {
+    if (!p) return 0;
+    GPRC_TRY(o.set(p, count));
+    if (o.host && some) GPRC_HIP(hipMemcpyAsync(o.dev, p, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, s));
+    return 0;
+  };
+  GPRC_TRY(stage(mean, mean_out, out_count, gaps));
+  GPRC_TRY(stage(var, var_out, out_count, gaps));
+  GPRC_TRY(stage(dmean, dmean_out, grad_count, grad_gaps));
+  GPRC_TRY(stage(dvar, dvar_out, grad_count, grad_gaps));
+  // the split: whole turns of a workgroup (BATCH_PREDICT_WAVES tiles) over enough workgroups for every CU, when the batch alone has fewer
+  int cus = 0;
+  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  const int64_t tiles = (ns_max + BATCH_PREDICT_TILE - 1) / BATCH_PREDICT_TILE;
+  const int64_t turns = (tiles + BATCH_PREDICT_WAVES - 1) / BATCH_PREDICT_WAVES;
+  const int split = (int)std::min<int64_t>(std::min<int64_t>(turns, 65535), std::max<int64_t>(1, (cus + B - 1) / B));
+  BatchPredictArgs a{m->X.p, m->prm.p, m->alpha.p, m->W.p, reinterpret_cast<const int*>(m->info.p), xs.dev,
+                     ns_each ? reinterpret_cast<const int64_t*>(counts.p) : nullptr, mean.dev, var.dev, m->x_stride, xs_stride, m->d, ns_max, ld_out, 0,
+                     m->prm_stride, m->np_store, m->n_params, dmean.dev, dvar.dev, ld_grad};
+  constexpr int64_t GRID_Y = 65535;
+  for (int64_t b0 = 0; b0 < B; b0 += GRID_Y) {
+    a.b0 = b0;
+    GPRC_TRY((grad ? launch_batch_predict_grad : launch_batch_predict)(s, m->kernel, a, std::min<int64_t>(GRID_Y, B - b0), split));
+  }
+  if (mean_out) GPRC_TRY(mean.finish(s));
+  if (var_out) GPRC_TRY(var.finish(s));
+  if (dmean_out) GPRC_TRY(dmean.finish(s));
+  if (dvar_out) GPRC_TRY(dvar.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
 
 }  // namespace
 
@@ -202,19 +271,22 @@ int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* param
   m->d = d;
   m->n_max = n_max;
   m->x_stride = x_stride;
-  // the model's own copy of the points: the kernel reads it now and gprc_gpr_batch_predict reads it again
+  m->y_stride = y_stride;
+  m->uneven = n_each != nullptr;
+  // the model's own copies of the points and the targets: the kernel reads them now, gprc_gpr_batch_predict and gprc_gpr_batch_loo again
   const int64_t x_count = (x_stride ? (B - 1) * x_stride : 0) + d * n_max;
   GPRC_TRY(m->X.alloc(x_count));
   GPRC_HIP(hipMemcpyAsync(m->X.p, X, sizeof(double) * (size_t)x_count, is_device_ptr(X) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-  In yin;
-  GPRC_TRY(yin.set(s, y, (y_stride ? (B - 1) * y_stride : 0) + n_max));
+  const int64_t y_count = (y_stride ? (B - 1) * y_stride : 0) + n_max;
+  GPRC_TRY(m->y.alloc(y_count));
+  GPRC_HIP(hipMemcpyAsync(m->y.p, y, sizeof(double) * (size_t)y_count, is_device_ptr(y) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   if (int rc = m->W.alloc(B * (int64_t)NBI * NBI)) {
     if (rc == GPRC_ERR_NOMEM)
       set_error(std::string(who) + ": L^-1 of every model, " + std::to_string((B * (int64_t)NBI * NBI * 8) >> 20) + " MiB of device memory, could not be allocated");
     return rc;
   }
   DevMem out;
-  GPRC_TRY(batch_launches(who, s, kernel, B, r, n_params, m->X.p, x_stride, yin.dev, y_stride, d, false, m->W.p, m->prm, out, m->alpha, m->info));
+  GPRC_TRY(batch_launches(who, s, kernel, B, r, n_params, m->X.p, x_stride, m->y.p, y_stride, d, false, m->W.p, m->prm, out, m->alpha, m->info));
   std::vector<double> hout((size_t)(B * r.out_stride));
   GPRC_HIP(hipMemcpyAsync(hout.data(), out.p, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, s));
   GPRC_HIP(hipMemcpyAsync(info_out, m->info.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s));
@@ -249,34 +321,28 @@ int gprc_gpr_batch_get_alpha(gprc_batch_model* m, double* alpha_out) {
 
 int gprc_gpr_batch_predict(gprc_batch_model* m, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each, double* mean_out,
                            double* var_out, int64_t ld_out) {
-  const char* who = "batch_predict";
+  return batch_predict_any("batch_predict", false, m, X_star, ns_max, xs_stride, ns_each, mean_out, var_out, ld_out, nullptr, nullptr, 0);
+}
+
+int gprc_gpr_batch_predict_grad(gprc_batch_model* m, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each,
+                                double* mean_out, double* var_out, int64_t ld_out, double* dmean_out, double* dvar_out, int64_t ld_grad) {
+  return batch_predict_any("batch_predict_grad", true, m, X_star, ns_max, xs_stride, ns_each, mean_out, var_out, ld_out, dmean_out, dvar_out, ld_grad);
+}
+
+int gprc_gpr_batch_loo(gprc_batch_model* m, double* mean_out, double* var_out, double* logdens_out, int64_t ld_out, double* loo_out) {
+  const char* who = "batch_loo";
   if (!m) return bad(who, "null model");
   if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
-  if (!X_star) return bad(who, "null input pointer (X_star)");
-  if (!mean_out && !var_out) return bad(who, "null output pointers (mean_out and var_out: one of them may be NULL, not both)");
-  if (ns_max < 1) return bad(who, "ns_max < 1");
-  if (xs_stride != 0 && xs_stride < m->d * ns_max) return bad(who, "xs_stride must be 0 (shared) or >= d * ns_max");
-  if (ld_out < ns_max) return bad(who, "ld_out < ns_max");
+  if (!mean_out && !var_out && !logdens_out && !loo_out) return bad(who, "null output pointers (mean_out, var_out, logdens_out, loo_out: not all four may be NULL)");
+  if ((mean_out || var_out || logdens_out) && ld_out < m->n_max) return bad(who, "ld_out < n_max");
   const int64_t B = m->B;
-  if (ns_each)
-    for (int64_t b = 0; b < B; ++b)
-      if (ns_each[b] < 1 || ns_each[b] > ns_max) return bad(who, "ns_each of model " + std::to_string(b) + " is outside 1 .. ns_max");
   gprc_ctx* ctx = m->ctx;
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
-  In xs;
-  GPRC_TRY(xs.set(s, X_star, (xs_stride ? (B - 1) * xs_stride : 0) + m->d * ns_max));
-  DevMem counts;
-  if (ns_each) {
-    static_assert(sizeof(int64_t) == sizeof(double), "the counts travel in a block of doubles");
-    GPRC_TRY(counts.alloc(B));
-    GPRC_HIP(hipMemcpyAsync(counts.p, ns_each, sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice, s));
-  }
-  // A host output goes through a temporary of the same pitch.  Where the launch does not write every entry of it -- counts, or a pitch
-  // beyond ns_max -- the temporary starts as the caller's array: what lies behind a model's count comes back as it was.
-  const int64_t out_count = (B - 1) * ld_out + ns_max;
-  const bool gaps = ns_each != nullptr || (ld_out > ns_max && B > 1);
-  Out mean, var;
+  // host outputs as gprc_gpr_batch_predict's: where the launch leaves entries alone the temporary starts as the caller's array
+  const int64_t out_count = (B - 1) * ld_out + m->n_max;
+  const bool gaps = m->uneven || (ld_out > m->n_max && B > 1);
+  Out mean, var, dens;
   auto stage = [&](Out& o, double* p) -> int {
     if (!p) return 0;
     GPRC_TRY(o.set(p, out_count));
@@ -285,22 +351,20 @@ int gprc_gpr_batch_predict(gprc_batch_model* m, const double* X_star, int64_t ns
   };
   GPRC_TRY(stage(mean, mean_out));
   GPRC_TRY(stage(var, var_out));
-  // the split: whole turns of a workgroup (BATCH_PREDICT_WAVES tiles) over enough workgroups for every CU, when the batch alone has fewer
-  int cus = 0;
-  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const int64_t tiles = (ns_max + BATCH_PREDICT_TILE - 1) / BATCH_PREDICT_TILE;
-  const int64_t turns = (tiles + BATCH_PREDICT_WAVES - 1) / BATCH_PREDICT_WAVES;
-  const int split = (int)std::min<int64_t>(std::min<int64_t>(turns, 65535), std::max<int64_t>(1, (cus + B - 1) / B));
-  BatchPredictArgs a{m->X.p, m->prm.p, m->alpha.p, m->W.p, reinterpret_cast<const int*>(m->info.p), xs.dev,
-                     ns_each ? reinterpret_cast<const int64_t*>(counts.p) : nullptr, mean.dev, var.dev, m->x_stride, xs_stride, m->d, ns_max, ld_out, 0,
-                     m->prm_stride, m->np_store, m->n_params};
-  constexpr int64_t GRID_Y = 65535;
-  for (int64_t b0 = 0; b0 < B; b0 += GRID_Y) {
+  GPRC_TRY(stage(dens, logdens_out));
+  DevMem score;
+  if (loo_out) GPRC_TRY(score.alloc(B));
+  BatchLooArgs a{m->W.p, m->alpha.p, m->y.p, m->prm.p, reinterpret_cast<const int*>(m->info.p), mean.dev, var.dev, dens.dev, score.p,
+                 m->y_stride, ld_out, 0, m->prm_stride, m->np_store};
+  constexpr int64_t GRID_X = int64_t(1) << 30;
+  for (int64_t b0 = 0; b0 < B; b0 += GRID_X) {
     a.b0 = b0;
-    GPRC_TRY(launch_batch_predict(s, m->kernel, a, std::min<int64_t>(GRID_Y, B - b0), split));
+    GPRC_TRY(launch_batch_loo(s, a, std::min<int64_t>(GRID_X, B - b0)));
   }
   if (mean_out) GPRC_TRY(mean.finish(s));
   if (var_out) GPRC_TRY(var.finish(s));
+  if (logdens_out) GPRC_TRY(dens.finish(s));
+  if (loo_out) GPRC_HIP(hipMemcpyAsync(loo_out, score.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
   GPRC_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -273,8 +273,35 @@ struct BatchPredictArgs {
   double* var;
   int64_t x_stride, xs_stride, d, ns_max, ld_out, b0;
   int prm_stride, np_store, n_params;
+  // launch_batch_predict_grad only: model b's gradients of test point j with respect to coordinate c at dmean / dvar + b ld_grad + d j + c
+  // (either may be null; with both null the launch is launch_batch_predict's work and bits), ld_grad >= d ns_max
+  double* dmean = nullptr;
+  double* dvar = nullptr;
+  int64_t ld_grad = 0;
 };
 int launch_batch_predict(hipStream_t s, int kernel, const BatchPredictArgs& a, int64_t models, int split);
+// The same launch with the gradients with respect to the test points (the same kernel body behind a template flag: mean and var keep
+// launch_batch_predict's bits):  dmean = -t_c sum_k alpha_k h_k (x*_c - x_kc),  dvar = 2 t_c sum_k u_k h_k (x*_c - x_kc),  u = W^T (W k*).
+int launch_batch_predict_grad(hipStream_t s, int kernel, const BatchPredictArgs& a, int64_t models, int split);
+
+// ---- launchers (kernels_batch_loo.hip: leave-one-out from a fitted batch) --------------------------
+// One workgroup per model, model b0 + g: p_i = sum_{k >= i} W[k + 128 i]^2, mean_i = y_i - alpha_i / p_i, var_i = 1 / p_i,
+// logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log 2 pi at mean / var / dens + b ld_out + i, i < n_b (each may be null), and
+// score[b] = sum_i logdens_i (may be null).  A flagged model (info != 0) gets NaN.  All DEVICE memory; prm, alpha, W, info as above.
+struct BatchLooArgs {
+  const double* W;
+  const double* alpha;
+  const double* y;
+  const double* prm;
+  const int* info;
+  double* mean;
+  double* var;
+  double* dens;
+  double* score;
+  int64_t y_stride, ld_out, b0;
+  int prm_stride, np_store;
+};
+int launch_batch_loo(hipStream_t s, const BatchLooArgs& a, int64_t models);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

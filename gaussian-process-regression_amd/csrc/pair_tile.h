@@ -80,8 +80,9 @@ inline KernelSpec make_deriv_spec(const KernelSpec& ks) {
 }
 
 // the factor of dk / dx*_c that pair_weight leaves out, without its sign and, for ARD, without the second 1 / l_c (the tail kernels
-// multiply by the deriv spec's p[c]; sqrexp_ard's 1.0 * p[c] is p[c] exactly): ks is the caller's spec, not the derived one
-inline double deriv_tail_factor(const KernelSpec& ks) {
+// multiply by the deriv spec's p[c]; sqrexp_ard's 1.0 * p[c] is p[c] exactly): ks is the caller's spec, not the derived one (it reads
+// p[0] of the isotropic kernels and gammaexp's p[1], which make_deriv_spec keeps: the batched kernels call it on their derived record)
+__host__ __device__ inline double deriv_tail_factor(const KernelSpec& ks) {
   const double il2 = 1.0 / (ks.p[0] * ks.p[0]);
   switch (ks.id) {
     case GPRC_GAMMAEXP: return ks.p[1];

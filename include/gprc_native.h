@@ -193,8 +193,8 @@ GPRC_API int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, cons
  * gprc_gpr_batch_logp_grad returns for the same inputs.  A model that is not positive definite is flagged (info_out[b] > 0, logp NaN)
  * and does not fail the call.  B = 0 returns GPRC_OK and *model_out = NULL.  The object belongs to ctx and owns device copies of the
  * points, alpha, L^-1 of every model, the per-model parameter records, the counts and info; the caller's arrays are not referenced again.
- * MEMORY: 128^2 doubles (128 KiB) per model for L^-1, held until gprc_batch_model_free, plus 128 + d * n_max (or x_stride) + n_params + 6
- * doubles per model; during the fit another 128^2 doubles per model of a launch, at most 32 MiB, from the context's pool.
+ * MEMORY: 128^2 doubles (128 KiB) per model for L^-1, held until gprc_batch_model_free, plus 128 + d * n_max (or x_stride) + n_max (or
+ * y_stride: the targets, which gprc_gpr_batch_loo reads) + n_params + 6 doubles per model; during the fit another 128^2 doubles per model of a launch, at most 32 MiB, from the context's pool.
  *
  * gprc_gpr_batch_predict: the posterior mean and the LATENT variance k(x*, x*) - |L^-1 k*|^2 (unclamped, as gprc_gpr_predict(pointwise = 1))
  * of every model at its own test points, one launch.
@@ -216,6 +216,35 @@ GPRC_API int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const doub
                                 int64_t y_stride, const int64_t* n_each, gprc_batch_model** model_out, double* logp_out, int* info_out);
 GPRC_API int gprc_gpr_batch_predict(gprc_batch_model* model, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each,
                                     double* mean_out, double* var_out, int64_t ld_out);
+/* gprc_gpr_batch_predict with the gradients with respect to the test points, one launch ("Batched prediction
+ * gradients and LOO"); the formulas, the conventions and the kernels are gprc_gpr_predict_grad's:
+ *   d mean / d x*_c = sum_k alpha_k dk(x*, x_k) / d x*_c,     d var / d x*_c = -2 sum_k u_k dk(x*, x_k) / d x*_c,  u = K_y^-1 k*,
+ * dk / d x*_c = -h (x*_c - x_kc) t_c; a gammaexp pair at distance 0 contributes 0; Matern is finite at a training point.
+ *   X_star, ns_max, xs_stride, ns_each, mean_out, var_out, ld_out   exactly gprc_gpr_batch_predict's
+ *   dmean_out, dvar_out   host or device: model b's gradient of test point j with respect to coordinate c at [b * ld_grad + d * j + c]
+ *            (X_star's own layout, as gprc_gpr_predict_grad), ld_grad >= d * ns_max; entries behind ns_each[b] points are left as they were
+ * Each of the four outputs may be NULL, not all four; without dvar_out the product with L^-T is not formed, without var_out and dvar_out
+ * L^-1 is not read.  mean_out and var_out are bit for bit gprc_gpr_batch_predict's, whichever outputs are asked for.  The gradient bits
+ * of a test point depend on its model and its coordinates alone: not on the other test points, their number, the batch, strides, host or
+ * device pointers, or which outputs are asked for.  A flagged model's outputs are NaN, its neighbours are unaffected.  Against
+ * gprc_gpr_fit + gprc_gpr_predict_grad they agree to rounding, not to the bit.  GPRC_ERR_ARG: gprc_gpr_batch_predict's (all four outputs
+ * NULL in place of both), and ld_grad < d * ns_max with a gradient asked for.
+ *
+ * gprc_gpr_batch_loo: leave-one-out cross-validation of every model in closed form, one launch, from what the object keeps: with
+ * p_i = sum_{k >= i} (L^-1)_ki^2 = (K_y^-1)_ii, for i < n_b
+ *   mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i  (of the NOISY y_i, as gprc_gpr_loo),
+ *   logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log(2 pi).
+ *   mean_out, var_out, logdens_out   host or device: model b's values at [b * ld_out + i], ld_out >= n_max; entries behind n_b are left
+ *            as they were
+ *   loo_out  HOST, B: sum_i logdens_i of every model, summed on the device in a fixed order (entries i and i + 64 first, then a binary
+ *            tree over the 64 pairs): the same bits on every call and in any batch
+ * Each of the four may be NULL, not all four.  A flagged model gets NaN.  GPRC_ERR_ARG: a null model, all four outputs NULL,
+ * ld_out < n_max with one of the three arrays asked for, a model whose context has been destroyed. */
+GPRC_API int gprc_gpr_batch_predict_grad(gprc_batch_model* model, const double* X_star, int64_t ns_max, int64_t xs_stride,
+                                         const int64_t* ns_each, double* mean_out, double* var_out, int64_t ld_out, double* dmean_out,
+                                         double* dvar_out, int64_t ld_grad);
+GPRC_API int gprc_gpr_batch_loo(gprc_batch_model* model, double* mean_out, double* var_out, double* logdens_out, int64_t ld_out,
+                                double* loo_out);
 GPRC_API int gprc_gpr_batch_get_alpha(gprc_batch_model* model, double* alpha_out);
 GPRC_API int gprc_batch_model_dims(const gprc_batch_model* model, int64_t* B_out, int64_t* d_out, int64_t* n_max_out);
 GPRC_API int gprc_batch_model_free(gprc_batch_model* model);
