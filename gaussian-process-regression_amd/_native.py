@@ -70,6 +70,13 @@ PROTOTYPES = {
     "gprc_gpr_batch_get_alpha": (C.c_int, [_vp, _vp]),
     "gprc_batch_model_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_batch_model_free": (C.c_int, [_vp]),
+    "gprc_dev_knn": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64]),
+    "gprc_lgpr_create": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, _i64, C.POINTER(_vp)]),
+    "gprc_lgpr_set_params": (C.c_int, [_vp, _dp, C.c_int, C.c_double]),
+    "gprc_lgpr_predict": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "gprc_lgpr_neighbours": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64]),
+    "gprc_lgpr_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "gprc_lgpr_free": (C.c_int, [_vp]),
     "gprc_gpr_loo": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "gprc_gpr_loo_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.POINTER(C.c_double), _dp]),
     "gprc_gpr_predict": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp]),

@@ -10,6 +10,7 @@
 //   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict, and
 //                   the stochastic log evidence with its gradient)
 //   gprc_batch.hip  small GPs in batches: the batched evidence and gradient, the fitted batch (gprc_batch_model) and its predict
+//   gprc_local.hip  the local GPR: device nearest-neighbour search, then one batched small model per test point (on gprc_batch's entry points)
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
@@ -302,6 +303,19 @@ struct BatchLooArgs {
   int prm_stride, np_store;
 };
 int launch_batch_loo(hipStream_t s, const BatchLooArgs& a, int64_t models);
+
+// ---- launchers (kernels_knn.hip: exact nearest neighbours, the front of the local GPR) -------------
+// Per query j < ns the m <= 128 candidates i < n with the smallest key (dist2, i), lexicographic, ascending, at idx / dist + j ld (dist may
+// be null; ld >= m), dist2 = sum_c ((xs_jc - x_ic) scale_c)^2 with c ascending (scale null: 1).  All DEVICE memory, points point-major.
+// knn_split chooses, from n, ns and the CU count only, into how many parts the candidates are cut (few queries: so that every CU has
+// work); the parts' lists are merged on the same key, so no output bit depends on the split.  work: knn_workspace_doubles() doubles.
+void knn_split(int64_t n, int64_t ns, int cus, int* parts, int64_t* part_len);
+size_t knn_workspace_doubles(int64_t ns, int m, int parts);
+int launch_knn(hipStream_t s, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, const double* scale, int m, int* idx, double* dist,
+               int64_t ld, int parts, int64_t part_len, double* work);
+// the neighbours as the slabs gprc_gpr_batch_fit reads: Xg + j d m the m points of query j (point-major, in idx's order), yg + j m their
+// targets; an index < 0 (an empty rank) gives NaN
+int launch_knn_gather(hipStream_t s, const int* idx, int64_t ld, const double* X, const double* y, int64_t d, int64_t ns, int64_t m, double* Xg, double* yg);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

@@ -1,0 +1,269 @@
+// gprc_local.hip -- the local GPR ("Local GPR"): the host side of gprc_dev_knn and gprc_lgpr_*.  A test point is
+// conditioned on its m <= 128 nearest training points only: the exact neighbour search of kernels_knn.hip, the gather into the strided
+// slabs of the batched small models, then gprc_gpr_batch_fit and gprc_gpr_batch_predict (gprc_batch.hip) on device pointers -- one
+// model per test point, one test point per model.  Nothing here factorises; the training set lives on the device once, in the object.
+// A model, and so a test point, does not look at any other: its bits do not depend on n*, on the chunk it falls into or on its place.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "gprc_host.h"
+#include "pair_tile.h"
+
+using namespace gprc;
+
+constexpr int64_t LGPR_CHUNK = 2048;   // test points per batched fit: 2048 x 128 KiB = 256 MiB of L^-1 at a time
+
+struct gprc_local_model {
+  gprc_ctx* ctx = nullptr;
+  uint64_t ctx_id = 0;
+  int kernel = 0;
+  std::vector<double> params;
+  double noise = 0.0;
+  int64_t n = 0, d = 0, m = 0;
+  DevMem X;       // d x n
+  DevMem y;       // n
+  DevMem scale;   // d doubles, 1 / l_c: the search metric of an ARD kernel (not allocated otherwise: Euclidean)
+};
+
+namespace {
+
+int bad(const char* who, const std::string& msg) { set_error(std::string(who) + ": " + msg); return GPRC_ERR_ARG; }
+
+// an int array on the device for a host or device destination of `rows` rows of m with pitch ld
+struct IntOut {
+  int* dev = nullptr;
+  int* host = nullptr;
+  DevMem tmp;
+  int64_t ld = 0, ld_host = 0, m = 0, rows = 0;
+  int set(int* p, int64_t ld_out, int64_t rows_, int64_t m_) {
+    dev = p; ld = ld_out; m = m_; rows = rows_;
+    if (is_device_ptr(p)) return 0;
+    host = p; ld_host = ld_out;
+    GPRC_TRY(tmp.alloc((rows * m + 1) / 2));
+    dev = reinterpret_cast<int*>(tmp.p); ld = m;
+    return 0;
+  }
+  int finish(hipStream_t s) {
+    if (host) GPRC_HIP(hipMemcpy2DAsync(host, sizeof(int) * ld_host, dev, sizeof(int) * ld, sizeof(int) * m, rows, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+};
+
+// the search on device pointers, asynchronous: the split, its workspace (released to the pool when this returns: the stream orders its reuse)
+int knn_on_device(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, const double* scale, int64_t m, int* idx, double* dist,
+                  int64_t ld) {
+  int cus = 0;
+  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  int parts = 1;
+  int64_t part_len = 0;
+  knn_split(n, ns, cus, &parts, &part_len);
+  DevMem work;
+  if (parts > 1) GPRC_TRY(work.alloc((int64_t)knn_workspace_doubles(ns, (int)m, parts)));
+  return launch_knn(ctx->stream, X, d, n, Xs, ns, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
+}
+
+int check_scale(const char* who, const double* scale, int64_t d) {
+  for (int64_t c = 0; c < d; ++c)
+    if (!(scale[c] > 0.0) || !std::isfinite(scale[c])) return bad(who, "scale[" + std::to_string(c) + "] must be finite and > 0");
+  return 0;
+}
+
+// idx / dist (rows of m, pitch ld_out, host or device; dist may be null) of the n_star points at X_star
+int knn_any(const char* who, gprc_ctx* ctx, const double* Xdev, int64_t d, int64_t n, const double* X_star, int64_t n_star, const double* scale_dev,
+            int64_t m, int* idx_out, double* dist_out, int64_t ld_out) {
+  hipStream_t s = ctx->stream;
+  In xs;
+  GPRC_TRY(xs.set(s, X_star, d * n_star));
+  IntOut idx;
+  GPRC_TRY(idx.set(idx_out, ld_out, n_star, m));
+  Out dist;
+  if (dist_out) {
+    if (is_device_ptr(dist_out) != (idx.host == nullptr)) return bad(who, "idx_out and dist_out must both be host or both be device memory");
+    if (idx.host) GPRC_TRY(dist.set(dist_out, ld_out, m, n_star));   // compact rows of m, copied back with the caller's pitch
+    else dist.dev = dist_out;
+  }
+  GPRC_TRY(knn_on_device(ctx, Xdev, d, n, xs.dev, n_star, scale_dev, m, idx.dev, dist.dev, idx.ld));
+  GPRC_TRY(idx.finish(s));
+  if (dist_out) GPRC_TRY(dist.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+void free_local_model(gprc_local_model* m) {
+  if (!m) return;
+  if (m->ctx) (void)hipSetDevice(m->ctx->device);
+  else                                   // the context went first: the buffers go straight back to the driver
+    for (DevMem* q : {&m->X, &m->y, &m->scale}) q->owner = nullptr;
+  delete m;
+}
+struct LocalModelFree { void operator()(gprc_local_model* m) const { free_local_model(m); } };
+
+int alive(const char* who, const gprc_local_model* m) {
+  if (!m) return bad(who, "null model");
+  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  return 0;
+}
+
+// parameters and noise into the object; an ARD kernel's metric 1 / l_c to the device
+int store_params(const char* who, gprc_local_model* m, const double* params, int n_params, double noise) {
+  if (!params) return bad(who, "null input pointer (params)");
+  if (!(noise >= 0.0) || !std::isfinite(noise)) return bad(who, "noise must be finite and >= 0");
+  KernelSpec ks;
+  GPRC_TRY(make_spec(m->kernel, params, n_params, m->d, &ks));
+  if (is_ard(m->kernel)) {
+    std::vector<double> sc((size_t)m->d);
+    for (int64_t c = 0; c < m->d; ++c) sc[(size_t)c] = 1.0 / params[c];
+    GPRC_TRY(check_scale(who, sc.data(), m->d));
+    if (!m->scale.p) GPRC_TRY(m->scale.alloc(m->d));
+    GPRC_HIP(hipMemcpyAsync(m->scale.p, sc.data(), sizeof(double) * sc.size(), hipMemcpyHostToDevice, m->ctx->stream));
+    GPRC_HIP(hipStreamSynchronize(m->ctx->stream));   // sc leaves scope
+  }
+  m->params.assign(params, params + n_params);
+  m->noise = noise;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gprc_dev_knn(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const double* X_star, int64_t n_star, const double* scale, int64_t m, int* idx_out,
+                 double* dist_out, int64_t ld_out) {
+  const char* who = "dev_knn";
+  if (!ctx) return bad(who, "null context");
+  if (d < 1 || n < 1 || n_star < 0) return bad(who, "d < 1, n < 1 or n_star < 0");
+  if (n >= (int64_t(1) << 31)) return bad(who, "n >= 2^31: the neighbour indices are 32-bit");
+  if (m < 1 || m > n || m > GPRC_BATCH_MAX_N) return bad(who, "m = " + std::to_string(m) + " is outside 1 .. min(n, 128)");
+  if (ld_out < m) return bad(who, "ld_out < m");
+  if (n_star == 0) return 0;
+  if (!X || !X_star) return bad(who, "null input pointer (X, X_star)");
+  if (!idx_out) return bad(who, "null output pointer (idx_out)");
+  if (scale && is_device_ptr(scale)) return bad(who, "scale must be host memory");
+  if (scale) GPRC_TRY(check_scale(who, scale, d));
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  In xin, sc;
+  GPRC_TRY(xin.set(s, X, d * n));
+  if (scale) GPRC_TRY(sc.set(s, scale, d));
+  return knn_any(who, ctx, xin.dev, d, n, X_star, n_star, sc.dev, m, idx_out, dist_out, ld_out);
+}
+
+int gprc_lgpr_create(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n, const double* y, double noise,
+                     int64_t m, gprc_local_model** model_out) {
+  const char* who = "lgpr_create";
+  if (model_out) *model_out = nullptr;
+  if (!ctx) return bad(who, "null context");
+  GPRC_TRY(check_grad_kernel(who, kernel));
+  if (!model_out) return bad(who, "null output pointer (model_out)");
+  if (!X || !y) return bad(who, "null input pointer (X, y)");
+  if (d < 1 || n < 1) return bad(who, "d < 1 or n < 1");
+  if (n >= (int64_t(1) << 31)) return bad(who, "n >= 2^31: the neighbour indices are 32-bit");
+  if (m < 1) return bad(who, "m < 1");
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  std::unique_ptr<gprc_local_model, LocalModelFree> mod(new gprc_local_model);
+  mod->ctx = ctx;
+  mod->ctx_id = ctx->id;
+  mod->kernel = kernel;
+  mod->n = n;
+  mod->d = d;
+  mod->m = std::min<int64_t>(std::min<int64_t>(m, n), GPRC_BATCH_MAX_N);
+  GPRC_TRY(store_params(who, mod.get(), params, n_params, noise));
+  GPRC_TRY(mod->X.alloc(d * n));
+  GPRC_HIP(hipMemcpyAsync(mod->X.p, X, sizeof(double) * (size_t)(d * n), is_device_ptr(X) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  GPRC_TRY(mod->y.alloc(n));
+  GPRC_HIP(hipMemcpyAsync(mod->y.p, y, sizeof(double) * (size_t)n, is_device_ptr(y) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  *model_out = mod.release();
+  return 0;
+}
+
+int gprc_lgpr_set_params(gprc_local_model* m, const double* params, int n_params, double noise) {
+  const char* who = "lgpr_set_params";
+  GPRC_TRY(alive(who, m));
+  GPRC_TRY(use_device(m->ctx));
+  return store_params(who, m, params, n_params, noise);
+}
+
+int gprc_lgpr_neighbours(gprc_local_model* m, const double* X_star, int64_t n_star, int* idx_out, double* dist_out, int64_t ld_out) {
+  const char* who = "lgpr_neighbours";
+  GPRC_TRY(alive(who, m));
+  if (n_star < 0) return bad(who, "n_star < 0");
+  if (ld_out < m->m) return bad(who, "ld_out < m");
+  if (n_star == 0) return 0;
+  if (!X_star) return bad(who, "null input pointer (X_star)");
+  if (!idx_out) return bad(who, "null output pointer (idx_out)");
+  GPRC_TRY(use_device(m->ctx));
+  return knn_any(who, m->ctx, m->X.p, m->d, m->n, X_star, n_star, m->scale.p, m->m, idx_out, dist_out, ld_out);
+}
+
+int gprc_lgpr_predict(gprc_local_model* m, const double* X_star, int64_t n_star, double* mean_out, double* var_out, int* info_out) {
+  const char* who = "lgpr_predict";
+  GPRC_TRY(alive(who, m));
+  if (n_star < 0) return bad(who, "n_star < 0");
+  if (n_star == 0) return 0;
+  if (!X_star) return bad(who, "null input pointer (X_star)");
+  if (!mean_out) return bad(who, "null output pointer (mean_out)");
+  if (info_out && is_device_ptr(info_out)) return bad(who, "info_out must be host memory");
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const int64_t d = m->d, k = m->m;
+  const int n_params = (int)m->params.size();
+  In xs;
+  GPRC_TRY(xs.set(s, X_star, d * n_star));
+  Out mean, var;
+  GPRC_TRY(mean.set(mean_out, n_star));
+  if (var_out) GPRC_TRY(var.set(var_out, n_star));
+  const int64_t chunk = std::min<int64_t>(n_star, LGPR_CHUNK);
+  // what every chunk's models share, once: the parameter rows and the noises of the batched fit, its host outputs
+  std::vector<double> thetas((size_t)(chunk * n_params)), noises((size_t)chunk, m->noise), logp((size_t)chunk);
+  for (int64_t b = 0; b < chunk; ++b) std::copy(m->params.begin(), m->params.end(), thetas.begin() + b * n_params);
+  std::vector<int> info((size_t)chunk);
+  DevMem idx, Xg, yg;
+  GPRC_TRY(idx.alloc((chunk * k + 1) / 2));
+  GPRC_TRY(Xg.alloc(chunk * d * k));
+  GPRC_TRY(yg.alloc(chunk * k));
+  int* idx_dev = reinterpret_cast<int*>(idx.p);
+  for (int64_t j0 = 0; j0 < n_star; j0 += chunk) {
+    const int64_t B = std::min<int64_t>(chunk, n_star - j0);
+    const double* xs_c = xs.dev + j0 * d;
+    GPRC_TRY(knn_on_device(ctx, m->X.p, d, m->n, xs_c, B, m->scale.p, k, idx_dev, nullptr, k));
+    GPRC_TRY(launch_knn_gather(s, idx_dev, k, m->X.p, m->y.p, d, B, k, Xg.p, yg.p));
+    gprc_batch_model* fitted = nullptr;
+    GPRC_TRY(gprc_gpr_batch_fit(ctx, m->kernel, B, thetas.data(), n_params, n_params, noises.data(), Xg.p, d, k, d * k, yg.p, k, nullptr, &fitted,
+                                logp.data(), info.data()));
+    // one test point per model, straight into the outputs; a flagged model's point is NaN
+    const int rc = gprc_gpr_batch_predict(fitted, xs_c, 1, d, nullptr, mean.dev + j0, var_out ? var.dev + j0 : nullptr, 1);
+    gprc_batch_model_free(fitted);
+    GPRC_TRY(rc);
+    if (info_out) std::copy(info.begin(), info.begin() + B, info_out + j0);
+  }
+  GPRC_TRY(mean.finish(s));
+  if (var_out) GPRC_TRY(var.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gprc_lgpr_dims(const gprc_local_model* m, int64_t* n_out, int64_t* d_out, int64_t* m_out) {
+  if (!m) return bad("lgpr_dims", "null model");
+  if (n_out) *n_out = m->n;
+  if (d_out) *d_out = m->d;
+  if (m_out) *m_out = m->m;
+  return 0;
+}
+
+int gprc_lgpr_free(gprc_local_model* m) {
+  if (!m) return 0;
+  if (m->ctx && !ctx_alive(m->ctx, m->ctx_id)) {   // the context went first: its stream is gone (and was synchronised), its pool too
+    m->ctx = nullptr;
+    (void)hipDeviceSynchronize();
+  }
+  if (m->ctx && m->ctx->stream) (void)hipStreamSynchronize(m->ctx->stream);
+  free_local_model(m);
+  return 0;
+}
+
+}  // extern "C"

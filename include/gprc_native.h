@@ -248,6 +248,48 @@ GPRC_API int gprc_gpr_batch_loo(gprc_batch_model* model, double* mean_out, doubl
 GPRC_API int gprc_gpr_batch_get_alpha(gprc_batch_model* model, double* alpha_out);
 GPRC_API int gprc_batch_model_dims(const gprc_batch_model* model, int64_t* B_out, int64_t* d_out, int64_t* n_max_out);
 GPRC_API int gprc_batch_model_free(gprc_batch_model* model);
+/* Exact k-nearest-neighbours by brute force in float64 ("Local GPR"): for every test point j the m training points
+ * with the smallest key (dist2, index), lexicographic -- the lower index first among equal distances -- in ascending key order,
+ *   dist2(j, i) = sum_c ((x*_jc - x_ic) * s_c)^2,   c ascending, one fused multiply-add per term;  s_c = 1 without a scale.
+ * The difference is taken before the scaling: a test point that coincides with a training point has distance exactly 0.
+ *   X, X_star   host or device, d x n and d x n_star, one point per column;  n < 2^31, any d >= 1, n_star >= 0 (0: nothing is done)
+ *   scale       HOST, d values, finite and > 0, or NULL
+ *   m           1 <= m <= min(n, 128)
+ *   idx_out, dist_out   host or device (both of one kind), the result of point j at [j * ld_out + r], r < m; ld_out >= m; what lies
+ *               between m and ld_out is left as it was; dist_out may be NULL
+ * Indices and distance bits are a function of (X, X_star, scale, m) alone: not of n_star, a point's place in the call, the tiling, or
+ * host versus device pointers.  A distance that is NaN is never selected; a rank that no comparable candidate fills reports index -1
+ * and distance +inf.  n * n_star * d multiply-adds, no n x n_star memory.  GPRC_ERR_ARG: a null context, X, X_star or idx_out, d < 1,
+ * n < 1, n >= 2^31, m outside 1 .. min(n, 128), ld_out < m, a scale that is not finite and > 0 or not in host memory.
+ *
+ * The local GPR: every test point is predicted from the exact GP of its own m nearest training points (local kriging).
+ * gprc_lgpr_create copies X and y to the device once and factorises nothing; kernels: those of gprc_gpr_batch_logp_grad; m is clamped
+ * to min(m, n, 128).  The neighbours are those of gprc_dev_knn, for the ARD kernels with s_c = 1 / l_c from the parameters -- the
+ * points of largest prior correlation -- and Euclidean for the others.  gprc_lgpr_set_params swaps parameters and noise without
+ * another upload.  gprc_lgpr_predict: per chunk of at most 2048 test points the neighbour search, then gprc_gpr_batch_fit and
+ * gprc_gpr_batch_predict on one model per point, its points in neighbour order.
+ *   X_star              host or device, d x n_star
+ *   mean_out, var_out   host or device, n_star values; the LATENT variance, as gprc_gpr_batch_predict's; var_out may be NULL
+ *   info_out            HOST, n_star ints, may be NULL: 0, or the leading minor of point j's local model that is not positive definite;
+ *                       such a point's mean and variance are NaN, the call does not fail and the other points are unaffected
+ * A test point's bits depend on the model, the parameters and its own coordinates only: not on n_star, the chunk it falls into or its
+ * place.  MEMORY: d * n + n doubles held by the object; during a predict 128 KiB + (d + 2) m doubles per point of a chunk, at most 256 MiB
+ * + the slabs, from the context's pool.  gprc_lgpr_neighbours: gprc_dev_knn with the model's points, m and metric.
+ * GPRC_ERR_ARG: a null context, model or pointer (var_out, info_out, dist_out may be NULL), a kernel outside the eight, bad parameters or
+ * noise (gprc_gpr_batch_fit's rules), m < 1, n >= 2^31, ld_out < m, a model whose context has been destroyed.  gprc_lgpr_free accepts NULL
+ * and a model whose context went first; gprc_lgpr_dims: each output may be NULL. */
+GPRC_API int gprc_dev_knn(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const double* X_star, int64_t n_star, const double* scale,
+                          int64_t m, int* idx_out, double* dist_out, int64_t ld_out);
+typedef struct gprc_local_model gprc_local_model;
+GPRC_API int gprc_lgpr_create(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                              const double* y, double noise, int64_t m, gprc_local_model** model_out);
+GPRC_API int gprc_lgpr_set_params(gprc_local_model* model, const double* params, int n_params, double noise);
+GPRC_API int gprc_lgpr_predict(gprc_local_model* model, const double* X_star, int64_t n_star, double* mean_out, double* var_out,
+                               int* info_out);
+GPRC_API int gprc_lgpr_neighbours(gprc_local_model* model, const double* X_star, int64_t n_star, int* idx_out, double* dist_out,
+                                  int64_t ld_out);
+GPRC_API int gprc_lgpr_dims(const gprc_local_model* model, int64_t* n_out, int64_t* d_out, int64_t* m_out);
+GPRC_API int gprc_lgpr_free(gprc_local_model* model);
 /* Leave-one-out cross-validation of a fitted GPR model in closed form (Rasmussen & Williams 5.4.2; no reference counterpart).  With
  * K_y = K + noise * I, P = K_y^-1, alpha = P y and p_i = P_ii, the prediction of y_i from the other n - 1 observations is
  *   mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i,     logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log(2 pi),
