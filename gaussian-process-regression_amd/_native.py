@@ -287,33 +287,51 @@ def ptr(a) -> int:
     raise TypeError(f"cannot take the address of {type(a)!r}")
 
 
-class Context:
-    """gprc_ctx: one GPU + one HIP stream.  `stream` is a raw hipStream_t (int) or None."""
-
-    def __init__(self, device: int = 0, stream: int | None = None):
-        self._h = _vp()
-        check(lib().gprc_ctx_create(int(device), _vp(stream) if stream else None, C.byref(self._h)))
-        self.device = int(device)
+class Handle:
+    """The one owner of a native handle: a class that keeps a library object alive derives from this and names, as class attributes,
+    the attribute its `c_void_p` lives in (the library fills it through C.byref), the function that frees it, and what a use after
+    close() says.  It gets the guarded accessor `.handle`, an idempotent close(), the `with` form and a __del__ that never raises --
+    not even for an object whose constructor raised before the handle existed."""
+    _slot = "_model"
+    _free = "gprc_model_free"
+    _closed = "model already closed"
 
     @property
     def handle(self):
-        if not self._h:
-            raise GprcError(ERR_ARG, "context already destroyed")
-        return self._h
-
-    def synchronize(self):
-        check(lib().gprc_ctx_synchronize(self.handle))
+        h = getattr(self, self._slot, None)
+        if not h:
+            raise GprcError(ERR_ARG, self._closed)
+        return h
 
     def close(self):
-        if self._h:
-            lib().gprc_ctx_destroy(self._h)
-            self._h = _vp()
+        if getattr(self, self._slot, None):
+            getattr(lib(), self._free)(getattr(self, self._slot))
+            setattr(self, self._slot, _vp())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+class Context(Handle):
+    """gprc_ctx: one GPU + one HIP stream.  `stream` is a raw hipStream_t (int) or None."""
+    _slot, _free, _closed = "_h", "gprc_ctx_destroy", "context already destroyed"
+
+    def __init__(self, device: int = 0, stream: int | None = None):
+        self._h = _vp()
+        check(lib().gprc_ctx_create(int(device), _vp(stream) if stream else None, C.byref(self._h)))
+        self.device = int(device)
+
+    def synchronize(self):
+        check(lib().gprc_ctx_synchronize(self.handle))
 
 
 _default_ctx: dict[int, Context] = {}

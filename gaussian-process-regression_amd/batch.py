@@ -12,12 +12,12 @@ import importlib
 import numpy as np
 
 from . import _native as nat
-from .covfunc import as_points
+from .covfunc import as_points, pad_point_sets
 
 _fit = importlib.import_module(__package__ + ".fit")   # (the package's attribute `fit` is the function)
 
 
-class BatchGPR:
+class BatchGPR(nat.Handle):
     """B small GPR models, one per row of `thetas` (B x p, the order `dens` takes them; a vector is one model), fitted together.
     X, y: one data set shared by every model (d x n, n values), or lists of B data sets, which may differ in n (they are padded into
     one strided array; the padding is never read); noise: a scalar or B values; name: a kernel of `fit.grad_dict`.  At most 128
@@ -26,6 +26,7 @@ class BatchGPR:
     .logp[B], .info[B]: the log evidence and 0, or the leading minor that is not positive definite -- such a model does not raise,
     its logp, alpha and predictions are NaN; both are bit for bit `logp_grad_batch`'s.  .alpha[B, n_max] (read from the device when
     asked for, zero behind a model's points).  The object holds 128 KiB of device memory a model until .close() (or its collection)."""
+    _free, _closed = "gprc_batch_model_free", "the batch has been closed"
 
     def __init__(self, X, y, noise, name, thetas, ctx=None):
         func = _fit.grad_dict[name]
@@ -44,12 +45,6 @@ class BatchGPR:
         nat.check(nat.lib().gprc_gpr_batch_fit(self._ctx.handle, func.kernel_id, B, thetas.ctypes.data, p, p, noises.ctypes.data, Xb.ctypes.data, d,
                                                n_max, x_stride, yb.ctypes.data, y_stride, None if n_each is None else n_each.ctypes.data,
                                                C.byref(self._model), self.logp.ctypes.data, self.info.ctypes.data))
-
-    @property
-    def handle(self):
-        if not self._model:
-            raise nat.GprcError(nat.ERR_ARG, "the batch has been closed")
-        return self._model
 
     @property
     def alpha(self):
@@ -71,13 +66,8 @@ class BatchGPR:
         pts = [as_points(x, d, "X_star") for x in X_star]
         if any(q.shape[0] != d or q.shape[1] < 1 for q in pts):
             raise ValueError(who + ": every set of test points must be d x n* with n* >= 1")
-        ns_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
-        ns_max = int(ns_each.max())
-        xs_stride = d * ns_max
-        Xsb = np.zeros((B, xs_stride))
-        for b, q in enumerate(pts):
-            Xsb[b, :q.size] = q.ravel(order="F")
-        return False, Xsb, ns_max, xs_stride, ns_each
+        Xsb, ns_each, ns_max = pad_point_sets(pts)
+        return False, Xsb, ns_max, d * ns_max, ns_each
 
     def predict(self, X_star, var=True):
         """Posterior mean and latent variance k(x*, x*) - |L^-1 k*|^2 of every model.  X_star: a d x n* array of test points shared by
@@ -131,20 +121,3 @@ class BatchGPR:
         score = np.full(self.B, np.nan)
         nat.check(nat.lib().gprc_gpr_batch_loo(self.handle, None, None, None, self.n_max, score.ctypes.data))
         return score
-
-    def close(self):
-        if getattr(self, "_model", None):
-            nat.lib().gprc_batch_model_free(self._model)
-            self._model = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -16,7 +16,7 @@ import numpy as np
 from . import _native as nat
 
 __all__ = ["cov_func", "covariance_matrix", "constant", "linear", "polynomial", "sqrexp", "gammaexp",
-           "rationalquadratic", "sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard", "CovFunc", "KernelGeneric", "as_points"]
+           "rationalquadratic", "sqrexp_ard", "matern32", "matern52", "matern32_ard", "matern52_ard", "CovFunc", "KernelGeneric", "as_points", "as_test_points"]
 
 
 def as_points(X, d=None, what="X"):
@@ -38,6 +38,35 @@ def as_points(X, d=None, what="X"):
     elif X.ndim != 2:
         raise ValueError(f"{what} must be a vector or a d x n matrix")
     return np.asfortranarray(X)
+
+
+def as_d_points(P, d, what):
+    """`as_points` for points that must have d rows (test points, inducing points): a matrix with d rows, or a vector filled
+    column by column into d rows (R/GPRclass.R:157-159)."""
+    P = as_points(P, d=d, what=what) if np.ndim(P) <= 1 else as_points(P, what=what)
+    if P.shape[0] != d:
+        raise ValueError(f"{what} must have nrow(X) rows")
+    return P
+
+
+def as_test_points(X_star, d, what="X_star"):
+    """The d x n* test points of a model on d-dimensional inputs, checked as GPR$predict checks them (R/GPRclass.R:156-159).  Every
+    model's predict goes through here (GPR.add_data too, with what="X_new"); the caller applies whatever layout call it needs."""
+    Xs = np.asarray(X_star)
+    if Xs.dtype.kind not in "fiub" or Xs.size % d:
+        raise ValueError(f"is.numeric({what}), length({what}) %% nrow(self$X) == 0 are not all TRUE")  # :156
+    return as_d_points(Xs, d, what)
+
+
+def pad_point_sets(pts):
+    """B point sets (d x n_b each, n_b may differ) in one zero-filled strided array: (Pb[B, d * n_max], n_each[B], n_max), set b
+    column-major from Pb[b, 0] on; the padding behind it is never read.  What the batched entry points take."""
+    n_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
+    n_max = int(n_each.max())
+    Pb = np.zeros((len(pts), pts[0].shape[0] * n_max))
+    for b, q in enumerate(pts):
+        Pb[b, :q.size] = q.ravel(order="F")
+    return Pb, n_each, n_max
 
 
 class KernelGeneric:

@@ -6,14 +6,14 @@ What runs where
     gprc_gpr_log_marginal; the reference's O(n^4) `min(det(leading minors)) > 0` guard (:119) is the Cholesky's
     own positive-definiteness test;
   * the optimiser driver is host code, as in the reference.  R's `optim(method = "Brent")` is `optimize()`, Brent's
-    fmin; it is restated here (golden section + successive parabolic interpolation, tol = sqrt(.Machine$double.eps))
+    fmin; it is restated in optim.py (golden section + successive parabolic interpolation, tol = sqrt(.Machine$double.eps))
     so that the one-parameter kernels (sqrexp, constant, linear) and the polynomial degree loop follow the same
     iterates.  `optim_until_error` (R/fit.R:47-69) is kept: a failing evaluation yields the sentinel -10000.
   * the two-parameter kernels gammaexp / rationalquadratic go through `optim(method = "BFGS")` with the gradient
     `dens_deriv` (R/fit.R:126-139).  That gradient is reproduced AS WRITTEN, by the native gprc_fit_gradient: it
     inverts the noise-free K, ignores `noise`, applies `diag(.) %*%` where a trace is meant and binds the parameter
     vector in `deriv`'s argument order, which is the reverse of the kernels' own.  R's BFGS is `vmmin` (Nash's
-    variable-metric Algorithm 21); it is restated below.  Consequences that follow from the reference's code and are
+    variable-metric Algorithm 21); it is restated in optim.py.  Consequences that follow from the reference's code and are
     kept: gammaexp's gradient has a NaN component (0 * log 0 on the diagonal), vmmin then takes its "uphill" exit at
     once and fit() returns the start values (1, 1); a failing gradient (K not invertible) aborts optim and
     optim_until_error falls back to the best objective value seen so far.
@@ -29,6 +29,16 @@ mode search of GPC$new, then one contraction), `optimize_gpc` maximises it over 
 The sparse GPR has it too: `elbo_grad` is Titsias' collapsed bound and its exact gradient with respect to the kernel parameters, the
 noise and the inducing points (gprc_sgpr_elbo_grad: the fit's pass, a second pass and one contraction), `optimize_sparse` maximises it
 over log(theta), log(noise) and the inducing points themselves.
+What lives here, and what is shared (the next objective or optimiser uses these, it does not copy a neighbour):
+  * fit(), its optim_until_error wrappers, cov_dict and SENTINEL: the reference-faithful part;
+  * the objective wrappers dens, dens_deriv, logp_grad, loo_grad, logq_grad, elbo_grad: each is `_staged` (points, targets, context,
+    parameter pointers) and one native call;
+  * the optimisers optimize, optimize_multistart, optimize_sparse, optimize_iterative, optimize_gpc: each is a `_Front` (start values,
+    z = [log theta, log noise, ...] and back, the gradient cut to match, the result dict) around `_maximise_over_log`; how one point
+    of z is evaluated -- exp (`_from_log`), range check (`_in_range`), chain factor and one-entry cache (`_Evaluation`) -- is the same
+    code for the single optimisers and for every instance of optimize_multistart, which takes the first two for all the points of a
+    round at once (tests/test_optimizers_cpu.py pins their iterates);
+  * vmmin, vmmin_steps and brent_fmin are optim.py's, re-exported here under their old names.
 Parity status: unpinned (the reference holds no numeric expectations for fit(); tests/testthat/test-fit.R:12-17 only
 checks which kernel NAME wins); cross-checked against scipy's bounded Brent on the same native objective, and the
 BFGS branch against the same driver running on the CPU oracle's objective and gradient.
@@ -42,8 +52,9 @@ import sys
 import numpy as np
 
 from . import _native as nat
-from .covfunc import (CovFunc, as_points, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
+from .covfunc import (CovFunc, as_d_points, as_points, pad_point_sets, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic, sqrexp_ard, matern32, matern52,
                       matern32_ard, matern52_ard)
+from .optim import brent_fmin, vmmin, vmmin_steps
 
 __all__ = ["fit", "dens", "dens_deriv", "logp_grad", "logp_grad_batch", "loo_grad", "optimize", "optimize_multistart", "vmmin_steps", "logq_grad", "optimize_gpc", "elbo", "elbo_grad", "optimize_sparse",
            "cov_dict", "brent_fmin", "vmmin"]
@@ -60,17 +71,26 @@ cov_dict = {
 SENTINEL = -10000.0  # R/fit.R:50
 
 
+def _staged(X, y, v, ctx, check_y=None):
+    """What every objective wrapper stages before its one native call: (Xm, y, d, n, ctx, (p, pp, npar)) -- the points d x n, the
+    targets as float64, the context (the default one when none is given) and nat.params_array of the parameter vector v.
+    check_y: None -- the length of y is the native layer's to refuse; "size" / "vector": length(y) == ncol(X) (and, for "vector",
+    one dimension) is checked here, where the wrapper has always checked it."""
+    Xm = as_points(X)
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    d, n = Xm.shape
+    if check_y and (y.size != n or (check_y == "vector" and y.ndim != 1)):
+        raise ValueError("length(y) == ncol(X) is not TRUE")
+    return Xm, y, d, n, ctx or nat.default_context(), nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+
+
 def dens(X, y, noise, name, v, ctx=None):
     """dens(v) of R/fit.R:117-124 for kernel `name` with parameter vector v (in the generic's argument order).
     Raises nat.NotPositiveDefinite when K + noise*I is not positive definite (the reference's stopifnot / chol error).
     `name` may also be a kernel of grad_dict that is not in cov_dict: "sqrexp_ard", "matern32_ard", "matern52_ard" (v = one length
     scale per row of X), "matern32", "matern52" (v = the length scale)."""
     func = _kernel_by_name(name)
-    Xm = as_points(X)
-    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-    d, n = Xm.shape
-    ctx = ctx or nat.default_context()
-    _, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    Xm, y, d, n, ctx, (_, pp, npar) = _staged(X, y, v, ctx)
     out = C.c_double()
     nat.check(nat.lib().gprc_gpr_log_marginal(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data,
                                               float(noise), C.byref(out)))
@@ -81,11 +101,7 @@ def dens_deriv(X, y, name, v, ctx=None):
     """dens_deriv(v) of R/fit.R:126-139 (quirks included, see the module docstring) for kernel `name`.
     Raises nat.NotPositiveDefinite when the noise-free K cannot be inverted (the reference's solve(K) error)."""
     func = cov_dict[name][0]
-    Xm = as_points(X)
-    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-    d, n = Xm.shape
-    ctx = ctx or nat.default_context()
-    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    Xm, y, d, n, ctx, (p, pp, npar) = _staged(X, y, v, ctx)
     g = np.empty(p.size)
     nat.check(nat.lib().gprc_fit_gradient(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data,
                                           g.ctypes.data_as(C.POINTER(C.c_double))))
@@ -118,21 +134,22 @@ def _func_of(name, par):
     return CovFunc(func, {"l": np.array(par)} if _is_ard(name) else func.bind(par, {}))
 
 
+def _value_and_noise_grad(symbol, X, y, noise, name, v, ctx):
+    """logp_grad and loo_grad: the two entry points take and return the same things"""
+    func = grad_dict[name]
+    Xm, y, d, n, ctx, (p, pp, npar) = _staged(X, y, v, ctx)
+    g = np.empty(p.size + 1)
+    out = C.c_double()
+    nat.check(getattr(nat.lib(), symbol)(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
+                                         C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.value, g
+
+
 def logp_grad(X, y, noise, name, v, ctx=None):
     """(logp, grad) of GPR(X, y, noise, name(v)): the log marginal likelihood and its exact gradient, one native call
     (gprc_gpr_logp_grad).  `v` in the order `dens` takes it; grad has len(v) + 1 entries, d logp / d noise last
     (noise enters as K + noise * I).  Raises nat.NotPositiveDefinite when K + noise * I is not positive definite."""
-    func = grad_dict[name]
-    Xm = as_points(X)
-    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-    d, n = Xm.shape
-    ctx = ctx or nat.default_context()
-    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
-    g = np.empty(p.size + 1)
-    out = C.c_double()
-    nat.check(nat.lib().gprc_gpr_logp_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
-                                           C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double))))
-    return out.value, g
+    return _value_and_noise_grad("gprc_gpr_logp_grad", X, y, noise, name, v, ctx)
 
 
 def loo_grad(X, y, noise, name, v, ctx=None):
@@ -140,17 +157,7 @@ def loo_grad(X, y, noise, name, v, ctx=None):
     GPR(...).loo_score returns, and its exact gradient, one native call (gprc_gpr_loo_grad).  The twin of `logp_grad`: `v` in the order
     `dens` takes it; grad has len(v) + 1 entries, d loo / d noise last.  Raises nat.NotPositiveDefinite when K + noise * I is not
     positive definite."""
-    func = grad_dict[name]
-    Xm = as_points(X)
-    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-    d, n = Xm.shape
-    ctx = ctx or nat.default_context()
-    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
-    g = np.empty(p.size + 1)
-    out = C.c_double()
-    nat.check(nat.lib().gprc_gpr_loo_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(noise),
-                                          C.byref(out), g.ctypes.data_as(C.POINTER(C.c_double))))
-    return out.value, g
+    return _value_and_noise_grad("gprc_gpr_loo_grad", X, y, noise, name, v, ctx)
 
 
 def elbo(X, y, noise, k, Z, jitter=1e-6, ctx=None):
@@ -167,16 +174,8 @@ def elbo_grad(X, y, noise, name, v, Z, jitter=1e-6, with_Z=True, ctx=None):
     entries, d elbo / d noise last; dZ is d x m like Z, d elbo / d Z[c, j], or None when not with_Z (grad has the same bits either
     way).  Raises nat.NotPositiveDefinite when K_uu + jitter I or B is not positive definite."""
     func = grad_dict[name]
-    Xm = np.asfortranarray(as_points(X))
-    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-    d, n = Xm.shape
-    if y.ndim != 1 or y.size != n:
-        raise ValueError("length(y) == ncol(X) is not TRUE")
-    Zm = np.asfortranarray(as_points(Z, d=d, what="Z") if np.ndim(Z) <= 1 else as_points(Z, what="Z"))
-    if Zm.shape[0] != d:
-        raise ValueError("Z must have nrow(X) rows")
-    ctx = ctx or nat.default_context()
-    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    Xm, y, d, n, ctx, (p, pp, npar) = _staged(X, y, v, ctx, check_y="vector")
+    Zm = as_d_points(Z, d, "Z")
     g = np.empty(p.size + 1)
     dZ = np.empty(Zm.shape, order="F") if with_Z else None
     out = C.c_double()
@@ -194,13 +193,7 @@ def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):
     (not GPC's 1e-5) is what a gradient accurate to 1e-10 needs.  Raises GprcError (ERR_MAXITER) when it does not converge
     within max_iter (0: 1000) steps."""
     func = grad_dict[name]
-    Xm = as_points(X)
-    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-    d, n = Xm.shape
-    if y.size != n:
-        raise ValueError("length(y) == ncol(X) is not TRUE")
-    ctx = ctx or nat.default_context()
-    p, pp, npar = nat.params_array(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    Xm, y, d, n, ctx, (p, pp, npar) = _staged(X, y, v, ctx, check_y="size")
     g = np.empty(p.size)
     out = C.c_double()
     nat.check(nat.lib().gprc_gpc_logq_grad(ctx.handle, func.kernel_id, pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, float(epsilon),
@@ -208,35 +201,114 @@ def logq_grad(X, y, name, v, epsilon=1e-10, max_iter=0, ctx=None):
     return out.value, g
 
 
-def _maximise_over_log(z0, value_and_grad_theta, maxit, n_log=None):
-    """vmmin on z = log(theta) of a function to MAXIMISE: value_and_grad_theta(theta) -> (value, d value / d theta); the chain
-    rule d / dz = theta * d / dtheta; an evaluation that raises NotPositiveDefinite / ArithmeticError / a native iteration cap,
-    or whose exp(z) over- or underflows, is the sentinel -10000 (optim_until_error).  n_log: only the first n_log entries of z are
-    logarithms, the rest are the variables themselves (the inducing points of optimize_sparse; they must stay finite).  Returns
-    vmmin's tuple (z in the same mixed form)."""
-    last = {}   # vmmin asks for the gradient at the point whose value it has just accepted: one evaluation serves both
-    n_log = len(z0) if n_log is None else n_log
+def _from_log(z, n_log):
+    """z -- one vector, or a stack of them, one per row -- with its first n_log entries exponentiated: the one place where an
+    optimiser's vector leaves the log scale (an overflow is inf here; who evaluates there asks `_in_range`)"""
+    t = z.copy()
+    with np.errstate(over="ignore"):
+        t[..., :n_log] = np.exp(z[..., :n_log])
+    return t
 
-    def evaluate(z):
-        key = z.tobytes()
-        if last.get("key") != key:
-            t, chain = z.copy(), np.ones(z.size)
-            with np.errstate(over="ignore"):
-                t[:n_log] = np.exp(z[:n_log])
-            chain[:n_log] = t[:n_log]
-            if not (np.all(np.isfinite(t)) and np.all(t[:n_log] > 0)):
-                raise ArithmeticError("parameter out of range")
-            val, g = value_and_grad_theta(t)
-            last.update(key=key, val=float(val), grad=np.asarray(g, dtype=np.float64) * chain)
-        return last["val"], last["grad"]
+
+def _in_range(t, n_log):
+    """whether a point of _from_log (every row of a stack) can be evaluated: all finite, what came from a logarithm > 0"""
+    return np.all(np.isfinite(t), axis=-1) & np.all(t[..., :n_log] > 0, axis=-1)
+
+
+def _out_of_range():
+    return ArithmeticError("parameter out of range")
+
+
+class _Evaluation:
+    """The rule "evaluate a point of z" of every optimiser here, with its one-entry cache: vmmin asks for the gradient at the point
+    whose value it has just accepted, so one evaluation serves both.  z's first n_log entries are logarithms (the chain rule
+    d / dz = theta * d / dtheta), the rest the variables themselves.  A point that fails is never cached."""
+
+    def __init__(self, n_log):
+        self.n_log = n_log
+        self.key = self.val = self.grad = None
+
+    def hit(self, z):
+        return z.tobytes() == self.key
+
+    def store(self, key, t, val, grad_theta):
+        """what the objective returned at t = _from_log(z), key = z.tobytes() (z is the optimiser's working vector: taken before it moves)"""
+        chain = np.ones(t.size)
+        chain[:self.n_log] = t[:self.n_log]
+        self.key, self.val, self.grad = key, float(val), np.asarray(grad_theta, dtype=np.float64) * chain
+
+    def at(self, z, value_and_grad_theta):
+        """(value, d value / dz) at z, from the cache or from value_and_grad_theta(theta) -> (value, d value / d theta); ArithmeticError
+        when an exp(z) over- or underflows or an entry is not finite"""
+        if not self.hit(z):
+            key, t = z.tobytes(), _from_log(z, self.n_log)
+            if not _in_range(t, self.n_log):
+                raise _out_of_range()
+            self.store(key, t, *value_and_grad_theta(t))
+        return self.val, self.grad
+
+
+def _maximise_over_log(z0, value_and_grad_theta, maxit, n_log=None):
+    """vmmin on z = log(theta) of a function to MAXIMISE: value_and_grad_theta(theta) -> (value, d value / d theta), evaluated by the
+    rule of `_Evaluation`; an evaluation that raises NotPositiveDefinite / ArithmeticError / a native iteration cap, or whose exp(z)
+    over- or underflows, is the sentinel -10000 (optim_until_error).  n_log: only the first n_log entries of z are logarithms, the
+    rest are the variables themselves (the inducing points of optimize_sparse; they must stay finite).  Returns vmmin's tuple (z in
+    the same mixed form)."""
+    point = _Evaluation(len(z0) if n_log is None else n_log)
 
     def fn(z):
         try:
-            return -evaluate(z)[0]
+            return -point.at(z, value_and_grad_theta)[0]
         except (nat.NotPositiveDefinite, ArithmeticError):
             return -SENTINEL
 
-    return vmmin(z0, fn, lambda z: -evaluate(z)[1], maxit=maxit)
+    return vmmin(z0, fn, lambda z: -point.at(z, value_and_grad_theta)[1], maxit=maxit)
+
+
+class _Front:
+    """What the five optimisers share around vmmin: the start values (defaulted, checked), the vector z = [log(theta), log(noise) when
+    the noise is optimised, whatever else the caller appends] and its inverse, the gradient cut to match, and the result dict.
+    noise=None: the objective has none (optimize_gpc).  many: `start` is S x p, one row per start (optimize_multistart)."""
+
+    def __init__(self, who, name, d, start, noise=None, with_noise=False, many=False):
+        if start is None:
+            start = _default_start(name, d)
+        start = np.asarray(start, dtype=np.float64)
+        self.starts = np.atleast_2d(start) if many else np.atleast_1d(start).ravel()[None, :]
+        if len(self.starts) < 1 or not (np.all(np.isfinite(self.starts)) and np.all(self.starts > 0)):
+            raise ValueError(who + ": start values must be finite and > 0")
+        self.name, self.noise, self.with_noise = name, noise, with_noise
+        self.npar = self.starts.shape[1]
+        self.n_log = self.npar + (1 if with_noise else 0)
+
+    def pack(self, s=0, extra=None, log_noise=None):
+        """z0 of start s.  log_noise: the noise's logarithm when the caller has its own (optimize_sparse takes libm's, which differs from
+        numpy's in the last bit now and then: its iterates stay what they were)"""
+        if not self.with_noise:
+            z = np.log(self.starts[s])
+        elif log_noise is None:
+            z = np.log(np.concatenate([self.starts[s], [float(self.noise)]]))
+        else:
+            z = np.concatenate([np.log(self.starts[s]), [log_noise]])
+        return z if extra is None else np.concatenate([z, extra])
+
+    def split(self, t):
+        """(theta, noise) of a point on the natural scale; (thetas, noises) of a stack of points, one per row"""
+        if t.ndim == 1:
+            return t[:self.npar].copy(), float(t[self.npar]) if self.with_noise else float(self.noise)
+        return t[:, :self.npar].copy(), t[:, self.npar].copy() if self.with_noise else np.full(len(t), float(self.noise))
+
+    def grad(self, g):
+        """the objective's gradient (len(theta) + 1 entries, the noise last) without the noise's entry when the noise is fixed"""
+        g = np.asarray(g, dtype=np.float64)
+        return g if self.with_noise else g[:self.npar]
+
+    def result(self, vmmin_tuple, **more):
+        z, fmin, fncount, grcount, fail = vmmin_tuple
+        t = _from_log(z, self.n_log)
+        par = tuple(float(v) for v in t[:self.npar])
+        noise = {} if self.noise is None else {"noise": self.split(t)[1]}
+        return {"par": par, **noise, **more, "value": -fmin, "counts": (fncount, grcount), "convergence": fail, "func": _func_of(self.name, par)}
 
 
 def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, value_and_grad=None, ctx=None, objective="logp"):
@@ -252,32 +324,19 @@ def optimize(X, y, noise, name, start=None, *, optimize_noise=True, maxit=100, v
     `value_and_grad` hook replaces either."""
     if objective not in ("logp", "loo"):
         raise ValueError('optimize: objective must be "logp" or "loo"')
-    func = grad_dict[name]
+    func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient)
     Xm = as_points(X)
-    d = Xm.shape[0]
-    if start is None:
-        start = _default_start(name, d)
-    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
-    npar = theta0.size
-    with_noise = bool(optimize_noise) and noise > 0
-    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
-        raise ValueError("optimize: start values must be finite and > 0")
+    front = _Front("optimize", name, Xm.shape[0], start, noise, bool(optimize_noise) and noise > 0)
     if value_and_grad is None:
         ctx = ctx or nat.default_context()
         native = loo_grad if objective == "loo" else logp_grad
         value_and_grad = lambda theta, nz: native(Xm, y, nz, name, theta, ctx)   # noqa: E731
-    z0 = np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0)
 
     def vg(t):
-        val, g = value_and_grad(t[:npar].copy(), float(t[npar]) if with_noise else float(noise))
-        g = np.asarray(g, dtype=np.float64)
-        return val, (g if with_noise else g[:npar])
+        val, g = value_and_grad(*front.split(t))
+        return val, front.grad(g)
 
-    z, fmin, fncount, grcount, fail = _maximise_over_log(z0, vg, maxit)
-    t = np.exp(z)
-    par = tuple(float(v) for v in t[:npar])
-    return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
-            "convergence": fail, "func": _func_of(name, par)}
+    return front.result(_maximise_over_log(front.pack(), vg, maxit))
 
 
 BATCH_MAX_N = 128   # include/gprc_native.h GPRC_BATCH_MAX_N: the points of one batched model
@@ -299,16 +358,12 @@ def batch_layout(X, y, B, who="logp_grad_batch"):
         if len(X) != B or len(y) != B:
             raise ValueError("%s: one data set per row of thetas" % who)
         pts = [as_points(x) for x in X]
+        ys = [np.asarray(yy, dtype=np.float64).reshape(1, -1) for yy in y]
         d = pts[0].shape[0]
-        n_each = np.array([q.shape[1] for q in pts], dtype=np.int64)
-        n_max = int(n_each.max())
-        Xb, yb = np.zeros((B, d * n_max)), np.zeros((B, n_max))
-        for b, (q, yy) in enumerate(zip(pts, y)):
-            yy = np.asarray(yy, dtype=np.float64).ravel()
-            if q.shape[0] != d or yy.size != q.shape[1]:
-                raise ValueError("%s: every data set needs the same nrow(X) and length(y) == ncol(X)" % who)
-            Xb[b, :q.size] = q.ravel(order="F")
-            yb[b, :yy.size] = yy
+        if any(q.shape[0] != d or yy.size != q.shape[1] for q, yy in zip(pts, ys)):
+            raise ValueError("%s: every data set needs the same nrow(X) and length(y) == ncol(X)" % who)
+        Xb, n_each, n_max = pad_point_sets(pts)
+        yb = pad_point_sets(ys)[0]
         x_stride, y_stride = d * n_max, n_max
     if n_max > BATCH_MAX_N:
         raise ValueError("%s: at most %d points a model; logp_grad takes larger ones" % (who, BATCH_MAX_N))
@@ -358,19 +413,16 @@ def optimize_multistart(X, y, noise, name, starts=None, *, n_starts=8, rng=None,
         rng = rng if rng is not None else np.random.default_rng()
         extra = np.exp(rng.uniform(math.log(1.0 / 8.0), math.log(8.0), (max(int(n_starts) - 1, 0), base.size)))
         starts = np.vstack([base[None, :], base[None, :] * extra])
-    starts = np.atleast_2d(np.asarray(starts, dtype=np.float64))
-    S, npar = starts.shape
-    if S < 1 or not (np.all(np.isfinite(starts)) and np.all(starts > 0)):
-        raise ValueError("optimize_multistart: start values must be finite and > 0")
-    with_noise = bool(optimize_noise) and noise > 0
+    front = _Front("optimize_multistart", name, d, starts, noise, bool(optimize_noise) and noise > 0, many=True)
     if value_and_grad_batch is None:
         ctx = ctx or nat.default_context()
         value_and_grad_batch = lambda thetas, noises: logp_grad_batch(X, y, noises, name, thetas, ctx)   # noqa: E731
 
-    class _Instance:   # one vmmin with _maximise_over_log's cache: the last evaluated point, its value and chained gradient
-        def __init__(self, theta0):
-            self.steps = vmmin_steps(np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0), maxit)
-            self.key = self.val = self.grad = self.result = None
+    class _Instance:   # one vmmin and the _Evaluation that `optimize` would give it
+        def __init__(self, s):
+            self.steps = vmmin_steps(front.pack(s), maxit)
+            self.point = _Evaluation(front.n_log)
+            self.result = None
             self.first = True
             self.want = next(self.steps)
 
@@ -380,48 +432,45 @@ def optimize_multistart(X, y, noise, name, starts=None, *, n_starts=8, rng=None,
             except StopIteration as stop:
                 self.want, self.result = None, stop.value
 
+        def answer(self):
+            """the cached point's value or gradient, whichever the instance waits on"""
+            self.advance(-self.point.val if self.want[0] == "f" else -self.point.grad)
+
         def run_on_cache(self):
             """answers from the cache until the instance finishes or waits on a point that has to be evaluated"""
-            while self.want is not None and self.want[1].tobytes() == self.key:
-                self.advance(-self.val if self.want[0] == "f" else -self.grad)
+            while self.want is not None and self.point.hit(self.want[1]):
+                self.answer()
 
-    inst = [_Instance(starts[s]) for s in range(S)]
+        def failed(self, error):
+            """the sentinel; vmmin without a gradient to go on raises what `optimize` raises from its gradient call"""
+            if self.first or self.want[0] == "g":
+                raise error
+            self.advance(-SENTINEL)
+
+    inst = [_Instance(s) for s in range(len(front.starts))]
     while True:
         for it in inst:
             it.run_on_cache()
         live = [it for it in inst if it.want is not None]
         if not live:
             break
-        with np.errstate(over="ignore"):
-            T = np.array([np.exp(it.want[1]) for it in live])
-        in_range = np.all(np.isfinite(T), axis=1) & np.all(T > 0, axis=1)
-        rows = np.flatnonzero(in_range)
-        vals = grads = infos = None
+        T = _from_log(np.array([it.want[1] for it in live]), front.n_log)
+        rows = np.flatnonzero(_in_range(T, front.n_log))          # this round's one call: the points that can be evaluated
         if rows.size:
-            vals, grads, infos = value_and_grad_batch(T[rows, :npar].copy(), T[rows, npar].copy() if with_noise else np.full(rows.size, float(noise)))
-            grads = np.asarray(grads, dtype=np.float64)
+            vals, grads, infos = value_and_grad_batch(*front.split(T[rows]))
         where = {int(r): k for k, r in enumerate(rows)}
         for i, it in enumerate(live):
             k = where.get(i)
-            failed = k is None or int(infos[k]) > 0
-            if failed:
-                if it.first or it.want[0] == "g":   # vmmin has no gradient to go on: what `optimize` raises from its gradient call
-                    raise (ArithmeticError("parameter out of range") if k is None else nat.NotPositiveDefinite(int(infos[k])))
+            if k is None:
+                it.failed(_out_of_range())
+            elif int(infos[k]) > 0:
+                it.failed(nat.NotPositiveDefinite(int(infos[k])))
+            else:
+                it.point.store(it.want[1].tobytes(), T[i], vals[k], front.grad(grads[k]))
                 it.first = False
-                it.advance(-SENTINEL)
-                continue
-            g = grads[k] if with_noise else grads[k][:npar]
-            it.key, it.val, it.grad = it.want[1].tobytes(), float(vals[k]), g * T[i]
-            it.first = False
-            it.advance(-it.val if it.want[0] == "f" else -it.grad)
+                it.answer()
 
-    results = []
-    for it in inst:
-        z, fmin, fncount, grcount, fail = it.result
-        t = np.exp(z)
-        par = tuple(float(v) for v in t[:npar])
-        results.append({"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
-                        "convergence": fail, "func": _func_of(name, par)})
+    results = [front.result(it.result) for it in inst]
     best = int(np.argmax([r["value"] for r in results]))
     return dict(results[best], all=results, best_index=best)
 
@@ -437,44 +486,29 @@ def optimize_sparse(X, y, noise, name, Z, start=None, *, optimize_noise=True, op
     underflowing, an inducing point no longer finite) counts as the sentinel -10000, as in `optimize`.  Returns dict(par, noise, Z,
     value, counts, convergence, func): SparseGPR(X, y, r["noise"], r["func"], r["Z"], jitter) is the fitted model; convergence 0:
     converged, 1: maxit reached."""
-    func = grad_dict[name]
+    func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient, as `optimize`)
     Xm = as_points(X)
     d = Xm.shape[0]
-    Z0 = np.asfortranarray(as_points(Z, d=d, what="Z") if np.ndim(Z) <= 1 else as_points(Z, what="Z"))
-    if Z0.shape[0] != d:
-        raise ValueError("Z must have nrow(X) rows")
-    m = Z0.shape[1]
-    if start is None:
-        start = _default_start(name, d)
-    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
-    npar = theta0.size
-    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
-        raise ValueError("optimize_sparse: start values must be finite and > 0")
+    Z0 = as_d_points(Z, d, "Z")
+    front = _Front("optimize_sparse", name, d, start, noise, bool(optimize_noise))
     if not (noise > 0 and math.isfinite(noise)):
         raise ValueError("optimize_sparse: noise must be finite and > 0")
-    with_noise, with_Z = bool(optimize_noise), bool(optimize_Z)
+    with_Z = bool(optimize_Z)
     if value_and_grad is None:
         ctx = ctx or nat.default_context()
         value_and_grad = lambda theta, nz, Zc: elbo_grad(Xm, y, nz, name, theta, Zc, jitter, with_Z, ctx)   # noqa: E731
-    n_log = npar + (1 if with_noise else 0)
-    z0 = np.concatenate([np.log(theta0), [math.log(noise)] if with_noise else [], Z0.ravel(order="F") if with_Z else []])
 
-    def split(t):
-        return (t[:npar].copy(), float(t[npar]) if with_noise else float(noise),
-                np.asfortranarray(t[n_log:].reshape((d, m), order="F")) if with_Z else Z0)
+    def Z_of(t):   # the inducing points lie behind the logarithms, column-major, as Z lies in memory
+        return np.asfortranarray(t[front.n_log:].reshape(Z0.shape, order="F")) if with_Z else Z0
 
     def vg(t):
-        val, g, dZ = value_and_grad(*split(t))
-        g = np.asarray(g, dtype=np.float64)
-        return val, np.concatenate([g if with_noise else g[:npar], np.asarray(dZ, dtype=np.float64).ravel(order="F") if with_Z else []])
+        val, g, dZ = value_and_grad(*front.split(t), Z_of(t))
+        g = front.grad(g)
+        return val, np.concatenate([g, np.asarray(dZ, dtype=np.float64).ravel(order="F")]) if with_Z else g
 
-    z, fmin, fncount, grcount, fail = _maximise_over_log(z0, vg, maxit, n_log)
-    t = z.copy()
-    t[:n_log] = np.exp(z[:n_log])
-    par_v, noise_v, Z_v = split(t)
-    par = tuple(float(v) for v in par_v)
-    return {"par": par, "noise": noise_v, "Z": Z_v, "value": -fmin, "counts": (fncount, grcount), "convergence": fail,
-            "func": _func_of(name, par)}
+    z0 = front.pack(extra=Z0.ravel(order="F") if with_Z else None, log_noise=math.log(noise))
+    vm = _maximise_over_log(z0, vg, maxit, front.n_log)
+    return front.result(vm, Z=Z_of(vm[0]))
 
 
 def iter_logp_grad(X, y, noise, name, v, *, g1, g2, tol=1e-8, max_iter=1000, precond_rank=128, ctx=None):
@@ -506,15 +540,9 @@ def optimize_iterative(X, y, noise, name, start=None, *, n_probes=31, rng=None, 
     func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient, as `optimize`)
     Xm = as_points(X)
     d, n = Xm.shape
-    if start is None:
-        start = _default_start(name, d)
-    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
-    npar = theta0.size
-    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
-        raise ValueError("optimize_iterative: start values must be finite and > 0")
+    front = _Front("optimize_iterative", name, d, start, noise, bool(optimize_noise))
     if not (noise > 0 and math.isfinite(noise)):
         raise ValueError("optimize_iterative: noise must be finite and > 0")
-    with_noise = bool(optimize_noise)
     if value_and_grad is None:
         if int(n_probes) < 2:
             raise ValueError("optimize_iterative: n_probes >= 2 is not TRUE")
@@ -532,20 +560,16 @@ def optimize_iterative(X, y, noise, name, start=None, *, n_probes=31, rng=None, 
                 raise
             return val, g, se
 
-    z0 = np.log(np.concatenate([theta0, [float(noise)]]) if with_noise else theta0)
     se_of = {}
 
     def vg(t):
-        out = value_and_grad(t[:npar].copy(), float(t[npar]) if with_noise else float(noise))
-        g = np.asarray(out[1], dtype=np.float64)
+        out = value_and_grad(*front.split(t))
+        g = front.grad(out[1])
         se_of[float(out[0])] = float(out[2]) if len(out) > 2 else float("nan")   # by value: vmmin returns the value it accepted
-        return out[0], (g if with_noise else g[:npar])
+        return out[0], g
 
-    z, fmin, fncount, grcount, fail = _maximise_over_log(z0, vg, maxit)
-    t = np.exp(z)
-    par = tuple(float(v) for v in t[:npar])
-    return {"par": par, "noise": float(t[npar]) if with_noise else float(noise), "value": -fmin, "counts": (fncount, grcount),
-            "convergence": fail, "func": _func_of(name, par), "se": se_of.get(-fmin, float("nan"))}
+    r = front.result(_maximise_over_log(front.pack(), vg, maxit))
+    return dict(r, se=se_of.get(r["value"], float("nan")))
 
 
 def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_grad=None, ctx=None):
@@ -555,14 +579,9 @@ def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_
     replaces the native objective `logq_grad`.  An evaluation that fails (a mode search that does not converge, a parameter
     over- or underflowing) counts as the sentinel -10000.  Returns dict(par, value, counts, convergence, func):
     GPC(X, y, r["func"], reference_stop=False) is the fitted classifier; convergence 0: converged, 1: maxit reached."""
-    func = grad_dict[name]
+    func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient, as `optimize`)
     Xm = as_points(X)
-    d = Xm.shape[0]
-    if start is None:
-        start = _default_start(name, d)
-    theta0 = np.atleast_1d(np.asarray(start, dtype=np.float64)).ravel()
-    if not (np.all(np.isfinite(theta0)) and np.all(theta0 > 0)):
-        raise ValueError("optimize_gpc: start values must be finite and > 0")
+    front = _Front("optimize_gpc", name, Xm.shape[0], start)
     if value_and_grad is None:
         ctx = ctx or nat.default_context()
 
@@ -574,192 +593,7 @@ def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_
                     raise ArithmeticError("the mode search did not converge") from e
                 raise
 
-    z, fmin, fncount, grcount, fail = _maximise_over_log(np.log(theta0), lambda t: value_and_grad(t.copy()), maxit)
-    par = tuple(float(v) for v in np.exp(z))
-    return {"par": par, "value": -fmin, "counts": (fncount, grcount), "convergence": fail,
-            "func": _func_of(name, par)}
-
-
-def vmmin(b0, fn, gr, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):
-    """R's optim(method = "BFGS") core: Nash's variable-metric minimiser (Compact Numerical Methods, Algorithm 21)
-    with R's constants (stepredn 0.2, acctol 1e-4, reltest 10).  Minimises fn; returns (par, value, fncount, grcount,
-    fail).  The algorithm is `vmmin_steps`; this is its driver for one instance: every value it asks for is fn's, every
-    gradient gr's."""
-    steps = vmmin_steps(b0, maxit, abstol, reltol)
-    try:
-        kind, point = next(steps)
-        while True:
-            kind, point = steps.send(fn(point) if kind == "f" else gr(point))
-    except StopIteration as stop:
-        return stop.value
-
-
-def vmmin_steps(b0, maxit=100, abstol=-math.inf, reltol=math.sqrt(np.finfo(float).eps)):
-    """`vmmin` as a generator, so that several instances can run in lockstep on one batched objective (`optimize_multistart`): it
-    yields ("f", point) when it wants the value at `point` and ("g", point) when it wants the gradient there, is sent the answer, and
-    returns vmmin's tuple (par, value, fncount, grcount, fail) as the value of its StopIteration.  `point` is the instance's own
-    working vector: it is valid until the answer is sent.  Restated from the published algorithm; control flow details that matter
-    for the reference's behaviour: a non-finite initial value is an error (ArithmeticError, raised into whoever drives the
-    generator); a search direction that is not downhill (including a NaN gradient projection) resets B once and then terminates."""
-    stepredn, acctol, reltest = 0.2, 1e-4, 10.0
-    b = np.array(b0, dtype=np.float64)
-    n = b.size
-    if maxit <= 0:
-        return b, float((yield ("f", b))), 0, 0, 0
-    f = float((yield ("f", b)))
-    if not math.isfinite(f):
-        raise ArithmeticError("initial value in 'vmmin' is not finite")
-    fmin = f
-    funcount = gradcount = 1
-    g = np.array((yield ("g", b)), dtype=np.float64)
-    it = 1
-    ilast = gradcount
-    B = np.zeros((n, n))
-    count = 0
-    while True:
-        if ilast == gradcount:
-            B = np.eye(n)
-        X = b.copy()
-        c = g.copy()
-        t = np.empty(n)
-        gradproj = 0.0
-        for i in range(n):
-            sacc = 0.0
-            for j in range(i + 1):
-                sacc -= B[i, j] * g[j]
-            for j in range(i + 1, n):
-                sacc -= B[j, i] * g[j]
-            t[i] = sacc
-            gradproj += sacc * g[i]
-        if gradproj < 0.0:  # downhill
-            steplength = 1.0
-            accpoint = False
-            while True:
-                count = 0
-                for i in range(n):
-                    b[i] = X[i] + steplength * t[i]
-                    if reltest + X[i] == reltest + b[i]:
-                        count += 1
-                if count < n:
-                    f = float((yield ("f", b)))
-                    funcount += 1
-                    accpoint = math.isfinite(f) and f <= fmin + gradproj * steplength * acctol
-                    if not accpoint:
-                        steplength *= stepredn
-                if count == n or accpoint:
-                    break
-            enough = f > abstol and abs(f - fmin) > reltol * (abs(fmin) + reltol)
-            if not enough:
-                count = n
-                fmin = f
-            if count < n:  # making progress
-                fmin = f
-                g = np.array((yield ("g", b)), dtype=np.float64)
-                gradcount += 1
-                it += 1
-                D1 = 0.0
-                for i in range(n):
-                    t[i] = steplength * t[i]
-                    c[i] = g[i] - c[i]
-                    D1 += t[i] * c[i]
-                if D1 > 0:
-                    D2 = 0.0
-                    for i in range(n):
-                        sacc = 0.0
-                        for j in range(i + 1):
-                            sacc += B[i, j] * c[j]
-                        for j in range(i + 1, n):
-                            sacc += B[j, i] * c[j]
-                        X[i] = sacc
-                        D2 += sacc * c[i]
-                    D2 = 1.0 + D2 / D1
-                    for i in range(n):
-                        for j in range(i + 1):
-                            B[i, j] += (D2 * t[i] * t[j] - X[i] * t[j] - t[i] * X[j]) / D1
-                else:
-                    ilast = gradcount
-            else:  # no progress
-                if ilast < gradcount:
-                    count = 0
-                    ilast = gradcount
-        else:  # uphill search direction (or NaN): reset B, or stop if it has just been reset
-            count = 0
-            if ilast == gradcount:
-                count = n
-            else:
-                ilast = gradcount
-        if it >= maxit:
-            break
-        if gradcount - ilast > 2 * n:
-            ilast = gradcount  # periodic restart
-        if not (count != n or ilast != gradcount):
-            break
-    return b, fmin, funcount, gradcount, (0 if it < maxit else 1)
-
-
-def brent_fmin(f, ax, bx, tol):
-    """Brent's fmin, the algorithm behind R's optimize() / optim(method = "Brent"): minimum of f on [ax, bx].
-    Restated from the published algorithm (Brent 1973, ch. 5; netlib fmin)."""
-    c = (3.0 - math.sqrt(5.0)) * 0.5
-    eps = math.sqrt(np.finfo(float).eps)
-    a, b = ax, bx
-    v = a + c * (b - a)
-    w = x = v
-    d = e = 0.0
-    fx = f(x)
-    fv = fw = fx
-    tol3 = tol / 3.0
-    while True:
-        xm = (a + b) * 0.5
-        tol1 = eps * abs(x) + tol3
-        t2 = tol1 * 2.0
-        if abs(x - xm) <= t2 - (b - a) * 0.5:
-            break
-        p = q = r = 0.0
-        if abs(e) > tol1:  # fit a parabola
-            r = (x - w) * (fx - fv)
-            q = (x - v) * (fx - fw)
-            p = (x - v) * q - (x - w) * r
-            q = (q - r) * 2.0
-            if q > 0.0:
-                p = -p
-            else:
-                q = -q
-            r = e
-            e = d
-        if abs(p) >= abs(q * 0.5 * r) or p <= q * (a - x) or p >= q * (b - x):  # golden-section step
-            e = (b - x) if x < xm else (a - x)
-            d = c * e
-        else:  # parabolic-interpolation step
-            d = p / q
-            u = x + d
-            if u - a < t2 or b - u < t2:  # f must not be evaluated too close to a or b
-                d = tol1 if x < xm else -tol1
-        if abs(d) >= tol1:  # f must not be evaluated too close to x
-            u = x + d
-        elif d > 0.0:
-            u = x + tol1
-        else:
-            u = x - tol1
-        fu = f(u)
-        if fu <= fx:
-            if u < x:
-                b = x
-            else:
-                a = x
-            v, w, x = w, x, u
-            fv, fw, fx = fw, fx, fu
-        else:
-            if u < x:
-                a = u
-            else:
-                b = u
-            if fu <= fw or w == x:
-                v, fv = w, fw
-                w, fw = u, fu
-            elif fu <= fv or v == x or v == w:
-                v, fv = u, fu
-    return x
+    return front.result(_maximise_over_log(front.pack(), lambda t: value_and_grad(t.copy()), maxit))
 
 
 def _optim_brent_until_error(f, lower, upper):

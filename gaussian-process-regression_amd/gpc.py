@@ -45,7 +45,7 @@ def class_probability_quadpack(fs_bar, Vfs):
     return out
 
 
-class GPC:
+class GPC(nat.Handle):
     """GPC$new(X, y, k, epsilon = 1e-5)  --  R/GPCclass.R:66."""
 
     def __init__(self, X, y, k, epsilon=1e-5, *, ctx=None, max_iter=0, reference_stop=True):
@@ -84,12 +84,17 @@ class GPC:
     def new(cls, *args, **kwargs):
         return cls(*args, **kwargs)
 
-    def predict_latent(self, X_star):
-        """fs_bar and Vfs of R/GPCclass.R:109-115 (the GPU part of predict_class)."""
-        Xs = np.asarray(X_star, dtype=np.float64)
-        Xs = as_points(Xs) if Xs.ndim <= 1 else as_points(Xs)                                    # :109
+    def _points(self, X_star):
+        """The reference gives a bare vector the dimensions 1 x length (:109), not GPR$predict's column-by-column fill, so a vector stands
+        for test points only when nrow(X) is 1: not covfunc.as_test_points, because the reference's two classes differ here."""
+        Xs = as_points(np.asarray(X_star, dtype=np.float64))                                     # :109
         if Xs.shape[0] != self._X.shape[0]:
             raise ValueError("X_star must have nrow(X) rows")
+        return Xs
+
+    def predict_latent(self, X_star):
+        """fs_bar and Vfs of R/GPCclass.R:109-115 (the GPU part of predict_class)."""
+        Xs = self._points(X_star)
         ns = Xs.shape[1]
         fs, vf = np.empty(ns), np.empty(ns)
         nat.check(nat.lib().gprc_gpc_predict_latent(self._model, Xs.ctypes.data, ns, fs.ctypes.data, vf.ctypes.data))
@@ -110,10 +115,7 @@ class GPC:
         the environment variable GPRC_GPC_INTEGRATOR).  The R binding keeps integrate() (r/R/native.R)."""
         integrator = integrator or DEFAULT_INTEGRATOR
         if integrator == "native":
-            Xs = np.asarray(X_star, dtype=np.float64)
-            Xs = as_points(Xs)
-            if Xs.shape[0] != self._X.shape[0]:
-                raise ValueError("X_star must have nrow(X) rows")
+            Xs = self._points(X_star)
             ns = Xs.shape[1]
             out = np.empty(ns)
             nat.check(nat.lib().gprc_gpc_predict_class(self._model, Xs.ctypes.data, ns, out.ctypes.data))
@@ -137,14 +139,3 @@ class GPC:
     f_hat = _ReadOnly("f_hat", lambda s: s._f_hat)
     L = _ReadOnly("L", _get_L)
     logq = _ReadOnly("logq", lambda s: s._logq)
-
-    def close(self):
-        if getattr(self, "_model", None):
-            nat.lib().gprc_model_free(self._model)
-            self._model = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 
 from . import _native as nat
-from .covfunc import (as_points, cov_func, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic,
+from .covfunc import (as_points, as_test_points, cov_func, constant, linear, polynomial, sqrexp, gammaexp, rationalquadratic,
                       sqrexp_ard, matern32, matern52, matern32_ard, matern52_ard, require_tagged)
 
 __all__ = ["GPR", "GPR_constant", "GPR_linear", "GPR_polynomial", "GPR_sqrexp", "GPR_gammaexp", "GPR_rationalquadratic",
@@ -42,7 +42,7 @@ class _ReadOnly:
         raise AttributeError(f"`${self.name}` is read only")
 
 
-class GPR:
+class GPR(nat.Handle):
     """GPR$new(X, y, noise = 0, k, cov_names)  --  R/GPRclass.R:127-128."""
 
     def __init__(self, X, y, noise=0, k=None, cov_names=None, *, ctx=None, devices=None, rccl=False, exchange="broadcast",
@@ -109,13 +109,7 @@ class GPR:
     def predict(self, X_star, pointwise_var=True):
         """GPR$predict(X_star, pointwise_var = TRUE)  --  R/GPRclass.R:155-170.
         pointwise: n* x 2 array cbind(mean, variance); otherwise [mean (n* x 1), covariance (n* x n*)]."""
-        d = self._X.shape[0]
-        Xs = np.asarray(X_star)
-        if Xs.dtype.kind not in "fiub" or Xs.size % d:
-            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")  # :156
-        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
-        if Xs.shape[0] != d:
-            raise ValueError("X_star must have nrow(X) rows")
+        Xs = as_test_points(X_star, self._X.shape[0])                                        # :156-159
         ns = Xs.shape[1]
         mean = np.empty(ns)
         if pointwise_var:
@@ -137,12 +131,7 @@ class GPR:
         rationalquadratic, matern32, matern52, matern32_ard, matern52_ard; gammaexp at a test point equal to a training point takes that
         pair's contribution as 0 (the Matern kernels need no such convention: that pair's term is an exact 0)."""
         d = self._X.shape[0]
-        Xs = np.asarray(X_star)
-        if Xs.dtype.kind not in "fiub" or Xs.size % d:
-            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")  # as :156
-        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
-        if Xs.shape[0] != d:
-            raise ValueError("X_star must have nrow(X) rows")
+        Xs = as_test_points(X_star, d)
         if self._mmodel is not None:
             raise ValueError("predict_grad: a model fitted over several devices has no prediction gradients; refit GPR on one device")
         ns = Xs.shape[1]
@@ -177,11 +166,7 @@ class GPR:
         Xa = np.asarray(X_new)
         if Xa.dtype.kind not in "fiub" or not _is_numeric_vector(y_new):
             raise TypeError("is.numeric(X_new), is.vector(y_new), is.numeric(y_new) are not all TRUE")     # as :129
-        if Xa.size % d:
-            raise ValueError("is.numeric(X_new), length(X_new) %% nrow(self$X) == 0 are not all TRUE")     # as :156
-        Xn = as_points(Xa, d=d, what="X_new") if Xa.ndim <= 1 else as_points(Xa, what="X_new")
-        if Xn.shape[0] != d:
-            raise ValueError("X_new must have nrow(X) rows")
+        Xn = as_test_points(Xa, d, "X_new")                                                              # as :156-159
         y_new = np.ascontiguousarray(np.asarray(y_new, dtype=np.float64))
         if y_new.size != Xn.shape[1]:
             raise ValueError("length(y_new) == ncol(X_new) is not TRUE")                                  # as :133
@@ -287,15 +272,7 @@ class GPR:
             nat.lib().gprc_mgpu_model_free(self._mmodel)     # owns the per-rank replicas, including the borrowed self._model
             self._mmodel = None
             self._model = C.c_void_p()
-        if getattr(self, "_model", None):
-            nat.lib().gprc_model_free(self._model)
-            self._model = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()                                      # a model of its own: gprc_model_free
 
 
 _mgpu_cache = {}

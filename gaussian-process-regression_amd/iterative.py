@@ -22,7 +22,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _native as nat
-from .covfunc import as_points, require_tagged
+from .covfunc import as_points, as_test_points, require_tagged
 
 __all__ = ["IterativeGPR", "SolveStats", "EvidenceEstimate"]
 
@@ -43,7 +43,7 @@ class EvidenceEstimate(NamedTuple):
     terms: np.ndarray           # the T quadrature terms q_s, E q_s = log det K_y - log det P
 
 
-class IterativeGPR:
+class IterativeGPR(nat.Handle):
     """IterativeGPR(X, y, noise, k, tol=1e-8, max_iter=1000, precond_rank=128): X d x n (one point per column), y of length n, noise > 0
     the variance, k a cov_func() of a stationary gprc kernel.  A column of a solve stops at |r| <= tol |b|; a loop that reaches max_iter
     raises GprcError (ERR_MAXITER).  precond_rank = 0 runs without a preconditioner; at most 1024."""
@@ -67,20 +67,8 @@ class IterativeGPR:
         nat.check(nat.lib().gprc_igpr_stats(self._model, C.byref(it), C.byref(rec), C.byref(true), C.byref(rank)))
         self._alpha, self._stats = alpha, SolveStats(it.value, rec.value, true.value, rank.value)
 
-    def _handle(self):
-        if not self._model:
-            raise nat.GprcError(nat.ERR_ARG, "model already closed")
-        return self._model
-
     def _points(self, X_star):
-        d = self._X.shape[0]
-        Xs = np.asarray(X_star)
-        if Xs.dtype.kind not in "fiub" or Xs.size % d:
-            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")
-        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
-        if Xs.shape[0] != d:
-            raise ValueError("X_star must have nrow(X) rows")
-        return np.asfortranarray(Xs)
+        return np.asfortranarray(as_test_points(X_star, self._X.shape[0]))
 
     def predict(self, X_star, pointwise_var=True):
         """The n* x 2 array cbind(mean, variance) as GPR.predict returns it (the latent variance); pointwise_var=False: the mean alone, of
@@ -89,7 +77,7 @@ class IterativeGPR:
         ns = Xs.shape[1]
         mean = np.empty(ns)
         var = np.empty(ns) if pointwise_var else None
-        nat.check(nat.lib().gprc_igpr_predict(self._handle(), Xs.ctypes.data, ns, mean.ctypes.data, var.ctypes.data if pointwise_var else None))
+        nat.check(nat.lib().gprc_igpr_predict(self.handle, Xs.ctypes.data, ns, mean.ctypes.data, var.ctypes.data if pointwise_var else None))
         return np.column_stack([mean, var]) if pointwise_var else mean
 
     def solve(self, B, with_stats=False):
@@ -101,7 +89,7 @@ class IterativeGPR:
         S = Bm.shape[1]
         out = np.empty((n, S), order="F")
         iters, res = (C.c_int * S)(), np.empty(S)
-        nat.check(nat.lib().gprc_igpr_solve(self._handle(), Bm.ctypes.data, n, S, out.ctypes.data, n, iters, res.ctypes.data_as(C.POINTER(C.c_double))))
+        nat.check(nat.lib().gprc_igpr_solve(self.handle, Bm.ctypes.data, n, S, out.ctypes.data, n, iters, res.ctypes.data_as(C.POINTER(C.c_double))))
         out = out[:, 0] if vector else out
         return (out, np.array(iters[:]), res) if with_stats else out
 
@@ -127,7 +115,7 @@ class IterativeGPR:
         g1, g2, T = self._normals(g1, g2)
         n = self._X.shape[1]
         Z = np.empty((n, T), order="F")
-        nat.check(nat.lib().gprc_igpr_probes(self._handle(), g1.ctypes.data if g1.size else None, max(g1.shape[0], 1), g2.ctypes.data, n, T,
+        nat.check(nat.lib().gprc_igpr_probes(self.handle, g1.ctypes.data if g1.size else None, max(g1.shape[0], 1), g2.ctypes.data, n, T,
                                              Z.ctypes.data, n))
         return Z
 
@@ -145,7 +133,7 @@ class IterativeGPR:
         g1, g2, T = self._normals(g1, g2)
         value, se = C.c_double(), C.c_double(float("nan"))
         grad, terms = np.empty(len(self._k.native_params(self._X.shape[0])) + 1), np.empty(T)
-        nat.check(nat.lib().gprc_igpr_logp_grad(self._handle(), g1.ctypes.data if g1.size else None, max(g1.shape[0], 1), g2.ctypes.data, n, T,
+        nat.check(nat.lib().gprc_igpr_logp_grad(self.handle, g1.ctypes.data if g1.size else None, max(g1.shape[0], 1), g2.ctypes.data, n, T,
                                                 C.byref(value), C.byref(se) if T >= 2 else None, grad.ctypes.data, terms.ctypes.data))
         return EvidenceEstimate(value.value, se.value, grad, terms)
 
@@ -167,7 +155,7 @@ class IterativeGPR:
         phase = np.ascontiguousarray(np.asarray(phase, dtype=np.float64).reshape(D))
         w = np.asfortranarray(np.asarray(w, dtype=np.float64).reshape(D, S))
         e = np.asfortranarray(np.asarray(e, dtype=np.float64).reshape(n, S))
-        return SamplePaths(self._handle(), d, nu, phase, w, e)
+        return SamplePaths(self.handle, d, nu, phase, w, e)
 
     def thompson_batch(self, q, lower, upper, n_features=1024, n_starts=16, rng=None, **kw):
         """GPR.thompson_batch: the d x q arg-maxima of q posterior sample paths over the box [lower, upper]"""
@@ -181,20 +169,3 @@ class IterativeGPR:
     noise = property(lambda self: self._noise)
     alpha = property(lambda self: self._alpha, doc="K_y^-1 y")
     stats = property(lambda self: self._stats, doc="SolveStats of the fit's solve")
-
-    def close(self):
-        if getattr(self, "_model", None):
-            nat.lib().gprc_model_free(self._model)
-            self._model = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as nat
-from .covfunc import as_points, require_tagged
+from .covfunc import as_points, as_test_points, require_tagged
 
 __all__ = ["LocalGPR", "knn", "MAX_NEIGHBOURS", "BATCHED_KERNELS"]
 
@@ -56,10 +56,11 @@ def knn(X, X_star, m, scale=None, ctx=None):
     return idx, dist
 
 
-class LocalGPR:
+class LocalGPR(nat.Handle):
     """LocalGPR(X, y, noise, k, m=64): X d x n (one point per column), y of length n, noise >= 0 the variance, k a cov_func() of a kernel
     with a batched small-model path, m the number of neighbours a test point is conditioned on (1 .. 128; clamped to n).  The object
     holds X and y on the device until .close() (or its collection); nothing is factorised before predict."""
+    _free = "gprc_lgpr_free"
 
     def __init__(self, X, y, noise, k, m=64, ctx=None):
         m = _check_m(m, "LocalGPR")
@@ -88,25 +89,13 @@ class LocalGPR:
         k.native_params(d)   # the parameter count against d
         return k
 
-    def _handle(self):
-        if not self._model:
-            raise nat.GprcError(nat.ERR_ARG, "model already closed")
-        return self._model
-
     def _points(self, X_star):
-        d = self._X.shape[0]
-        Xs = np.asarray(X_star)
-        if Xs.dtype.kind not in "fiub" or Xs.size % d:
-            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")
-        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
-        if Xs.shape[0] != d:
-            raise ValueError("X_star must have nrow(X) rows")
-        return np.asfortranarray(Xs)
+        return np.asfortranarray(as_test_points(X_star, self._X.shape[0]))
 
     def predict(self, X_star, pointwise_var=True):
         """The n* x 2 array cbind(mean, variance) as GPR.predict returns it (the latent variance); pointwise_var=False: the mean alone, of
         length n*.  A test point whose local model is not positive definite is NaN and has .info > 0; the call does not raise for it."""
-        handle = self._handle()
+        handle = self.handle
         Xs = self._points(X_star)
         ns = Xs.shape[1]
         mean = np.empty(ns)
@@ -119,7 +108,7 @@ class LocalGPR:
 
     def neighbours(self, X_star):
         """(idx[n*, m], dist2[n*, m]) of the test points in the model's metric, the order the local models take their points in"""
-        handle = self._handle()
+        handle = self.handle
         Xs = self._points(X_star)
         ns, m = Xs.shape[1], self._m
         idx, dist = np.empty((ns, m), dtype=np.intc), np.empty((ns, m))
@@ -132,7 +121,7 @@ class LocalGPR:
         if k.gprc_kernel[0] != self._k.gprc_kernel[0]:
             raise ValueError("LocalGPR.set_params: the kernel cannot change, only its parameters")
         _, pp, npar = nat.params_array(k.native_params(self._X.shape[0]))
-        nat.check(nat.lib().gprc_lgpr_set_params(self._handle(), pp, npar, float(noise)))
+        nat.check(nat.lib().gprc_lgpr_set_params(self.handle, pp, npar, float(noise)))
         self._k, self._noise = k, float(noise)
 
     X = property(lambda self: self._X)
@@ -141,20 +130,3 @@ class LocalGPR:
     noise = property(lambda self: self._noise)
     m = property(lambda self: self._m, doc="neighbours per test point, min(m, n)")
     info = property(lambda self: self._info, doc="per test point of the last predict: 0, or the minor of its local model that is not positive definite")
-
-    def close(self):
-        if getattr(self, "_model", None):
-            nat.lib().gprc_lgpr_free(self._model)
-            self._model = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -15,6 +15,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _native as nat
+from .covfunc import as_test_points
 
 __all__ = ["multivariate_normal", "expand_range", "mvn_factor", "sym_eigen", "spectral_frequencies", "SamplePaths", "PathMaxima", "maximize_paths"]
 
@@ -236,12 +237,13 @@ def maximize_paths(eval_grad, lower, upper, n_paths, *, n_starts=16, max_iter=20
     return PathMaxima(np.asfortranarray(x[:, best]), f[best].copy(), np.asfortranarray(x), f, pg, n_evals)
 
 
-class SamplePaths:
+class SamplePaths(nat.Handle):
     """Posterior sample paths of a fitted GPR (GPR.sample_paths; gprc_gpr_paths_*): n_paths functions that can be evaluated at any points,
     again and again.  They describe the posterior at creation and stay valid after GPR.add_data or GPR.close.  `paths(X_star)` returns
     the n* x n_paths array of their values; `paths_grad(X_star)` the values and their gradients with respect to the points;
     `maximize(lower, upper)` every path's maximiser over a box (maximize_paths); `.weights` the n x n_paths matrix U of the update term;
     `.close()` releases the device memory (also a context manager)."""
+    _slot, _free, _closed = "_h", "gprc_gpr_paths_free", "sample paths already closed"
 
     def __init__(self, model_handle, d, nu, phase, w, e):
         self._h = C.c_void_p()
@@ -251,38 +253,22 @@ class SamplePaths:
                                                   C.byref(self._h)))
         self.n, self.n_features, self.n_paths = e.shape[0], D, S
 
-    def _handle(self):
-        if not self._h:
-            raise nat.GprcError(nat.ERR_ARG, "sample paths already closed")
-        return self._h
-
     def paths(self, X_star):
         """f_s(X_star[, i]) as an n* x n_paths array; X_star as GPR.predict takes it"""
-        Xs = self._points(X_star)
+        Xs = as_test_points(X_star, self._d)
         ns = Xs.shape[1]
         out = np.empty((ns, self.n_paths), order="F")
-        nat.check(nat.lib().gprc_gpr_paths_eval(self._handle(), Xs.ctypes.data, ns, out.ctypes.data, ns))
+        nat.check(nat.lib().gprc_gpr_paths_eval(self.handle, Xs.ctypes.data, ns, out.ctypes.data, ns))
         return out
-
-    def _points(self, X_star):
-        from .covfunc import as_points
-        d = self._d
-        Xs = np.asarray(X_star)
-        if Xs.dtype.kind not in "fiub" or Xs.size % d:
-            raise ValueError("is.numeric(X_star), length(X_star) %% nrow(self$X) == 0 are not all TRUE")
-        Xs = as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star")
-        if Xs.shape[0] != d:
-            raise ValueError("X_star must have nrow(X) rows")
-        return Xs
 
     def paths_grad(self, X_star):
         """(F, dF): the values f_s(X_star[, i]) as `paths` returns them (the same bits), n* x n_paths, and their gradients with respect
         to the point, dF[i, s, c] = d f_s / d x_c, n* x n_paths x d; both in Fortran order (gprc_gpr_paths_eval_grad)"""
-        Xs = self._points(X_star)
+        Xs = as_test_points(X_star, self._d)
         ns = Xs.shape[1]
         F = np.empty((ns, self.n_paths), order="F")
         dF = np.empty((ns, self.n_paths, self._d), order="F")
-        nat.check(nat.lib().gprc_gpr_paths_eval_grad(self._handle(), Xs.ctypes.data, ns, F.ctypes.data, ns, dF.ctypes.data, ns))
+        nat.check(nat.lib().gprc_gpr_paths_eval_grad(self.handle, Xs.ctypes.data, ns, F.ctypes.data, ns, dF.ctypes.data, ns))
         return F, dF
 
     def maximize(self, lower, upper, **kw):
@@ -292,22 +278,5 @@ class SamplePaths:
     @property
     def weights(self):
         U = np.empty((self.n, self.n_paths), order="F")
-        nat.check(nat.lib().gprc_gpr_paths_get_weights(self._handle(), U.ctypes.data))
+        nat.check(nat.lib().gprc_gpr_paths_get_weights(self.handle, U.ctypes.data))
         return U
-
-    def close(self):
-        if getattr(self, "_h", None):
-            nat.lib().gprc_gpr_paths_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as nat
-from .covfunc import as_points, require_tagged
+from .covfunc import as_d_points, as_points, require_tagged
 
 __all__ = ["SparseGPR", "select_inducing", "elbo"]
 
@@ -43,12 +43,8 @@ def _checked(X, y, noise, k, Z, jitter, who):
     y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
     if y.ndim != 1 or y.size != Xm.shape[1]:
         raise ValueError("length(y) == ncol(X) is not TRUE")
-    d = Xm.shape[0]
-    Zm = np.asfortranarray(as_points(Z, d=d, what="Z") if np.ndim(Z) <= 1 else as_points(Z, what="Z"))
-    if Zm.shape[0] != d:
-        raise ValueError("Z must have nrow(X) rows")
     k = require_tagged(k, who)
-    return Xm, y, float(noise), k, Zm, float(jitter)
+    return Xm, y, float(noise), k, as_d_points(Z, Xm.shape[0], "Z"), float(jitter)
 
 
 def elbo(X, y, noise, k, Z, jitter=1e-6, ctx=None, with_trace=False):
@@ -64,7 +60,7 @@ def elbo(X, y, noise, k, Z, jitter=1e-6, ctx=None, with_trace=False):
     return (e.value, t.value) if with_trace else e.value
 
 
-class SparseGPR:
+class SparseGPR(nat.Handle):
     """SparseGPR(X, y, noise, k, Z, jitter=1e-6): X d x n (one point per column), y of length n, noise > 0 the variance, k a
     cov_func() of any gprc kernel, Z d x m inducing points (select_inducing picks columns of X).  The model keeps Z, not X or y."""
 
@@ -83,30 +79,14 @@ class SparseGPR:
 
     def predict(self, X_star):
         """(mean, var) at the columns of X_star: two arrays of length n*; var is the latent variance (add `noise` for an observation)."""
-        if not self._model:
-            raise nat.GprcError(nat.ERR_ARG, "model already closed")
-        d = self._Z.shape[0]
-        Xs = np.asarray(X_star)
-        Xs = np.asfortranarray(as_points(Xs, d=d, what="X_star") if Xs.ndim <= 1 else as_points(Xs, what="X_star"))
-        if Xs.shape[0] != d:
-            raise ValueError("X_star must have nrow(X) rows")
+        handle = self.handle
+        Xs = as_d_points(np.asarray(X_star), self._Z.shape[0], "X_star")
         ns = Xs.shape[1]
         mean, var = np.empty(ns), np.empty(ns)
-        nat.check(nat.lib().gprc_sgpr_predict(self._model, Xs.ctypes.data, ns, mean.ctypes.data, var.ctypes.data))
+        nat.check(nat.lib().gprc_sgpr_predict(handle, Xs.ctypes.data, ns, mean.ctypes.data, var.ctypes.data))
         return mean, var
 
     elbo = property(lambda self: self._elbo, doc="the collapsed bound, <= log p(y)")
     trace = property(lambda self: self._trace, doc="sum_i k(x_i,x_i) - |v_i|^2: what the inducing points do not explain")
     Z = property(lambda self: self._Z, doc="the inducing points, d x m")
     noise = property(lambda self: self._noise)
-
-    def close(self):
-        if self._model:
-            nat.lib().gprc_model_free(self._model)
-            self._model = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
