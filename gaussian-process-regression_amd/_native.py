@@ -77,6 +77,10 @@ PROTOTYPES = {
     "gprc_lgpr_neighbours": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64]),
     "gprc_lgpr_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_lgpr_free": (C.c_int, [_vp]),
+    "gprc_dev_knn_before": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64]),
+    "gprc_lgpr_vecchia_prepare": (C.c_int, [_vp, _i64]),
+    "gprc_lgpr_vecchia_logp_grad": (C.c_int, [_vp, _dp, C.c_int, C.c_double, C.POINTER(C.c_double), _vp, _vp, C.POINTER(_i64)]),
+    "gprc_lgpr_vecchia_neighbours": (C.c_int, [_vp, _vp, _i64]),
     "gprc_gpr_loo": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "gprc_gpr_loo_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, C.POINTER(C.c_double), _dp]),
     "gprc_gpr_predict": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp]),

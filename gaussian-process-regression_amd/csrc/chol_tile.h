@@ -125,6 +125,7 @@ __device__ __forceinline__ void diag16_sweep(double4_t& A, double4_t& V, double 
   (diag16_pivot<J>(A, V, rinvs, lcol, bad, q, r), ...);
 }
 
+template <int LDD = BLD>   // the leading dimension of D (kernels_vecchia.hip factors images narrower than the 128-wide block)
 __device__ __forceinline__ void diag16(double* D, double* Wd, double* wdiag, int* info, int col) {
   const int l = threadIdx.x & 63, r = l & 15, q = l >> 4;
   double4_t A, V;
@@ -133,7 +134,7 @@ __device__ __forceinline__ void diag16(double* D, double* Wd, double* wdiag, int
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int x = q + 4 * rr;
-    A[rr] = (x >= r) ? D[x + r * BLD] : D[r + x * BLD];   // the upper triangle mirrors the lower one
+    A[rr] = (x >= r) ? D[x + r * LDD] : D[r + x * LDD];   // the upper triangle mirrors the lower one
     V[rr] = (x == r) ? 1.0 : 0.0;
   }
   diag16_sweep(A, V, rinvs, lcol, bad, q, r, std::make_integer_sequence<int, 16>{});
@@ -144,12 +145,12 @@ __device__ __forceinline__ void diag16(double* D, double* Wd, double* wdiag, int
     if (r == x) {                                    // the pivot of row x is still where it was read (later updates add l_x l_y with l_x = 0)
       double ljj, rinv;
       sqrt_rsqrt(A[rr], ljj, rinv);
-      D[x + x * BLD] = ljj;
+      D[x + x * LDD] = ljj;
     }
-    if (r > x) D[r + x * BLD] = lcol[rr];            // column x of L: lane row q = x % 4 kept it
+    if (r > x) D[r + x * LDD] = lcol[rr];            // column x of L: lane row q = x % 4 kept it
     const double w = (r <= x) ? V[rr] * rinvs[rr] : 0.0;
     Wd[x + r * 16] = w;
-    if (r < x) D[r + x * BLD] = w;                    // strict lower part of the inverse, transposed into the upper triangle
+    if (r < x) D[r + x * LDD] = w;                    // strict lower part of the inverse, transposed into the upper triangle
     if (r == x) wdiag[x] = w;
   }
 }

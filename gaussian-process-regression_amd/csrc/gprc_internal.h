@@ -313,9 +313,46 @@ void knn_split(int64_t n, int64_t ns, int cus, int* parts, int64_t* part_len);
 size_t knn_workspace_doubles(int64_t ns, int m, int parts);
 int launch_knn(hipStream_t s, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, const double* scale, int m, int* idx, double* dist,
                int64_t ld, int parts, int64_t part_len, double* work);
+// The predecessor-constrained search (gprc_dev_knn_before): query j < count is column first + j of X itself and its candidates are the
+// columns i < first + j only; ranks that no candidate fills report -1 and +inf.  Same key, tie rule, layout, split and merge; the split
+// is knn_split(first + count, count, ...).
+int launch_knn_before(hipStream_t s, const double* X, int64_t d, int64_t first, int64_t count, const double* scale, int m, int* idx, double* dist, int64_t ld,
+                      int parts, int64_t part_len, double* work);
 // the neighbours as the slabs gprc_gpr_batch_fit reads: Xg + j d m the m points of query j (point-major, in idx's order), yg + j m their
 // targets; an index < 0 (an empty rank) gives NaN
 int launch_knn_gather(hipStream_t s, const int* idx, int64_t ld, const double* X, const double* y, int64_t d, int64_t ns, int64_t m, double* Xg, double* yg);
+
+// ---- launchers (kernels_vecchia.hip: the conditionals of the Vecchia likelihood) -------------------
+// One conditional log p(y_i | y_N(i)) per workgroup, `count` <= GPRC_VECCHIA_CHUNK points i0 .. i0 + count - 1 per launch, i0 a multiple of
+// 256.  All DEVICE memory: X (d x n, point-major), y (n), nbr (n rows of m ranks, pitch m: the neighbours of gprc_dev_knn_before, the first
+// rank of -1 ends the model; m = 0: not read), ks (make_deriv_spec of the caller's spec), and per point j = i - i0 of the launch
+//   out + j out_stride   cond_i, then (want_grad) the n_params sums WITHOUT the factors that do not depend on the pair -- the host halves
+//                        them after the sum over points and applies cross_grad_finish -- and sum_r G_rr;  out_stride = n_params + 2
+//   info + j             0, or the first non-positive pivot, 1-based: cond_i and the sums of such a point are NaN
+// launch_vecchia_reduce: row g of grp (out_stride + 1 doubles) = the columns of the points [256 g, 256 g + 256) of the launch added in a
+// fixed order (want_grad: all of them, else the first alone) and, last, the number of flagged points among them; cond (may be null) + j
+// gets cond_i.  Kernels: those of with_gradient_kernel.
+struct VecchiaArgs {
+  const double* X;
+  const double* y;
+  const int* nbr;
+  const KernelSpec* ks;
+  double* out;
+  int* info;
+  int64_t d, i0;
+  double noise;
+  int m, n_params, out_stride, want_grad;
+};
+struct VecchiaReduceArgs {
+  const double* out;
+  const int* info;
+  double* grp;
+  double* cond;
+  int64_t count;
+  int out_stride, want_grad;
+};
+int launch_vecchia(hipStream_t s, int kernel, const VecchiaArgs& a, int64_t count);
+int launch_vecchia_reduce(hipStream_t s, const VecchiaReduceArgs& a);
 
 // ---- launchers (kernels_sgrad.hip) -------------------------------------------------------------
 // the sparse bound gradient's contraction over G (rows_pad x cols_pad, column-major, pitch ld; rows_pad % 128 == 0, cols_pad % 64 == 0),

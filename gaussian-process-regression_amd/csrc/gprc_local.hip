@@ -3,6 +3,10 @@
 // slabs of the batched small models, then gprc_gpr_batch_fit and gprc_gpr_batch_predict (gprc_batch.hip) on device pointers -- one
 // model per test point, one test point per model.  Nothing here factorises; the training set lives on the device once, in the object.
 // A model, and so a test point, does not look at any other: its bits do not depend on n*, on the chunk it falls into or on its place.
+// The Vecchia likelihood ("Vecchia likelihood"): gprc_dev_knn_before, and on the same object gprc_lgpr_vecchia_prepare
+// (the conditioning sets, searched once and kept as n x m_cond indices), gprc_lgpr_vecchia_logp_grad (launches of kernels_vecchia.hip over
+// chunks of GPRC_VECCHIA_CHUNK points, the groups' rows added in order in long double, 1/2 and cross_grad_finish once) and
+// gprc_lgpr_vecchia_neighbours.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -25,6 +29,8 @@ struct gprc_local_model {
   DevMem X;       // d x n
   DevMem y;       // n
   DevMem scale;   // d doubles, 1 / l_c: the search metric of an ARD kernel (not allocated otherwise: Euclidean)
+  DevMem nbr;     // gprc_lgpr_vecchia_prepare: n rows of m_cond 32-bit indices, the conditioning sets, frozen until the next prepare
+  int64_t m_cond = -1;   // -1: no prepare yet; 0: n = 1, nothing to keep
 };
 
 namespace {
@@ -64,6 +70,19 @@ int knn_on_device(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const do
   return launch_knn(ctx->stream, X, d, n, Xs, ns, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
 }
 
+// the predecessor-constrained search on device pointers, asynchronous: queries first .. first + count - 1, candidates below each
+int knn_before_on_device(gprc_ctx* ctx, const double* X, int64_t d, int64_t first, int64_t count, const double* scale, int64_t m, int* idx, double* dist,
+                         int64_t ld) {
+  int cus = 0;
+  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  int parts = 1;
+  int64_t part_len = 0;
+  knn_split(first + count, count, cus, &parts, &part_len);
+  DevMem work;
+  if (parts > 1) GPRC_TRY(work.alloc((int64_t)knn_workspace_doubles(count, (int)m, parts)));
+  return launch_knn_before(ctx->stream, X, d, first, count, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
+}
+
 int check_scale(const char* who, const double* scale, int64_t d) {
   for (int64_t c = 0; c < d; ++c)
     if (!(scale[c] > 0.0) || !std::isfinite(scale[c])) return bad(who, "scale[" + std::to_string(c) + "] must be finite and > 0");
@@ -95,7 +114,7 @@ void free_local_model(gprc_local_model* m) {
   if (!m) return;
   if (m->ctx) (void)hipSetDevice(m->ctx->device);
   else                                   // the context went first: the buffers go straight back to the driver
-    for (DevMem* q : {&m->X, &m->y, &m->scale}) q->owner = nullptr;
+    for (DevMem* q : {&m->X, &m->y, &m->scale, &m->nbr}) q->owner = nullptr;
   delete m;
 }
 struct LocalModelFree { void operator()(gprc_local_model* m) const { free_local_model(m); } };
@@ -244,6 +263,150 @@ int gprc_lgpr_predict(gprc_local_model* m, const double* X_star, int64_t n_star,
   GPRC_TRY(mean.finish(s));
   if (var_out) GPRC_TRY(var.finish(s));
   GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gprc_dev_knn_before(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, int64_t first, int64_t count, const double* scale, int64_t m, int* idx_out,
+                        double* dist_out, int64_t ld_out) {
+  const char* who = "dev_knn_before";
+  if (!ctx) return bad(who, "null context");
+  if (d < 1 || n < 1) return bad(who, "d < 1 or n < 1");
+  if (n >= (int64_t(1) << 31)) return bad(who, "n >= 2^31: the neighbour indices are 32-bit");
+  if (m < 1 || m > GPRC_BATCH_MAX_N) return bad(who, "m = " + std::to_string(m) + " is outside 1 .. 128");
+  if (first < 0 || count < 0 || first > n || count > n - first) return bad(who, "the window [first, first + count) is outside 0 .. n");
+  if (ld_out < m) return bad(who, "ld_out < m");
+  if (count == 0) return 0;
+  if (!X) return bad(who, "null input pointer (X)");
+  if (!idx_out) return bad(who, "null output pointer (idx_out)");
+  if (scale && is_device_ptr(scale)) return bad(who, "scale must be host memory");
+  if (scale) GPRC_TRY(check_scale(who, scale, d));
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  In xin, sc;
+  GPRC_TRY(xin.set(s, X, d * (first + count)));   // no column from first + count on is a candidate or a query
+  if (scale) GPRC_TRY(sc.set(s, scale, d));
+  IntOut idx;
+  GPRC_TRY(idx.set(idx_out, ld_out, count, m));
+  Out dist;
+  if (dist_out) {
+    if (is_device_ptr(dist_out) != (idx.host == nullptr)) return bad(who, "idx_out and dist_out must both be host or both be device memory");
+    if (idx.host) GPRC_TRY(dist.set(dist_out, ld_out, m, count));
+    else dist.dev = dist_out;
+  }
+  GPRC_TRY(knn_before_on_device(ctx, xin.dev, d, first, count, sc.dev, m, idx.dev, dist.dev, idx.ld));
+  GPRC_TRY(idx.finish(s));
+  if (dist_out) GPRC_TRY(dist.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gprc_lgpr_vecchia_prepare(gprc_local_model* m, int64_t m_cond) {
+  const char* who = "lgpr_vecchia_prepare";
+  GPRC_TRY(alive(who, m));
+  if (m_cond < 1 || m_cond > GPRC_BATCH_MAX_N - 1) return bad(who, "m_cond = " + std::to_string(m_cond) + " is outside 1 .. 127");
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  const int64_t mc = std::min<int64_t>(m_cond, m->n - 1);
+  GPRC_HIP(hipStreamSynchronize(ctx->stream));
+  if (m->nbr.p) {   // a second prepare replaces the first
+    pool_release(m->nbr.owner, m->nbr.p, m->nbr.bytes);
+    m->nbr.p = nullptr;
+    m->nbr.bytes = 0;
+  }
+  m->m_cond = -1;
+  if (mc > 0) {
+    GPRC_TRY(m->nbr.alloc((m->n * mc + 1) / 2));
+    GPRC_TRY(knn_before_on_device(ctx, m->X.p, m->d, 0, m->n, m->scale.p, mc, reinterpret_cast<int*>(m->nbr.p), nullptr, mc));
+    GPRC_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  m->m_cond = mc;
+  return 0;
+}
+
+int gprc_lgpr_vecchia_neighbours(gprc_local_model* m, int* idx_out, int64_t ld_out) {
+  const char* who = "lgpr_vecchia_neighbours";
+  GPRC_TRY(alive(who, m));
+  if (m->m_cond < 0) return bad(who, "no gprc_lgpr_vecchia_prepare yet");
+  if (ld_out < m->m_cond) return bad(who, "ld_out < m_cond");
+  if (m->m_cond == 0) return 0;
+  if (!idx_out) return bad(who, "null output pointer (idx_out)");
+  GPRC_TRY(use_device(m->ctx));
+  GPRC_HIP(hipMemcpy2DAsync(idx_out, sizeof(int) * (size_t)ld_out, m->nbr.p, sizeof(int) * (size_t)m->m_cond, sizeof(int) * (size_t)m->m_cond, (size_t)m->n,
+                            is_device_ptr(idx_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, m->ctx->stream));
+  GPRC_HIP(hipStreamSynchronize(m->ctx->stream));
+  return 0;
+}
+
+int gprc_lgpr_vecchia_logp_grad(gprc_local_model* m, const double* params, int n_params, double noise, double* logp_out, double* grad_out, double* cond_out,
+                                int64_t* flagged_out) {
+  const char* who = "lgpr_vecchia_logp_grad";
+  GPRC_TRY(alive(who, m));
+  if (!params) return bad(who, "null input pointer (params)");
+  if (!logp_out) return bad(who, "null output pointer (logp_out)");
+  if (!(noise >= 0.0) || !std::isfinite(noise)) return bad(who, "noise must be finite and >= 0");
+  if (m->m_cond < 0) return bad(who, "no gprc_lgpr_vecchia_prepare yet");
+  if (grad_out && is_device_ptr(grad_out)) return bad(who, "grad_out must be host memory");
+  KernelSpec ks;
+  GPRC_TRY(make_spec(m->kernel, params, n_params, m->d, &ks));
+  if (is_ard(m->kernel))
+    for (int k = 0; k < n_params; ++k)
+      if (!(1.0 / params[k] > 0.0) || !std::isfinite(1.0 / params[k])) return bad(who, "length scale " + std::to_string(k) + " must be finite and > 0");
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const int64_t n = m->n;
+  const bool want_grad = grad_out != nullptr;
+  const int stride = n_params + 2, grp_stride = stride + 1;
+  const int64_t chunk = std::min<int64_t>(n, GPRC_VECCHIA_CHUNK), groups = (n + 255) / 256;
+  static_assert(GPRC_VECCHIA_CHUNK % 256 == 0, "launches start at multiples of 256: the groups are those of the global index");
+  const KernelSpec dspec = make_deriv_spec(ks);
+  DevMem spec_dev, out, info, grp;
+  GPRC_TRY(spec_dev.alloc((int64_t)((sizeof(KernelSpec) + 7) / 8)));
+  GPRC_TRY(out.alloc(chunk * stride));
+  GPRC_TRY(info.alloc((chunk + 1) / 2));
+  GPRC_TRY(grp.alloc(groups * grp_stride));
+  Out cond;
+  if (cond_out) GPRC_TRY(cond.set(cond_out, n));
+  GPRC_HIP(hipMemcpyAsync(spec_dev.p, &dspec, sizeof(KernelSpec), hipMemcpyHostToDevice, s));
+  VecchiaArgs a{m->X.p, m->y.p, reinterpret_cast<const int*>(m->nbr.p), reinterpret_cast<const KernelSpec*>(spec_dev.p), out.p, reinterpret_cast<int*>(info.p),
+                m->d, 0, noise, (int)m->m_cond, n_params, stride, want_grad ? 1 : 0};
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    const int64_t count = std::min<int64_t>(chunk, n - i0);
+    a.i0 = i0;
+    GPRC_TRY(launch_vecchia(s, m->kernel, a, count));
+    VecchiaReduceArgs r{out.p, reinterpret_cast<const int*>(info.p), grp.p + (i0 / 256) * grp_stride, cond_out ? cond.dev + i0 : nullptr, count, stride,
+                        want_grad ? 1 : 0};
+    GPRC_TRY(launch_vecchia_reduce(s, r));
+  }
+  std::vector<double> hgrp((size_t)(groups * grp_stride));
+  GPRC_HIP(hipMemcpyAsync(hgrp.data(), grp.p, sizeof(double) * hgrp.size(), hipMemcpyDeviceToHost, s));   // waits for dspec's upload too
+  if (cond_out) GPRC_TRY(cond.finish(s));
+  GPRC_HIP(hipStreamSynchronize(s));
+  // the groups' rows in order, in long double; 1/2 and the factors of cross_grad_finish once, after the sum over points
+  long double value = 0.0L, flagged = 0.0L, dnoise = 0.0L;
+  std::vector<long double> acc((size_t)n_params, 0.0L);
+  for (int64_t g = 0; g < groups; ++g) {
+    const double* row = hgrp.data() + g * grp_stride;
+    value += (long double)row[0];
+    flagged += (long double)row[stride];
+    if (want_grad) {
+      for (int k = 0; k < n_params; ++k) acc[(size_t)k] += (long double)row[1 + k];
+      dnoise += (long double)row[1 + n_params];
+    }
+  }
+  const bool any = flagged > 0.0L;
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  *logp_out = any ? qnan : (double)value;
+  if (flagged_out) *flagged_out = (int64_t)flagged;
+  if (want_grad) {
+    if (any) {
+      for (int k = 0; k <= n_params; ++k) grad_out[k] = qnan;
+    } else {
+      for (int k = 0; k < n_params; ++k) acc[(size_t)k] *= 0.5L;
+      cross_grad_finish(ks, acc.data(), grad_out);
+      grad_out[n_params] = (double)(0.5L * dnoise);
+    }
+  }
   return 0;
 }
 

@@ -102,9 +102,13 @@ struct KnnArgs {
   double* dist;           // likewise; may be null when parts == 1
   int64_t d, n, ns, ld, part_len;   // part p takes the candidates [p part_len, min(n, (p + 1) part_len)), part_len a multiple of KNN_TC
   int m, parts;
+  int64_t q_first;        // BEFORE only: query j is column q_first + j of X itself (Xs = X + q_first d)
 };
 
-template <bool SCALED, bool BIG>
+// BEFORE (gprc_dev_knn_before, the conditioning sets of the Vecchia likelihood): the queries are columns of X and a candidate is eligible
+// iff its index is below its query's.  An ineligible lane passes +inf, like a lane without a candidate, and a workgroup's tile loop ends
+// at its largest query index: about half the pair work.  Ranks that no candidate fills keep the list's initial (+inf, -1).
+template <bool SCALED, bool BIG, bool BEFORE = false>
 __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const KnnArgs a) {
   __shared__ double cand[KNN_DC * KNN_LDC];
   __shared__ double qry[KNN_DC * KNN_WG_Q];     // [c][query of the workgroup]
@@ -118,8 +122,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const KnnArgs a) {
   KnnList L[KNN_Q];
 #pragma unroll
   for (int q = 0; q < KNN_Q; ++q) list_init(L[q]);
+  int64_t t_end = i_end;
+  if constexpr (BEFORE) {   // the largest query index of the workgroup: no candidate from there on is eligible for any of its queries
+    const int64_t q_last = a.q_first + (q0 + KNN_WG_Q < a.ns ? q0 + KNN_WG_Q : a.ns) - 1;
+    if (q_last < t_end) t_end = q_last;
+  }
 
-  for (int64_t t0 = i_begin; t0 < i_end; t0 += KNN_TC) {
+  for (int64_t t0 = i_begin; t0 < t_end; t0 += KNN_TC) {
     double acc[KNN_A][KNN_Q];
 #pragma unroll
     for (int s = 0; s < KNN_A; ++s)
@@ -161,7 +170,11 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const KnnArgs a) {
       const int64_t gi = t0 + s * 64 + lane;
       const bool in = gi < i_end;
 #pragma unroll
-      for (int q = 0; q < KNN_Q; ++q) list_consider<BIG>(L[q], lane, a.m, in ? acc[s][q] : __builtin_huge_val(), (int)gi);
+      for (int q = 0; q < KNN_Q; ++q) {
+        bool eligible = in;
+        if constexpr (BEFORE) eligible = in && gi < a.q_first + q0 + wave * KNN_Q + q;
+        list_consider<BIG>(L[q], lane, a.m, eligible ? acc[s][q] : __builtin_huge_val(), (int)gi);
+      }
     }
   }
 #pragma unroll
@@ -254,23 +267,26 @@ size_t knn_workspace_doubles(int64_t ns, int m, int parts) {
   return entries + (entries + 1) / 2;   // the distances, then the indices
 }
 
-int launch_knn(hipStream_t s, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, const double* scale, int m, int* idx, double* dist,
-               int64_t ld, int parts, int64_t part_len, double* work) {
+namespace {
+
+template <bool BEFORE>
+int launch_knn_any(hipStream_t s, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, int64_t q_first, const double* scale, int m, int* idx,
+                   double* dist, int64_t ld, int parts, int64_t part_len, double* work) {
   if (ns <= 0) return 0;
   const int64_t groups = (ns + KNN_WG_Q - 1) / KNN_WG_Q;
   const bool split = parts > 1;
   const size_t entries = (size_t)parts * (size_t)ns * (size_t)m;
   double* wdist = split ? work : dist;
   int* widx = split ? reinterpret_cast<int*>(work + entries) : idx;
-  KnnArgs a{X, Xs, scale, widx, wdist, d, n, ns, ld, part_len, m, parts};
+  KnnArgs a{X, Xs, scale, widx, wdist, d, n, ns, ld, part_len, m, parts, q_first};
   const dim3 grid((unsigned)groups, (unsigned)parts), block(KNN_THREADS);
   const bool big = m > 64;
   if (scale) {
-    if (big) hipLaunchKernelGGL((knn_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((knn_kernel<true, false>), grid, block, 0, s, a);
+    if (big) hipLaunchKernelGGL((knn_kernel<true, true, BEFORE>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((knn_kernel<true, false, BEFORE>), grid, block, 0, s, a);
   } else {
-    if (big) hipLaunchKernelGGL((knn_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((knn_kernel<false, false>), grid, block, 0, s, a);
+    if (big) hipLaunchKernelGGL((knn_kernel<false, true, BEFORE>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((knn_kernel<false, false, BEFORE>), grid, block, 0, s, a);
   }
   GPRC_LAUNCH_CHECK();
   if (split) {
@@ -281,6 +297,18 @@ int launch_knn(hipStream_t s, const double* X, int64_t d, int64_t n, const doubl
     GPRC_LAUNCH_CHECK();
   }
   return 0;
+}
+
+}  // namespace
+
+int launch_knn(hipStream_t s, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, const double* scale, int m, int* idx, double* dist,
+               int64_t ld, int parts, int64_t part_len, double* work) {
+  return launch_knn_any<false>(s, X, d, n, Xs, ns, 0, scale, m, idx, dist, ld, parts, part_len, work);
+}
+
+int launch_knn_before(hipStream_t s, const double* X, int64_t d, int64_t first, int64_t count, const double* scale, int m, int* idx, double* dist, int64_t ld,
+                      int parts, int64_t part_len, double* work) {
+  return launch_knn_any<true>(s, X, d, first + count, X + first * d, count, first, scale, m, idx, dist, ld, parts, part_len, work);
 }
 
 int launch_knn_gather(hipStream_t s, const int* idx, int64_t ld, const double* X, const double* y, int64_t d, int64_t ns, int64_t m, double* Xg, double* yg) {

@@ -29,11 +29,14 @@ mode search of GPC$new, then one contraction), `optimize_gpc` maximises it over 
 The sparse GPR has it too: `elbo_grad` is Titsias' collapsed bound and its exact gradient with respect to the kernel parameters, the
 noise and the inducing points (gprc_sgpr_elbo_grad: the fit's pass, a second pass and one contraction), `optimize_sparse` maximises it
 over log(theta), log(noise) and the inducing points themselves.
+The local GPR learns its parameters on Vecchia's approximation of the likelihood: `vecchia_logp_grad` is the sum of the n conditionals
+log p(y_i | y_N(i)) and its exact gradient (gprc_lgpr_vecchia_logp_grad: one small model per workgroup), `optimize_local` maximises it
+with the conditioning sets searched once per pass and frozen inside it.
 What lives here, and what is shared (the next objective or optimiser uses these, it does not copy a neighbour):
   * fit(), its optim_until_error wrappers, cov_dict and SENTINEL: the reference-faithful part;
   * the objective wrappers dens, dens_deriv, logp_grad, loo_grad, logq_grad, elbo_grad: each is `_staged` (points, targets, context,
     parameter pointers) and one native call;
-  * the optimisers optimize, optimize_multistart, optimize_sparse, optimize_iterative, optimize_gpc: each is a `_Front` (start values,
+  * the optimisers optimize, optimize_multistart, optimize_sparse, optimize_iterative, optimize_local, optimize_gpc: each is a `_Front` (start values,
     z = [log theta, log noise, ...] and back, the gradient cut to match, the result dict) around `_maximise_over_log`; how one point
     of z is evaluated -- exp (`_from_log`), range check (`_in_range`), chain factor and one-entry cache (`_Evaluation`) -- is the same
     code for the single optimisers and for every instance of optimize_multistart, which takes the first two for all the points of a
@@ -57,7 +60,7 @@ from .covfunc import (CovFunc, as_d_points, as_points, pad_point_sets, constant,
 from .optim import brent_fmin, vmmin, vmmin_steps
 
 __all__ = ["fit", "dens", "dens_deriv", "logp_grad", "logp_grad_batch", "loo_grad", "optimize", "optimize_multistart", "vmmin_steps", "logq_grad", "optimize_gpc", "elbo", "elbo_grad", "optimize_sparse",
-           "cov_dict", "brent_fmin", "vmmin"]
+           "vecchia_logp_grad", "optimize_local", "cov_dict", "brent_fmin", "vmmin"]
 
 # R/fit.R:2-33: name -> (kernel generic, display name, start values)
 cov_dict = {
@@ -248,25 +251,26 @@ class _Evaluation:
         return self.val, self.grad
 
 
-def _maximise_over_log(z0, value_and_grad_theta, maxit, n_log=None):
+def _maximise_over_log(z0, value_and_grad_theta, maxit, n_log=None, failed=SENTINEL):
     """vmmin on z = log(theta) of a function to MAXIMISE: value_and_grad_theta(theta) -> (value, d value / d theta), evaluated by the
     rule of `_Evaluation`; an evaluation that raises NotPositiveDefinite / ArithmeticError / a native iteration cap, or whose exp(z)
     over- or underflows, is the sentinel -10000 (optim_until_error).  n_log: only the first n_log entries of z are logarithms, the
     rest are the variables themselves (the inducing points of optimize_sparse; they must stay finite).  Returns vmmin's tuple (z in
-    the same mixed form)."""
+    the same mixed form).  failed: what such an evaluation counts as instead of the sentinel (optimize_local: -inf, a point vmmin never
+    accepts -- at its sizes the objective itself lies below -10000)."""
     point = _Evaluation(len(z0) if n_log is None else n_log)
 
     def fn(z):
         try:
             return -point.at(z, value_and_grad_theta)[0]
         except (nat.NotPositiveDefinite, ArithmeticError):
-            return -SENTINEL
+            return -failed
 
     return vmmin(z0, fn, lambda z: -point.at(z, value_and_grad_theta)[1], maxit=maxit)
 
 
 class _Front:
-    """What the five optimisers share around vmmin: the start values (defaulted, checked), the vector z = [log(theta), log(noise) when
+    """What the six optimisers share around vmmin: the start values (defaulted, checked), the vector z = [log(theta), log(noise) when
     the noise is optimised, whatever else the caller appends] and its inverse, the gradient cut to match, and the result dict.
     noise=None: the objective has none (optimize_gpc).  many: `start` is S x p, one row per start (optimize_multistart)."""
 
@@ -570,6 +574,94 @@ def optimize_iterative(X, y, noise, name, start=None, *, n_probes=31, rng=None, 
 
     r = front.result(_maximise_over_log(front.pack(), vg, maxit))
     return dict(r, se=se_of.get(r["value"], float("nan")))
+
+
+def _ordered(X, y, order, seed, who):
+    """(X, y, label) in the order of conditioning: order a permutation of the columns, "random" / "given" (local.vecchia_order), or None"""
+    from .local import vecchia_order
+    Xm = as_points(X)
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    if y.ndim != 1 or y.size != Xm.shape[1]:
+        raise ValueError("length(y) == ncol(X) is not TRUE")
+    if order is None or (isinstance(order, str) and order == "given"):
+        return Xm, y, "given"
+    if isinstance(order, str):
+        perm, label = vecchia_order(Xm, order, seed), order
+    else:
+        perm, label = np.asarray(order), "custom"
+        if perm.ndim != 1 or perm.size != y.size or not np.array_equal(np.sort(perm), np.arange(y.size)):
+            raise ValueError(who + ": order must be a permutation of 0 .. ncol(X) - 1")
+    return np.asfortranarray(Xm[:, perm]), np.ascontiguousarray(y[perm]), label
+
+
+def vecchia_logp_grad(X, y, noise, name, v, m=32, order=None, ctx=None):
+    """(logp_V, grad) of LocalGPR(X, y, noise, name(v)): Vecchia's approximation of the log marginal likelihood -- every observation
+    conditioned on its min(m, i) nearest earlier ones, in the metric of name(v) -- and its exact gradient, len(v) + 1 entries, d / d noise
+    last (local.LocalGPR.vecchia_prepare + vecchia_logp_grad; gprc_lgpr_vecchia_logp_grad).  `name` a key of grad_dict, `v` in the order
+    `dens` takes it; m: 1 .. 127; order: None / "given" (the columns as they come), "random", or a permutation.  With m >= n - 1 it is
+    `logp_grad`'s value and gradient to rounding.  NaN when a conditional's model is not positive definite."""
+    from .local import LocalGPR
+    Xo, yo, _ = _ordered(X, y, order, 0, "vecchia_logp_grad")
+    with LocalGPR(Xo, yo, noise, _func_of(name, np.atleast_1d(np.asarray(v, dtype=np.float64))), m=min(int(m) + 1, 128), ctx=ctx) as model:
+        model.vecchia_prepare(m)
+        return model.vecchia_logp_grad()
+
+
+def optimize_local(X, y, noise, name, start=None, *, m=32, order="random", seed=0, rounds=None, optimize_noise=True, maxit=100, value_and_grad=None,
+                   ctx=None):
+    """`optimize` for the local GPR (local.LocalGPR), at n where no n x n factor fits: maximise the Vecchia likelihood (`vecchia_logp_grad`)
+    of kernel `name` over its parameters, and over the noise when `optimize_noise` and noise > 0, with vmmin on z = log(theta).  (X, y) are
+    put into `order` first ("random" with `seed`, "given", or a permutation: local.vecchia_order).  A pass searches the conditioning
+    sets in the metric of its start values (vecchia_prepare), freezes them and runs vmmin; `rounds` passes, each from the previous result:
+    default 2 for the ARD kernels, whose metric moves with the parameters, 1 otherwise.  value_and_grad(theta, noise) -> (logp_V, grad)
+    replaces the native objective; value_and_grad.prepare(theta, noise), when it has one, is called at the start of every pass.  An
+    evaluation that fails (a model not positive definite, a parameter over- or underflowing) is a point vmmin never accepts: it counts as
+    -inf, not as the siblings' sentinel -10000, which at n = 2^20 lies far ABOVE the likelihood itself.  Returns
+    `optimize`'s dict(par, noise, value, counts, convergence, func) of the last pass, counts added over the passes, and `m`, `order`,
+    `rounds`: LocalGPR(X, y, r["noise"], r["func"]) is the fitted model."""
+    func = grad_dict[name]   # noqa: F841  (KeyError for a kernel without a gradient, as `optimize`)
+    if int(m) != m or not 1 <= int(m) <= 127:
+        raise ValueError("optimize_local: m must be an integer in 1 .. 127")
+    rounds = (2 if _is_ard(name) else 1) if rounds is None else int(rounds)
+    if rounds < 1:
+        raise ValueError("optimize_local: rounds >= 1 is not TRUE")
+    Xo, yo, label = _ordered(X, y, order, seed, "optimize_local")
+    d = Xo.shape[0]
+    front = _Front("optimize_local", name, d, start, noise, bool(optimize_noise) and noise > 0)
+    model = None
+    if value_and_grad is None:
+        from .local import LocalGPR
+        model = LocalGPR(Xo, yo, noise, _func_of(name, front.starts[0]), m=min(int(m) + 1, 128), ctx=ctx)
+
+        def value_and_grad(theta, nz):
+            with np.errstate(divide="ignore", over="ignore"):
+                if not _in_range(1.0 / theta, theta.size):   # a subnormal length scale: finite and > 0, but 1 / l is not (the native layer refuses it)
+                    raise _out_of_range()
+            val, g = model.vecchia_logp_grad(theta, nz)
+            if model.vecchia_flagged or not math.isfinite(val):
+                raise ArithmeticError("a conditional's model is not positive definite")
+            return val, g
+
+        def prepare(theta, nz):
+            model.set_params(_func_of(name, theta), nz)
+            model.vecchia_prepare(int(m))
+    else:
+        prepare = getattr(value_and_grad, "prepare", lambda theta, nz: None)
+
+    def vg(t):
+        val, g = value_and_grad(*front.split(t))
+        return val, front.grad(g)
+
+    try:
+        z, fn, gr = front.pack(), 0, 0
+        for _ in range(rounds):
+            prepare(*front.split(_from_log(z, front.n_log)))
+            out = _maximise_over_log(z, vg, maxit, failed=-math.inf)
+            z, fn, gr = out[0], fn + out[2], gr + out[3]
+        return front.result((z, out[1], fn, gr, out[4]), m=int(m), order=label, rounds=rounds)
+    finally:
+        if model is not None:
+            model.close()
 
 
 def optimize_gpc(X, y, name, start=None, *, epsilon=1e-10, maxit=100, value_and_grad=None, ctx=None):

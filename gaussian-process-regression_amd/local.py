@@ -8,7 +8,16 @@ per test point.  The cost depends on n only through the search; nothing of size 
 
 s_c = 1 / l_c for the ARD kernels (the neighbours are the points of largest prior correlation), 1 for the others.  Kernels: those with
 a batched small-model path -- sqrexp, sqrexp_ard, gammaexp, rationalquadratic and the four Matern kernels.
-Out of scope here: learning the parameters on the local model (take them from fit.optimize* on a subsample), gradients at x*.
+
+The parameters are learnt on the local model itself, through Vecchia's approximation of the likelihood (the likelihood of a
+nearest-neighbour GP; DESIGN.md section 7, "Vecchia likelihood"): with the order of conditioning the column order of X,
+
+    log p_V(y) = sum_i log p(y_i | y_N(i)),    N(i) = the min(m, i) points j < i with the smallest (dist2, j)
+
+LocalGPR.vecchia_prepare searches the conditioning sets once (gprc_dev_knn_before) and freezes them, LocalGPR.vecchia_logp_grad is the
+sum and its exact gradient in one native call (gprc_lgpr_vecchia_logp_grad), fit.optimize_local the optimiser over it.  The order
+matters: vecchia_order gives a random permutation to apply to (X, y) first.
+Out of scope here: max-min ordering, grouped conditioning sets, Vecchia prediction, gradients at x*.
 """
 from __future__ import annotations
 
@@ -19,9 +28,10 @@ import numpy as np
 from . import _native as nat
 from .covfunc import as_points, as_test_points, require_tagged
 
-__all__ = ["LocalGPR", "knn", "MAX_NEIGHBOURS", "BATCHED_KERNELS"]
+__all__ = ["LocalGPR", "knn", "knn_before", "vecchia_order", "MAX_NEIGHBOURS", "MAX_CONDITIONING", "BATCHED_KERNELS"]
 
 MAX_NEIGHBOURS = 128   # a local model is one batched small model (include/gprc_native.h GPRC_BATCH_MAX_N)
+MAX_CONDITIONING = 127   # a conditional is the model of the conditioning set and the point itself
 BATCHED_KERNELS = (nat.SQREXP, nat.GAMMAEXP, nat.RATQUAD, nat.SQREXP_ARD, nat.MATERN32, nat.MATERN52, nat.MATERN32_ARD, nat.MATERN52_ARD)
 
 
@@ -42,11 +52,7 @@ def knn(X, X_star, m, scale=None, ctx=None):
         raise ValueError("knn: X_star must have nrow(X) rows")
     if m > n:
         raise ValueError("knn: m <= ncol(X) is not TRUE")
-    sc = None
-    if scale is not None:
-        sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
-        if sc.size != d or not (np.all(np.isfinite(sc)) and np.all(sc > 0)):
-            raise ValueError("knn: scale must be nrow(X) finite values > 0")
+    sc = _checked_scale(scale, d, "knn")
     Xs = np.asfortranarray(Xs)
     ns = Xs.shape[1]
     idx, dist = np.empty((ns, m), dtype=np.intc), np.empty((ns, m))
@@ -54,6 +60,47 @@ def knn(X, X_star, m, scale=None, ctx=None):
     nat.check(nat.lib().gprc_dev_knn(ctx.handle, Xm.ctypes.data, d, n, Xs.ctypes.data, ns, None if sc is None else sc.ctypes.data, m,
                                      idx.ctypes.data, dist.ctypes.data, m))
     return idx, dist
+
+
+def _checked_scale(scale, d, who):
+    if scale is None:
+        return None
+    sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).ravel())
+    if sc.size != d or not (np.all(np.isfinite(sc)) and np.all(sc > 0)):
+        raise ValueError(who + ": scale must be nrow(X) finite values > 0")
+    return sc
+
+
+def knn_before(X, m, scale=None, first=0, count=None, ctx=None):
+    """(idx[count, m], dist2[count, m]): for every column i in [first, first + count) of X (d x n) the m nearest columns j < i by knn's
+    key, ascending (gprc_dev_knn_before): the conditioning sets of the Vecchia likelihood.  Ranks that no predecessor fills (i < m) are
+    -1 and +inf.  1 <= m <= 128; count=None: up to the last column."""
+    m = _check_m(m, "knn_before")
+    Xm = np.asfortranarray(as_points(X, what="X"))
+    d, n = Xm.shape
+    first = int(first)
+    count = n - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > n:
+        raise ValueError("knn_before: the window [first, first + count) must lie in 0 .. ncol(X)")
+    sc = _checked_scale(scale, d, "knn_before")
+    idx, dist = np.empty((count, m), dtype=np.intc), np.empty((count, m))
+    ctx = ctx or nat.default_context()
+    nat.check(nat.lib().gprc_dev_knn_before(ctx.handle, Xm.ctypes.data, d, n, first, count, None if sc is None else sc.ctypes.data, m,
+                                            idx.ctypes.data, dist.ctypes.data, m))
+    return idx, dist
+
+
+def vecchia_order(X, kind="random", seed=0):
+    """A permutation of the columns of X (d x n) to condition in: "random" (np.random.default_rng(seed).permutation) or "given" (the
+    identity).  The Vecchia likelihood conditions every point on its nearest EARLIER points, so the order matters: in the order a
+    regular grid or a time series is stored in, the predecessors all lie to one side; a random order gives every point neighbours
+    at every scale around it.  (A max-min ordering does better still; it is out of scope here.)"""
+    n = as_points(X, what="X").shape[1]
+    if kind == "given":
+        return np.arange(n)
+    if kind == "random":
+        return np.random.default_rng(seed).permutation(n)
+    raise ValueError('vecchia_order: kind must be "random" or "given"')
 
 
 class LocalGPR(nat.Handle):
@@ -74,6 +121,7 @@ class LocalGPR(nat.Handle):
         d, n = Xm.shape
         self._X, self._y, self._k, self._noise, self._m = Xm, y, k, float(noise), min(m, n)
         self._info = None
+        self._vecchia_m = self._vecchia_flagged = None
         self._model = C.c_void_p()
         self._ctx = ctx or nat.default_context()
         _, pp, npar = nat.params_array(k.native_params(d))
@@ -124,6 +172,51 @@ class LocalGPR(nat.Handle):
         nat.check(nat.lib().gprc_lgpr_set_params(self.handle, pp, npar, float(noise)))
         self._k, self._noise = k, float(noise)
 
+    def vecchia_prepare(self, m=None):
+        """Search and keep the conditioning sets of the Vecchia likelihood: for every point its min(m, i) nearest EARLIER points in the
+        model's current metric (1 / l_c of the ARD kernels, Euclidean otherwise), n x m indices on the device.  m: 1 .. 127, default
+        min(self.m, 127), clamped to n - 1.  The sets stay as they are -- through set_params too -- until the next vecchia_prepare, so
+        vecchia_logp_grad is a smooth function of the parameters.  Returns the m in use."""
+        m = min(self._m, MAX_CONDITIONING) if m is None else m
+        if int(m) != m or not 1 <= int(m) <= MAX_CONDITIONING:
+            raise ValueError(f"LocalGPR.vecchia_prepare: m must be an integer in 1 .. {MAX_CONDITIONING}")
+        nat.check(nat.lib().gprc_lgpr_vecchia_prepare(self.handle, int(m)))
+        self._vecchia_m = min(int(m), self._X.shape[1] - 1)
+        return self._vecchia_m
+
+    def vecchia_logp_grad(self, theta=None, noise=None, grad=True, cond=False):
+        """(logp_V, grad[, cond]) at the parameter vector theta (the ABI's order; default: the model's own) and the noise (default: the
+        model's own): the Vecchia log likelihood over the prepared conditioning sets and its exact gradient, len(theta) + 1 entries,
+        d / d noise last (None when not grad: the value has the same bits); cond=True appends the n conditionals log p(y_i | y_N(i)).
+        The model's own parameters are not changed.  A point whose model is not positive definite makes logp_V and grad NaN and its
+        conditional NaN; .vecchia_flagged counts them; the call does not raise for it."""
+        handle = self.handle
+        if self._vecchia_m is None:
+            raise ValueError("LocalGPR.vecchia_logp_grad: call vecchia_prepare first")
+        d, n = self._X.shape
+        p, pp, npar = nat.params_array(self._k.native_params(d) if theta is None else np.atleast_1d(np.asarray(theta, dtype=np.float64)))
+        g = np.empty(npar + 1) if grad else None
+        c = np.empty(n) if cond else None
+        out, flagged = C.c_double(), C.c_int64()
+        nat.check(nat.lib().gprc_lgpr_vecchia_logp_grad(handle, pp, npar, float(self._noise if noise is None else noise), C.byref(out),
+                                                        g.ctypes.data if grad else None, c.ctypes.data if cond else None, C.byref(flagged)))
+        self._vecchia_flagged = int(flagged.value)
+        return (out.value, g, c) if cond else (out.value, g)
+
+    @property
+    def vecchia_neighbours(self):
+        """idx[n, m] of the last vecchia_prepare: row i the conditioning set of point i, nearest first, -1 at the ranks >= i"""
+        handle = self.handle
+        if self._vecchia_m is None:
+            raise ValueError("LocalGPR.vecchia_neighbours: call vecchia_prepare first")
+        n, m = self._X.shape[1], self._vecchia_m
+        idx = np.empty((n, m), dtype=np.intc)
+        if m > 0:
+            nat.check(nat.lib().gprc_lgpr_vecchia_neighbours(handle, idx.ctypes.data, m))
+        return idx
+
+    vecchia_flagged = property(lambda self: self._vecchia_flagged,
+                               doc="points of the last vecchia_logp_grad whose model was not positive definite (None before the first)")
     X = property(lambda self: self._X)
     y = property(lambda self: self._y)
     k = property(lambda self: self._k)

@@ -290,6 +290,42 @@ GPRC_API int gprc_lgpr_neighbours(gprc_local_model* model, const double* X_star,
                                   int64_t ld_out);
 GPRC_API int gprc_lgpr_dims(const gprc_local_model* model, int64_t* n_out, int64_t* d_out, int64_t* m_out);
 GPRC_API int gprc_lgpr_free(gprc_local_model* model);
+/* The predecessor-constrained search (the conditioning sets of the Vecchia likelihood below): for every query i in [first, first + count),
+ * a column of X itself, the m smallest keys (dist2, j) among the columns j < i of X.  Distance formula, key, tie rule, NaN rule and the
+ * layout of idx_out / dist_out (query i at row i - first) are exactly gprc_dev_knn's; ranks that no candidate fills (i < m) report -1
+ * and +inf.  1 <= m <= 128 (m may exceed n), n < 2^31, 0 <= first, 0 <= count (0: nothing is done), first + count <= n.  Results are a
+ * function of (X, scale, m, i) alone: not of first, count, the tiling, the split, or host versus device pointers.  About half the pair
+ * work of gprc_dev_knn with n_star = n.  GPRC_ERR_ARG: gprc_dev_knn's cases, and a window outside 0 .. n.
+ *
+ * The Vecchia likelihood of the local GPR ("Vecchia likelihood"; the likelihood of a nearest-neighbour GP): with
+ * the order of conditioning the column order of X,
+ *   log p_V(y) = sum_i log p(y_i | y_N(i)),   N(i) = the min(m_cond, i) points j < i with the smallest key (dist2, j),
+ * the exact log marginal likelihood when m_cond >= n - 1, n independent models of at most m_cond + 1 points, and its exact gradient.
+ * gprc_lgpr_vecchia_prepare searches once (gprc_dev_knn_before) in the model's CURRENT metric -- 1 / l_c from the parameters of
+ * gprc_lgpr_create or gprc_lgpr_set_params for the ARD kernels, Euclidean otherwise -- and keeps n x m_cond 32-bit indices on the device
+ * in the object; 1 <= m_cond <= 127, clamped to n - 1 (n = 1 keeps nothing: the sum is the one marginal).  A second prepare replaces the
+ * first; gprc_lgpr_set_params does not touch the stored neighbours: they are frozen until the next prepare, so the objective is smooth
+ * in the parameters.  gprc_lgpr_vecchia_logp_grad evaluates at the GIVEN parameters and noise (the object's own are unchanged):
+ *   grad_out     HOST, n_params + 1 entries, d / d noise last; may be NULL for the value alone, with the same value bits
+ *   cond_out     host or device, n entries log p(y_i | y_N(i)), or NULL
+ *   flagged_out  HOST, the number of points whose model is not positive definite, or NULL.  With any flagged point *logp_out and grad_out
+ *                are NaN and the call returns GPRC_OK; cond_out is NaN exactly at the flagged points, the others keep their bits
+ * Kernels: those of gprc_gpr_batch_logp_grad.  One model per workgroup, factored in LDS (Cholesky only: no inverse, nothing of size
+ * (m_cond + 1)^2 leaves the CU); launches of at most GPRC_VECCHIA_CHUNK points, a multiple of 256; the device adds groups of 256
+ * consecutive points by global index in a fixed order and the host adds the groups' rows in order in long double: value, gradient and
+ * cond_out have the same bits on every call, for host and device pointers and whichever outputs are asked for, and cond_i depends on
+ * (X, y, N(i), the parameters) alone.  MEMORY: d * n + n doubles (as before) + 4 * n * m_cond bytes held by the object; per launch
+ * (n_params + 2) doubles and one int a point, n_params + 3 doubles per 256 points of the call.
+ * gprc_lgpr_vecchia_neighbours: the stored indices, row i at idx_out + i * ld_out (host or device; ld_out >= m_cond), -1 at ranks >= i.
+ * GPRC_ERR_ARG: a null model or pointer (grad_out, cond_out, flagged_out may be NULL), m_cond outside 1 .. 127, bad parameters or noise
+ * (gprc_lgpr_create's rules), no prepare yet (n > 1), ld_out < m_cond, a model whose context has been destroyed. */
+#define GPRC_VECCHIA_CHUNK 16384
+GPRC_API int gprc_dev_knn_before(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, int64_t first, int64_t count, const double* scale,
+                                 int64_t m, int* idx_out, double* dist_out, int64_t ld_out);
+GPRC_API int gprc_lgpr_vecchia_prepare(gprc_local_model* model, int64_t m_cond);
+GPRC_API int gprc_lgpr_vecchia_logp_grad(gprc_local_model* model, const double* params, int n_params, double noise, double* logp_out,
+                                         double* grad_out, double* cond_out, int64_t* flagged_out);
+GPRC_API int gprc_lgpr_vecchia_neighbours(gprc_local_model* model, int* idx_out, int64_t ld_out);
 /* Leave-one-out cross-validation of a fitted GPR model in closed form (Rasmussen & Williams 5.4.2; no reference counterpart).  With
  * K_y = K + noise * I, P = K_y^-1, alpha = P y and p_i = P_ii, the prediction of y_i from the other n - 1 observations is
  *   mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i,     logdens_i = 1/2 log p_i - alpha_i^2 / (2 p_i) - 1/2 log(2 pi),
