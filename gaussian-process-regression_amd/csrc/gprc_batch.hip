@@ -2,8 +2,9 @@
 // gprc_gpr_batch_logp_grad, gprc_gpr_batch_fit, gprc_gpr_batch_predict, gprc_gpr_batch_predict_grad and gprc_gpr_batch_loo.
 // The argument checks, one record of derived constants per model (make_deriv_spec, once per model), the staging of host arrays, the
 // launches of kernels_batch.hip -- at most GPRC_BATCH_LAUNCH models each, on one set of scratch slabs from the context's pool -- and the
-// tail every exact gradient has: the sums that the device leaves get 1/2 and the factors of cross_grad_finish, a model that is not
-// positive definite gets NaN.  A model's record, its launch and its tail do not look at any other model: its bits do not depend on the batch.
+// tail every exact gradient has (half_theta_grad, gprc_host.h): the sums that the device leaves get 1/2 and the factors of
+// cross_grad_finish, a model that is not positive definite gets NaN.  A model's record, its launch and its tail do not look at any other
+// model: its bits do not depend on the batch.
 // The two fitting entry points share every step up to the launches (batch_checks, batch_records, batch_launches): the fitted batch differs
 // only in where the buffers live -- the gprc_batch_model owns them -- and in where the kernel puts W = L^-1 (BatchArgs::w).
 #include <algorithm>
@@ -19,9 +20,7 @@ using namespace gprc;
 static_assert(GPRC_BATCH_MAX_N == NBI, "a batched model is one LDS-resident diagonal block");
 
 // A fitted batch: what gprc_gpr_batch_predict, _predict_grad and _loo read again, all in device memory from the context's pool.
-struct gprc_batch_model {
-  gprc_ctx* ctx = nullptr;
-  uint64_t ctx_id = 0;
+struct gprc_batch_model : Bound {
   int kernel = 0, n_params = 0, np_store = 0, prm_stride = 0;
   int64_t B = 0, d = 0, n_max = 0, x_stride = 0, y_stride = 0;
   bool uneven = false;   // fitted with n_each: a model may have fewer than n_max points
@@ -34,8 +33,6 @@ struct gprc_batch_model {
 };
 
 namespace {
-
-int bad(const char* who, const std::string& msg) { set_error(std::string(who) + ": " + msg); return GPRC_ERR_ARG; }
 
 // the checks both fitting entry points make, in one order; *empty: B = 0, nothing to do
 int batch_checks(const char* who, gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params, const double* noise,
@@ -119,20 +116,16 @@ int batch_launches(const char* who, hipStream_t s, int kernel, int64_t B, const 
   return 0;
 }
 
-void free_batch_model(gprc_batch_model* m) {
-  if (!m) return;
-  if (m->ctx) (void)hipSetDevice(m->ctx->device);
-  else                                   // the context went first: the buffers go straight back to the driver
-    for (DevMem* q : {&m->X, &m->y, &m->alpha, &m->W, &m->prm, &m->info}) q->owner = nullptr;
-  delete m;
+// a row of alpha_out: the model's alpha; NaN for a flagged model's points, zero behind n_b
+void expand_alpha(const double* alpha_b, bool ok, int64_t nb, int64_t n_max, double* row) {
+  for (int64_t i = 0; i < n_max; ++i) row[i] = ok ? alpha_b[i] : (i < nb ? std::numeric_limits<double>::quiet_NaN() : 0.0);
 }
-struct BatchModelFree { void operator()(gprc_batch_model* m) const { free_batch_model(m); } };
 
 // gprc_gpr_batch_predict and gprc_gpr_batch_predict_grad: one set of checks, one staging, one split rule; grad: the gradient entry point
 int batch_predict_any(const char* who, bool grad, gprc_batch_model* m, const double* X_star, int64_t ns_max, int64_t xs_stride, const int64_t* ns_each,
                       double* mean_out, double* var_out, int64_t ld_out, double* dmean_out, double* dvar_out, int64_t ld_grad) {
   if (!m) return bad(who, "null model");
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  GPRC_TRY(ctx_gone(who, *m));
   if (!X_star) return bad(who, "null input pointer (X_star)");
   if (!grad && !mean_out && !var_out) return bad(who, "null output pointers (mean_out and var_out: one of them may be NULL, not both)");
   if (grad && !mean_out && !var_out && !dmean_out && !dvar_out)
@@ -163,16 +156,10 @@ int batch_predict_any(const char* who, bool grad, gprc_batch_model* m, const dou
   const int64_t grad_count = (B - 1) * ld_grad + m->d * ns_max;
   const bool grad_gaps = ns_each != nullptr || (ld_grad > m->d * ns_max && B > 1);
   Out mean, var, dmean, dvar;
-  auto stage = [&](Out& o, double* p, int64_t count, bool some) -> int {
-    if (!p) return 0;
-    GPRC_TRY(o.set(p, count));
-    if (o.host && some) GPRC_HIP(hipMemcpyAsync(o.dev, p, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, s));
-    return 0;
-  };
-  GPRC_TRY(stage(mean, mean_out, out_count, gaps));
-  GPRC_TRY(stage(var, var_out, out_count, gaps));
-  GPRC_TRY(stage(dmean, dmean_out, grad_count, grad_gaps));
-  GPRC_TRY(stage(dvar, dvar_out, grad_count, grad_gaps));
+  GPRC_TRY(mean.set_keeping(mean_out, out_count, gaps, s));
+  GPRC_TRY(var.set_keeping(var_out, out_count, gaps, s));
+  GPRC_TRY(dmean.set_keeping(dmean_out, grad_count, grad_gaps, s));
+  GPRC_TRY(dvar.set_keeping(dvar_out, grad_count, grad_gaps, s));
   // the split: whole turns of a workgroup (BATCH_PREDICT_WAVES tiles) over enough workgroups for every CU, when the batch alone has fewer
   int cus = 0;
   GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
@@ -187,12 +174,7 @@ int batch_predict_any(const char* who, bool grad, gprc_batch_model* m, const dou
     a.b0 = b0;
     GPRC_TRY((grad ? launch_batch_predict_grad : launch_batch_predict)(s, m->kernel, a, std::min<int64_t>(GRID_Y, B - b0), split));
   }
-  if (mean_out) GPRC_TRY(mean.finish(s));
-  if (var_out) GPRC_TRY(var.finish(s));
-  if (dmean_out) GPRC_TRY(dmean.finish(s));
-  if (dvar_out) GPRC_TRY(dvar.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  return finish_sync(s, mean, var, dmean, dvar);
 }
 
 }  // namespace
@@ -224,25 +206,16 @@ int gprc_gpr_batch_logp_grad(gprc_ctx* ctx, int kernel, int64_t B, const double*
   if (alpha_out) GPRC_HIP(hipMemcpyAsync(halpha.data(), alpha.p, sizeof(double) * halpha.size(), hipMemcpyDeviceToHost, s));
   GPRC_HIP(hipStreamSynchronize(s));
   const double qnan = std::numeric_limits<double>::quiet_NaN();
-  std::vector<long double> acc((size_t)n_params);
+  std::vector<long double> sums((size_t)n_params + 1);
   for (int64_t b = 0; b < B; ++b) {
     const double* rr = hout.data() + b * out_stride;
     const bool ok = info_out[b] == 0;
     logp_out[b] = ok ? rr[0] : qnan;
     if (grad_out) {
-      double* g = grad_out + b * (n_params + 1);
-      if (ok) {
-        for (int k = 0; k < n_params; ++k) acc[(size_t)k] = 0.5L * (long double)rr[1 + k];
-        cross_grad_finish(specs[(size_t)b], acc.data(), g);
-        g[n_params] = (double)(0.5L * (long double)rr[1 + n_params]);
-      } else {
-        for (int k = 0; k <= n_params; ++k) g[k] = qnan;
-      }
+      for (int k = 0; k <= n_params; ++k) sums[(size_t)k] = (long double)rr[1 + k];
+      half_theta_grad(specs[(size_t)b], sums.data(), sums[(size_t)n_params], ok, n_params, grad_out + b * (n_params + 1));
     }
-    if (alpha_out) {
-      const int64_t nb = n_each ? n_each[b] : n_max;
-      for (int64_t i = 0; i < n_max; ++i) alpha_out[b * n_max + i] = ok ? halpha[(size_t)(b * NBI + i)] : (i < nb ? qnan : 0.0);
-    }
+    if (alpha_out) expand_alpha(halpha.data() + b * NBI, ok, n_each ? n_each[b] : n_max, n_max, alpha_out + b * n_max);
   }
   return 0;
 }
@@ -260,7 +233,7 @@ int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* param
   GPRC_TRY(batch_records(kernel, B, params, n_params, ld_params, noise, d, n_max, n_each, false, &r));
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
-  std::unique_ptr<gprc_batch_model, BatchModelFree> m(new gprc_batch_model);
+  std::unique_ptr<gprc_batch_model, BoundDelete> m(new gprc_batch_model);
   m->ctx = ctx;
   m->ctx_id = ctx->id;
   m->kernel = kernel;
@@ -274,12 +247,8 @@ int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* param
   m->y_stride = y_stride;
   m->uneven = n_each != nullptr;
   // the model's own copies of the points and the targets: the kernel reads them now, gprc_gpr_batch_predict and gprc_gpr_batch_loo again
-  const int64_t x_count = (x_stride ? (B - 1) * x_stride : 0) + d * n_max;
-  GPRC_TRY(m->X.alloc(x_count));
-  GPRC_HIP(hipMemcpyAsync(m->X.p, X, sizeof(double) * (size_t)x_count, is_device_ptr(X) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-  const int64_t y_count = (y_stride ? (B - 1) * y_stride : 0) + n_max;
-  GPRC_TRY(m->y.alloc(y_count));
-  GPRC_HIP(hipMemcpyAsync(m->y.p, y, sizeof(double) * (size_t)y_count, is_device_ptr(y) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  GPRC_TRY(m->X.copy_from(s, X, (x_stride ? (B - 1) * x_stride : 0) + d * n_max));
+  GPRC_TRY(m->y.copy_from(s, y, (y_stride ? (B - 1) * y_stride : 0) + n_max));
   if (int rc = m->W.alloc(B * (int64_t)NBI * NBI)) {
     if (rc == GPRC_ERR_NOMEM)
       set_error(std::string(who) + ": L^-1 of every model, " + std::to_string((B * (int64_t)NBI * NBI * 8) >> 20) + " MiB of device memory, could not be allocated");
@@ -300,7 +269,7 @@ int gprc_gpr_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* param
 int gprc_gpr_batch_get_alpha(gprc_batch_model* m, double* alpha_out) {
   const char* who = "batch_get_alpha";
   if (!m) return bad(who, "null model");
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  GPRC_TRY(ctx_gone(who, *m));
   if (!alpha_out) return bad(who, "null output pointer (alpha_out)");
   GPRC_TRY(use_device(m->ctx));
   hipStream_t s = m->ctx->stream;
@@ -310,11 +279,9 @@ int gprc_gpr_batch_get_alpha(gprc_batch_model* m, double* alpha_out) {
   GPRC_HIP(hipMemcpyAsync(hprm.data(), m->prm.p, sizeof(double) * hprm.size(), hipMemcpyDeviceToHost, s));
   GPRC_HIP(hipMemcpyAsync(hinfo.data(), m->info.p, sizeof(int) * hinfo.size(), hipMemcpyDeviceToHost, s));
   GPRC_HIP(hipStreamSynchronize(s));
-  const double qnan = std::numeric_limits<double>::quiet_NaN();
-  for (int64_t b = 0; b < m->B; ++b) {   // as gprc_gpr_batch_logp_grad's alpha_out: NaN for a flagged model's points, zero behind n_b
+  for (int64_t b = 0; b < m->B; ++b) {   // as gprc_gpr_batch_logp_grad's alpha_out
     const int64_t nb = (int64_t)hprm[(size_t)(b * m->prm_stride + m->np_store + 1)];
-    for (int64_t i = 0; i < m->n_max; ++i)
-      alpha_out[b * m->n_max + i] = hinfo[(size_t)b] == 0 ? halpha[(size_t)(b * NBI + i)] : (i < nb ? qnan : 0.0);
+    expand_alpha(halpha.data() + b * NBI, hinfo[(size_t)b] == 0, nb, m->n_max, alpha_out + b * m->n_max);
   }
   return 0;
 }
@@ -332,7 +299,7 @@ int gprc_gpr_batch_predict_grad(gprc_batch_model* m, const double* X_star, int64
 int gprc_gpr_batch_loo(gprc_batch_model* m, double* mean_out, double* var_out, double* logdens_out, int64_t ld_out, double* loo_out) {
   const char* who = "batch_loo";
   if (!m) return bad(who, "null model");
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
+  GPRC_TRY(ctx_gone(who, *m));
   if (!mean_out && !var_out && !logdens_out && !loo_out) return bad(who, "null output pointers (mean_out, var_out, logdens_out, loo_out: not all four may be NULL)");
   if ((mean_out || var_out || logdens_out) && ld_out < m->n_max) return bad(who, "ld_out < n_max");
   const int64_t B = m->B;
@@ -343,15 +310,9 @@ int gprc_gpr_batch_loo(gprc_batch_model* m, double* mean_out, double* var_out, d
   const int64_t out_count = (B - 1) * ld_out + m->n_max;
   const bool gaps = m->uneven || (ld_out > m->n_max && B > 1);
   Out mean, var, dens;
-  auto stage = [&](Out& o, double* p) -> int {
-    if (!p) return 0;
-    GPRC_TRY(o.set(p, out_count));
-    if (o.host && gaps) GPRC_HIP(hipMemcpyAsync(o.dev, p, sizeof(double) * (size_t)out_count, hipMemcpyHostToDevice, s));
-    return 0;
-  };
-  GPRC_TRY(stage(mean, mean_out));
-  GPRC_TRY(stage(var, var_out));
-  GPRC_TRY(stage(dens, logdens_out));
+  GPRC_TRY(mean.set_keeping(mean_out, out_count, gaps, s));
+  GPRC_TRY(var.set_keeping(var_out, out_count, gaps, s));
+  GPRC_TRY(dens.set_keeping(logdens_out, out_count, gaps, s));
   DevMem score;
   if (loo_out) GPRC_TRY(score.alloc(B));
   BatchLooArgs a{m->W.p, m->alpha.p, m->y.p, m->prm.p, reinterpret_cast<const int*>(m->info.p), mean.dev, var.dev, dens.dev, score.p,
@@ -361,12 +322,8 @@ int gprc_gpr_batch_loo(gprc_batch_model* m, double* mean_out, double* var_out, d
     a.b0 = b0;
     GPRC_TRY(launch_batch_loo(s, a, std::min<int64_t>(GRID_X, B - b0)));
   }
-  if (mean_out) GPRC_TRY(mean.finish(s));
-  if (var_out) GPRC_TRY(var.finish(s));
-  if (logdens_out) GPRC_TRY(dens.finish(s));
   if (loo_out) GPRC_HIP(hipMemcpyAsync(loo_out, score.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  return finish_sync(s, mean, var, dens);
 }
 
 int gprc_batch_model_dims(const gprc_batch_model* m, int64_t* B_out, int64_t* d_out, int64_t* n_max_out) {
@@ -377,15 +334,6 @@ int gprc_batch_model_dims(const gprc_batch_model* m, int64_t* B_out, int64_t* d_
   return 0;
 }
 
-int gprc_batch_model_free(gprc_batch_model* m) {
-  if (!m) return 0;
-  if (m->ctx && !ctx_alive(m->ctx, m->ctx_id)) {   // the context went first: its stream is gone (and was synchronised), its pool too
-    m->ctx = nullptr;
-    (void)hipDeviceSynchronize();
-  }
-  if (m->ctx && m->ctx->stream) (void)hipStreamSynchronize(m->ctx->stream);
-  free_batch_model(m);
-  return 0;
-}
+int gprc_batch_model_free(gprc_batch_model* m) { return free_bound(m, delete_bound<gprc_batch_model>); }
 
 }  // extern "C"

@@ -160,9 +160,15 @@ int ws_get(gprc_ctx* ctx, int slot, int64_t count, double** out) {
 
 int DevMem::alloc(int64_t count) {
   if (count <= 0) count = 1;
-  owner = g_cur_ctx;
+  owner = {g_cur_ctx, g_cur_ctx ? g_cur_ctx->id : 0};
   bytes = sizeof(double) * (size_t)count;
-  return pool_alloc(owner, bytes, (void**)&p);
+  return pool_alloc(owner.ctx, bytes, (void**)&p);
+}
+
+int DevMem::copy_from(hipStream_t s, const double* src, int64_t count) {
+  GPRC_TRY(alloc(count));
+  GPRC_HIP(hipMemcpyAsync(p, src, sizeof(double) * (size_t)count, hipMemcpyDefault, s));
+  return 0;
 }
 
 }  // namespace gprc

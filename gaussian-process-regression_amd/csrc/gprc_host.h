@@ -1,8 +1,10 @@
-// gprc_host.h -- what the units of the host layer (gprc_ctx, gprc_sched, gprc_model: see gprc_internal.h) share: the two
-// handle types, scoped device memory and argument staging, the schedules and the owner of a model.
+// gprc_host.h -- what the units of the host layer (see gprc_internal.h for the list) share: the context, the base of every handle that
+// lives on one (Bound: the liveness check ctx_gone, the one free free_bound) and the model, scoped device memory that knows whether its
+// owner is alive (DevMem), argument staging (In, Out, IntOut, finish_sync), bad(who, msg), the gradient tail, the schedules.
 #pragma once
 #include <atomic>
 #include <cstdio>
+#include <limits>
 #include <memory>
 #include <vector>
 
@@ -41,9 +43,13 @@ struct gprc_ctx {
 
 enum ModelType { MODEL_GPR = 1, MODEL_GPC = 2, MODEL_SGPR = 3, MODEL_IGPR = 4 };
 
-struct gprc_model {
+// what a handle that lives on a context starts with: gprc_model, gprc_paths, gprc_batch_model, gprc_local_model
+struct Bound {
   gprc_ctx* ctx = nullptr;
   uint64_t ctx_id = 0;
+};
+
+struct gprc_model : Bound {
   int type = 0;
   gprc::KernelSpec ks{};
   int64_t n = 0, d = 0, n_pad = 0;
@@ -90,12 +96,50 @@ bool is_device_ptr(const void* p);
 // workspace slot `slot` of the context, at least `count` doubles (contents undefined)
 int ws_get(gprc_ctx* ctx, int slot, int64_t count, double** out);
 
-struct DevMem {  // scoped device allocation from the current context's pool
+inline int bad(const char* who, const std::string& msg) { set_error(std::string(who) + ": " + msg); return GPRC_ERR_ARG; }
+
+// 0, or GPRC_ERR_ARG with "<who>: <what>" when the handle's context has been destroyed (the handle may only be freed then)
+inline int ctx_gone(const char* who, const Bound& h, const char* what = "the model's context has been destroyed") {
+  return h.ctx && ctx_alive(h.ctx, h.ctx_id) ? 0 : bad(who, what);
+}
+// the *_free entry points: if the context went first its stream is gone (and was synchronised) and its pool too, so f(h) sees ctx == nullptr
+template <class H, class Free>
+int free_bound(H* h, Free f) {
+  if (!h) return 0;
+  if (h->ctx && !ctx_alive(h->ctx, h->ctx_id)) {
+    h->ctx = nullptr;
+    (void)hipDeviceSynchronize();
+  }
+  if (h->ctx && h->ctx->stream) (void)hipStreamSynchronize(h->ctx->stream);
+  f(h);
+  return 0;
+}
+// ... of a handle whose buffers are DevMem members (they know where to go): f is delete_bound<H>, which is also its unique_ptr's deleter
+template <class H>
+void delete_bound(H* h) {
+  if (!h) return;
+  if (h->ctx) (void)hipSetDevice(h->ctx->device);
+  delete h;
+}
+struct BoundDelete {
+  template <class H>
+  void operator()(H* h) const { delete_bound(h); }
+};
+
+// Scoped device allocation from the current context's pool.  It remembers its owner as a handle remembers its context, (pointer, id): a
+// block released after its owner has gone goes straight back to the driver, so a handle's members need no telling when the context dies first.
+struct DevMem {
   double* p = nullptr;
-  gprc_ctx* owner = nullptr;
+  Bound owner;
   size_t bytes = 0;
-  ~DevMem() { if (p) pool_release(owner, p, bytes); }
+  ~DevMem() { reset(); }
+  void reset() {   // releases now; the object is empty again
+    if (p) pool_release(ctx_alive(owner.ctx, owner.ctx_id) ? owner.ctx : nullptr, p, bytes);
+    p = nullptr;
+    bytes = 0;
+  }
   int alloc(int64_t count);
+  int copy_from(hipStream_t s, const double* src, int64_t count);   // alloc + an asynchronous copy of a host or device array
 };
 struct IntMem {  // scoped int buffer, straight from the driver (not pooled)
   int* p = nullptr;
@@ -140,19 +184,61 @@ struct Out {
     dev = tmp.p; ld = rows;
     return 0;
   }
-  int finish(hipStream_t s) {
+  // an optional vector (null p: nothing is set) that the launch may not write whole: with `keep` a host temporary starts as the caller's
+  // array, so what the launch leaves alone comes back as it was
+  int set_keeping(double* p, int64_t cnt, bool keep, hipStream_t s) {
+    if (!p) return 0;
+    GPRC_TRY(set(p, cnt));
+    if (host && keep) GPRC_HIP(hipMemcpyAsync(dev, p, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  int finish(hipStream_t s) {   // nothing to do for an Out that was never set, or set to device memory
     if (cols) GPRC_HIP(hipMemcpy2DAsync(host, sizeof(double) * ld_host, tmp.p, sizeof(double) * ld, sizeof(double) * ld, cols, hipMemcpyDeviceToHost, s));
     else if (host) GPRC_HIP(hipMemcpyAsync(host, tmp.p, tmp.bytes, hipMemcpyDeviceToHost, s));
     return 0;
   }
 };
+// an int array on the device for a host or device destination of `rows` rows of m with pitch ld
+struct IntOut {
+  int* dev = nullptr;
+  int* host = nullptr;
+  DevMem tmp;
+  int64_t ld = 0, ld_host = 0, m = 0, rows = 0;
+  int set(int* p, int64_t ld_out, int64_t rows_, int64_t m_) {
+    dev = p; ld = ld_out; m = m_; rows = rows_;
+    if (is_device_ptr(p)) return 0;
+    host = p; ld_host = ld_out;
+    GPRC_TRY(tmp.alloc((rows * m + 1) / 2));
+    dev = reinterpret_cast<int*>(tmp.p); ld = m;
+    return 0;
+  }
+  int finish(hipStream_t s) {
+    if (host) GPRC_HIP(hipMemcpy2DAsync(host, sizeof(int) * ld_host, dev, sizeof(int) * ld, sizeof(int) * m, rows, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+};
 
-// the end of an entry point: host outputs are copied back, then the stream is waited for
-inline int finish_sync(hipStream_t s, Out& a, Out* b = nullptr) {
-  GPRC_TRY(a.finish(s));
-  if (b) GPRC_TRY(b->finish(s));
+// the end of an entry point: host outputs (Out, IntOut; unset ones are skipped) are copied back in order, then the stream is waited for
+template <class... Outs>
+int finish_sync(hipStream_t s, Outs&... outs) {
+  int rc = 0;
+  ((rc = rc ? rc : outs.finish(s)), ...);
+  GPRC_TRY(rc);
   GPRC_HIP(hipStreamSynchronize(s));
   return 0;
+}
+
+// The tail of an exact gradient whose device sums lack 1/2 and the factors that do not depend on (i, j): sums (n_params) and dnoise in,
+// grad_out (n_params + 1, d / dnoise last) out; all NaN when the model was flagged (!ok)
+inline void half_theta_grad(const KernelSpec& ks, const long double* sums, long double dnoise, bool ok, int n_params, double* grad_out) {
+  if (!ok) {
+    for (int k = 0; k <= n_params; ++k) grad_out[k] = std::numeric_limits<double>::quiet_NaN();
+    return;
+  }
+  long double acc[MAX_PARAMS];   // n_params <= MAX_PARAMS: make_spec
+  for (int k = 0; k < n_params; ++k) acc[k] = 0.5L * sums[k];
+  cross_grad_finish(ks, acc, grad_out);
+  grad_out[n_params] = (double)(0.5L * dnoise);
 }
 
 // ---- gprc_sched.hip ----------------------------------------------------------------------------------

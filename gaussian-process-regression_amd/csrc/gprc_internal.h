@@ -1,7 +1,10 @@
 // gprc_internal.h -- shared declarations of the gfx950 implementation behind include/gprc_native.h.
-// Host-side launchers live next to their kernels; the host layer only composes them, one unit per job (shared types: gprc_host.h):
-//   gprc_ctx.hip    errors, the event profiler, context lifetime, the block pool, workspace slots, argument staging, and the entry
-//                   points that are only staging around one launcher (kernel matrices, class probabilities, combine_all)
+// Host-side launchers live next to their kernels; the host layer only composes them, one unit per job.  What the units share is
+// gprc_host.h: the base of every handle that lives on a context with its liveness check and its free (Bound, ctx_gone, free_bound), device
+// memory that knows whether its owner is alive (DevMem), the staging types (In, Out, IntOut, finish_sync) and bad(who, msg).
+//   gprc_ctx.hip    errors, the event profiler, context lifetime and the registry of live contexts, the block pool, workspace slots,
+//                   DevMem's allocation, and the entry points that are only staging around one launcher (kernel matrices, class
+//                   probabilities, combine_all)
 //   gprc_sched.hip  the factor and solve schedules, chunk workspaces, every schedule knob of the host layer; the layout helpers and
 //                   the gprc_dev_* building blocks
 //   gprc_model.hip  the model pipelines (GPR, extend, GPC, gradients, predict, MVN, eigen) and their entry points
@@ -10,7 +13,8 @@
 //   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict, and
 //                   the stochastic log evidence with its gradient)
 //   gprc_batch.hip  small GPs in batches: the batched evidence and gradient, the fitted batch (gprc_batch_model) and its predict
-//   gprc_local.hip  the local GPR: device nearest-neighbour search, then one batched small model per test point (on gprc_batch's entry points)
+//   gprc_local.hip  the local GPR: device nearest-neighbour search (one front for both searches), then one batched small model per test
+//                   point (on gprc_batch's entry points); the Vecchia likelihood on the same object
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and

@@ -31,9 +31,8 @@ namespace {
 constexpr int64_t IGPR_MAX_RANK = 1024;
 
 int igpr_usable(const char* who, const gprc_model* m) {
-  if (!m || m->type != MODEL_IGPR) { set_error(std::string(who) + ": not an iterative GPR model"); return GPRC_ERR_ARG; }
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error(std::string(who) + ": the model's context has been destroyed"); return GPRC_ERR_ARG; }
-  return 0;
+  if (!m || m->type != MODEL_IGPR) return bad(who, "not an iterative GPR model");
+  return ctx_gone(who, *m);
 }
 
 // L (rows x r, pitch ldl, DEVICE), piv (r, DEVICE) and the rank; synchronises
@@ -191,9 +190,9 @@ int igpr_probes_dev(gprc_model* m, const double* G1, int64_t ldg1, const double*
 }
 
 int check_probe_args(const char* who, const gprc_model* m, const double* G1, int64_t ldg1, const double* G2, int64_t ldg2, int64_t T) {
-  if (T < 1 || T > 65535) { set_error(std::string(who) + ": the number of probes T must be between 1 and 65535"); return GPRC_ERR_ARG; }
-  if (!G2 || ldg2 < m->n) { set_error(std::string(who) + ": G2 must be non-null with ldg2 >= n"); return GPRC_ERR_ARG; }
-  if (m->rank > 0 && (!G1 || ldg1 < m->rank)) { set_error(std::string(who) + ": G1 must be non-null with ldg1 >= the preconditioner's rank"); return GPRC_ERR_ARG; }
+  if (T < 1 || T > 65535) return bad(who, "the number of probes T must be between 1 and 65535");
+  if (!G2 || ldg2 < m->n) return bad(who, "G2 must be non-null with ldg2 >= n");
+  if (m->rank > 0 && (!G1 || ldg1 < m->rank)) return bad(who, "G1 must be non-null with ldg1 >= the preconditioner's rank");
   return 0;
 }
 
@@ -304,9 +303,7 @@ int gprc_igpr_predict(gprc_model* m, const double* X_star, int64_t ns, double* m
       GPRC_TRY(launch_cg_var(s, ks_blk.p, w.p, n, scur, ov.dev + s0));
     }
   }
-  GPRC_TRY(om.finish(s));
-  if (var_out) GPRC_TRY(ov.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
+  GPRC_TRY(finish_sync(s, om, ov));
   return rc;
 }
 

@@ -19,9 +19,7 @@ using namespace gprc;
 
 constexpr int64_t LGPR_CHUNK = 2048;   // test points per batched fit: 2048 x 128 KiB = 256 MiB of L^-1 at a time
 
-struct gprc_local_model {
-  gprc_ctx* ctx = nullptr;
-  uint64_t ctx_id = 0;
+struct gprc_local_model : Bound {
   int kernel = 0;
   std::vector<double> params;
   double noise = 0.0;
@@ -35,52 +33,23 @@ struct gprc_local_model {
 
 namespace {
 
-int bad(const char* who, const std::string& msg) { set_error(std::string(who) + ": " + msg); return GPRC_ERR_ARG; }
-
-// an int array on the device for a host or device destination of `rows` rows of m with pitch ld
-struct IntOut {
-  int* dev = nullptr;
-  int* host = nullptr;
-  DevMem tmp;
-  int64_t ld = 0, ld_host = 0, m = 0, rows = 0;
-  int set(int* p, int64_t ld_out, int64_t rows_, int64_t m_) {
-    dev = p; ld = ld_out; m = m_; rows = rows_;
-    if (is_device_ptr(p)) return 0;
-    host = p; ld_host = ld_out;
-    GPRC_TRY(tmp.alloc((rows * m + 1) / 2));
-    dev = reinterpret_cast<int*>(tmp.p); ld = m;
-    return 0;
-  }
-  int finish(hipStream_t s) {
-    if (host) GPRC_HIP(hipMemcpy2DAsync(host, sizeof(int) * ld_host, dev, sizeof(int) * ld, sizeof(int) * m, rows, hipMemcpyDeviceToHost, s));
-    return 0;
-  }
+// the queries of a search: the ns points at Xs, or (Xs null) the window [first, first + ns) of X itself, candidates below each
+struct KnnQueries {
+  const double* Xs;
+  int64_t first, ns;
 };
 
 // the search on device pointers, asynchronous: the split, its workspace (released to the pool when this returns: the stream orders its reuse)
-int knn_on_device(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const double* Xs, int64_t ns, const double* scale, int64_t m, int* idx, double* dist,
-                  int64_t ld) {
+int knn_run(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const KnnQueries& q, const double* scale, int64_t m, int* idx, double* dist, int64_t ld) {
   int cus = 0;
   GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   int parts = 1;
   int64_t part_len = 0;
-  knn_split(n, ns, cus, &parts, &part_len);
+  knn_split(q.Xs ? n : q.first + q.ns, q.ns, cus, &parts, &part_len);
   DevMem work;
-  if (parts > 1) GPRC_TRY(work.alloc((int64_t)knn_workspace_doubles(ns, (int)m, parts)));
-  return launch_knn(ctx->stream, X, d, n, Xs, ns, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
-}
-
-// the predecessor-constrained search on device pointers, asynchronous: queries first .. first + count - 1, candidates below each
-int knn_before_on_device(gprc_ctx* ctx, const double* X, int64_t d, int64_t first, int64_t count, const double* scale, int64_t m, int* idx, double* dist,
-                         int64_t ld) {
-  int cus = 0;
-  GPRC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  int parts = 1;
-  int64_t part_len = 0;
-  knn_split(first + count, count, cus, &parts, &part_len);
-  DevMem work;
-  if (parts > 1) GPRC_TRY(work.alloc((int64_t)knn_workspace_doubles(count, (int)m, parts)));
-  return launch_knn_before(ctx->stream, X, d, first, count, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
+  if (parts > 1) GPRC_TRY(work.alloc((int64_t)knn_workspace_doubles(q.ns, (int)m, parts)));
+  if (q.Xs) return launch_knn(ctx->stream, X, d, n, q.Xs, q.ns, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
+  return launch_knn_before(ctx->stream, X, d, q.first, q.ns, scale, (int)m, idx, dist, ld, parts, part_len, work.p);
 }
 
 int check_scale(const char* who, const double* scale, int64_t d) {
@@ -89,40 +58,32 @@ int check_scale(const char* who, const double* scale, int64_t d) {
   return 0;
 }
 
-// idx / dist (rows of m, pitch ld_out, host or device; dist may be null) of the n_star points at X_star
-int knn_any(const char* who, gprc_ctx* ctx, const double* Xdev, int64_t d, int64_t n, const double* X_star, int64_t n_star, const double* scale_dev,
-            int64_t m, int* idx_out, double* dist_out, int64_t ld_out) {
-  hipStream_t s = ctx->stream;
-  In xs;
-  GPRC_TRY(xs.set(s, X_star, d * n_star));
+// The checks of a call with work to do that the two gprc_dev_knn* entry points share.  (The 2^31 limit and ld_out < m are theirs too, but
+// each stands between checks that differ -- of m, of the window -- and two can fire at once: they stay where they are.)
+int knn_checks(const char* who, const int* idx_out, const double* scale, int64_t d) {
+  if (!idx_out) return bad(who, "null output pointer (idx_out)");
+  if (scale && is_device_ptr(scale)) return bad(who, "scale must be host memory");
+  return scale ? check_scale(who, scale, d) : 0;
+}
+
+// idx / dist (rows of m, pitch ld_out, both host or both device; dist may be null) of the queries, which are on the device; synchronises
+int knn_to_caller(const char* who, gprc_ctx* ctx, const double* Xdev, int64_t d, int64_t n, const KnnQueries& q, const double* scale_dev, int64_t m,
+                  int* idx_out, double* dist_out, int64_t ld_out) {
   IntOut idx;
-  GPRC_TRY(idx.set(idx_out, ld_out, n_star, m));
+  GPRC_TRY(idx.set(idx_out, ld_out, q.ns, m));
   Out dist;
   if (dist_out) {
     if (is_device_ptr(dist_out) != (idx.host == nullptr)) return bad(who, "idx_out and dist_out must both be host or both be device memory");
-    if (idx.host) GPRC_TRY(dist.set(dist_out, ld_out, m, n_star));   // compact rows of m, copied back with the caller's pitch
+    if (idx.host) GPRC_TRY(dist.set(dist_out, ld_out, m, q.ns));   // compact rows of m, copied back with the caller's pitch
     else dist.dev = dist_out;
   }
-  GPRC_TRY(knn_on_device(ctx, Xdev, d, n, xs.dev, n_star, scale_dev, m, idx.dev, dist.dev, idx.ld));
-  GPRC_TRY(idx.finish(s));
-  if (dist_out) GPRC_TRY(dist.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  GPRC_TRY(knn_run(ctx, Xdev, d, n, q, scale_dev, m, idx.dev, dist.dev, idx.ld));
+  return finish_sync(ctx->stream, idx, dist);
 }
-
-void free_local_model(gprc_local_model* m) {
-  if (!m) return;
-  if (m->ctx) (void)hipSetDevice(m->ctx->device);
-  else                                   // the context went first: the buffers go straight back to the driver
-    for (DevMem* q : {&m->X, &m->y, &m->scale, &m->nbr}) q->owner = nullptr;
-  delete m;
-}
-struct LocalModelFree { void operator()(gprc_local_model* m) const { free_local_model(m); } };
 
 int alive(const char* who, const gprc_local_model* m) {
   if (!m) return bad(who, "null model");
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) return bad(who, "the model's context has been destroyed");
-  return 0;
+  return ctx_gone(who, *m);
 }
 
 // parameters and noise into the object; an ARD kernel's metric 1 / l_c to the device
@@ -158,15 +119,14 @@ int gprc_dev_knn(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const dou
   if (ld_out < m) return bad(who, "ld_out < m");
   if (n_star == 0) return 0;
   if (!X || !X_star) return bad(who, "null input pointer (X, X_star)");
-  if (!idx_out) return bad(who, "null output pointer (idx_out)");
-  if (scale && is_device_ptr(scale)) return bad(who, "scale must be host memory");
-  if (scale) GPRC_TRY(check_scale(who, scale, d));
+  GPRC_TRY(knn_checks(who, idx_out, scale, d));
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
-  In xin, sc;
+  In xin, sc, xs;
   GPRC_TRY(xin.set(s, X, d * n));
   if (scale) GPRC_TRY(sc.set(s, scale, d));
-  return knn_any(who, ctx, xin.dev, d, n, X_star, n_star, sc.dev, m, idx_out, dist_out, ld_out);
+  GPRC_TRY(xs.set(s, X_star, d * n_star));
+  return knn_to_caller(who, ctx, xin.dev, d, n, {xs.dev, 0, n_star}, sc.dev, m, idx_out, dist_out, ld_out);
 }
 
 int gprc_lgpr_create(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n, const double* y, double noise,
@@ -182,7 +142,7 @@ int gprc_lgpr_create(gprc_ctx* ctx, int kernel, const double* params, int n_para
   if (m < 1) return bad(who, "m < 1");
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
-  std::unique_ptr<gprc_local_model, LocalModelFree> mod(new gprc_local_model);
+  std::unique_ptr<gprc_local_model, BoundDelete> mod(new gprc_local_model);
   mod->ctx = ctx;
   mod->ctx_id = ctx->id;
   mod->kernel = kernel;
@@ -190,10 +150,8 @@ int gprc_lgpr_create(gprc_ctx* ctx, int kernel, const double* params, int n_para
   mod->d = d;
   mod->m = std::min<int64_t>(std::min<int64_t>(m, n), GPRC_BATCH_MAX_N);
   GPRC_TRY(store_params(who, mod.get(), params, n_params, noise));
-  GPRC_TRY(mod->X.alloc(d * n));
-  GPRC_HIP(hipMemcpyAsync(mod->X.p, X, sizeof(double) * (size_t)(d * n), is_device_ptr(X) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-  GPRC_TRY(mod->y.alloc(n));
-  GPRC_HIP(hipMemcpyAsync(mod->y.p, y, sizeof(double) * (size_t)n, is_device_ptr(y) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  GPRC_TRY(mod->X.copy_from(s, X, d * n));
+  GPRC_TRY(mod->y.copy_from(s, y, n));
   GPRC_HIP(hipStreamSynchronize(s));
   *model_out = mod.release();
   return 0;
@@ -215,7 +173,9 @@ int gprc_lgpr_neighbours(gprc_local_model* m, const double* X_star, int64_t n_st
   if (!X_star) return bad(who, "null input pointer (X_star)");
   if (!idx_out) return bad(who, "null output pointer (idx_out)");
   GPRC_TRY(use_device(m->ctx));
-  return knn_any(who, m->ctx, m->X.p, m->d, m->n, X_star, n_star, m->scale.p, m->m, idx_out, dist_out, ld_out);
+  In xs;
+  GPRC_TRY(xs.set(m->ctx->stream, X_star, m->d * n_star));
+  return knn_to_caller(who, m->ctx, m->X.p, m->d, m->n, {xs.dev, 0, n_star}, m->scale.p, m->m, idx_out, dist_out, ld_out);
 }
 
 int gprc_lgpr_predict(gprc_local_model* m, const double* X_star, int64_t n_star, double* mean_out, double* var_out, int* info_out) {
@@ -249,7 +209,7 @@ int gprc_lgpr_predict(gprc_local_model* m, const double* X_star, int64_t n_star,
   for (int64_t j0 = 0; j0 < n_star; j0 += chunk) {
     const int64_t B = std::min<int64_t>(chunk, n_star - j0);
     const double* xs_c = xs.dev + j0 * d;
-    GPRC_TRY(knn_on_device(ctx, m->X.p, d, m->n, xs_c, B, m->scale.p, k, idx_dev, nullptr, k));
+    GPRC_TRY(knn_run(ctx, m->X.p, d, m->n, {xs_c, 0, B}, m->scale.p, k, idx_dev, nullptr, k));
     GPRC_TRY(launch_knn_gather(s, idx_dev, k, m->X.p, m->y.p, d, B, k, Xg.p, yg.p));
     gprc_batch_model* fitted = nullptr;
     GPRC_TRY(gprc_gpr_batch_fit(ctx, m->kernel, B, thetas.data(), n_params, n_params, noises.data(), Xg.p, d, k, d * k, yg.p, k, nullptr, &fitted,
@@ -260,10 +220,7 @@ int gprc_lgpr_predict(gprc_local_model* m, const double* X_star, int64_t n_star,
     GPRC_TRY(rc);
     if (info_out) std::copy(info.begin(), info.begin() + B, info_out + j0);
   }
-  GPRC_TRY(mean.finish(s));
-  if (var_out) GPRC_TRY(var.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  return finish_sync(s, mean, var);
 }
 
 int gprc_dev_knn_before(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, int64_t first, int64_t count, const double* scale, int64_t m, int* idx_out,
@@ -277,27 +234,13 @@ int gprc_dev_knn_before(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, in
   if (ld_out < m) return bad(who, "ld_out < m");
   if (count == 0) return 0;
   if (!X) return bad(who, "null input pointer (X)");
-  if (!idx_out) return bad(who, "null output pointer (idx_out)");
-  if (scale && is_device_ptr(scale)) return bad(who, "scale must be host memory");
-  if (scale) GPRC_TRY(check_scale(who, scale, d));
+  GPRC_TRY(knn_checks(who, idx_out, scale, d));
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
   In xin, sc;
   GPRC_TRY(xin.set(s, X, d * (first + count)));   // no column from first + count on is a candidate or a query
   if (scale) GPRC_TRY(sc.set(s, scale, d));
-  IntOut idx;
-  GPRC_TRY(idx.set(idx_out, ld_out, count, m));
-  Out dist;
-  if (dist_out) {
-    if (is_device_ptr(dist_out) != (idx.host == nullptr)) return bad(who, "idx_out and dist_out must both be host or both be device memory");
-    if (idx.host) GPRC_TRY(dist.set(dist_out, ld_out, m, count));
-    else dist.dev = dist_out;
-  }
-  GPRC_TRY(knn_before_on_device(ctx, xin.dev, d, first, count, sc.dev, m, idx.dev, dist.dev, idx.ld));
-  GPRC_TRY(idx.finish(s));
-  if (dist_out) GPRC_TRY(dist.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  return knn_to_caller(who, ctx, xin.dev, d, first + count, {nullptr, first, count}, sc.dev, m, idx_out, dist_out, ld_out);
 }
 
 int gprc_lgpr_vecchia_prepare(gprc_local_model* m, int64_t m_cond) {
@@ -308,15 +251,11 @@ int gprc_lgpr_vecchia_prepare(gprc_local_model* m, int64_t m_cond) {
   GPRC_TRY(use_device(ctx));
   const int64_t mc = std::min<int64_t>(m_cond, m->n - 1);
   GPRC_HIP(hipStreamSynchronize(ctx->stream));
-  if (m->nbr.p) {   // a second prepare replaces the first
-    pool_release(m->nbr.owner, m->nbr.p, m->nbr.bytes);
-    m->nbr.p = nullptr;
-    m->nbr.bytes = 0;
-  }
+  m->nbr.reset();   // a second prepare replaces the first
   m->m_cond = -1;
   if (mc > 0) {
     GPRC_TRY(m->nbr.alloc((m->n * mc + 1) / 2));
-    GPRC_TRY(knn_before_on_device(ctx, m->X.p, m->d, 0, m->n, m->scale.p, mc, reinterpret_cast<int*>(m->nbr.p), nullptr, mc));
+    GPRC_TRY(knn_run(ctx, m->X.p, m->d, m->n, {nullptr, 0, m->n}, m->scale.p, mc, reinterpret_cast<int*>(m->nbr.p), nullptr, mc));
     GPRC_HIP(hipStreamSynchronize(ctx->stream));
   }
   m->m_cond = mc;
@@ -380,8 +319,7 @@ int gprc_lgpr_vecchia_logp_grad(gprc_local_model* m, const double* params, int n
   }
   std::vector<double> hgrp((size_t)(groups * grp_stride));
   GPRC_HIP(hipMemcpyAsync(hgrp.data(), grp.p, sizeof(double) * hgrp.size(), hipMemcpyDeviceToHost, s));   // waits for dspec's upload too
-  if (cond_out) GPRC_TRY(cond.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
+  GPRC_TRY(finish_sync(s, cond));
   // the groups' rows in order, in long double; 1/2 and the factors of cross_grad_finish once, after the sum over points
   long double value = 0.0L, flagged = 0.0L, dnoise = 0.0L;
   std::vector<long double> acc((size_t)n_params, 0.0L);
@@ -395,18 +333,9 @@ int gprc_lgpr_vecchia_logp_grad(gprc_local_model* m, const double* params, int n
     }
   }
   const bool any = flagged > 0.0L;
-  const double qnan = std::numeric_limits<double>::quiet_NaN();
-  *logp_out = any ? qnan : (double)value;
+  *logp_out = any ? std::numeric_limits<double>::quiet_NaN() : (double)value;
   if (flagged_out) *flagged_out = (int64_t)flagged;
-  if (want_grad) {
-    if (any) {
-      for (int k = 0; k <= n_params; ++k) grad_out[k] = qnan;
-    } else {
-      for (int k = 0; k < n_params; ++k) acc[(size_t)k] *= 0.5L;
-      cross_grad_finish(ks, acc.data(), grad_out);
-      grad_out[n_params] = (double)(0.5L * dnoise);
-    }
-  }
+  if (want_grad) half_theta_grad(ks, acc.data(), dnoise, !any, n_params, grad_out);
   return 0;
 }
 
@@ -418,15 +347,6 @@ int gprc_lgpr_dims(const gprc_local_model* m, int64_t* n_out, int64_t* d_out, in
   return 0;
 }
 
-int gprc_lgpr_free(gprc_local_model* m) {
-  if (!m) return 0;
-  if (m->ctx && !ctx_alive(m->ctx, m->ctx_id)) {   // the context went first: its stream is gone (and was synchronised), its pool too
-    m->ctx = nullptr;
-    (void)hipDeviceSynchronize();
-  }
-  if (m->ctx && m->ctx->stream) (void)hipStreamSynchronize(m->ctx->stream);
-  free_local_model(m);
-  return 0;
-}
+int gprc_lgpr_free(gprc_local_model* m) { return free_bound(m, delete_bound<gprc_local_model>); }
 
 }  // extern "C"

@@ -87,7 +87,7 @@ int alloc_model(gprc_ctx* ctx, int type, const KernelSpec& ks, int64_t n, int64_
 // epsilon when that value is out of range, else null), then an empty model of `type` on the context's device
 int begin_model(const char* who, int type, gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,
                 int64_t n, const double* y, bool out_ok, const char* scalar_bad, ModelPtr& m) {
-  if (!ctx || !X || !y || !out_ok || d < 1 || n < 1) { set_error(std::string(who) + ": bad arguments"); return GPRC_ERR_ARG; }
+  if (!ctx || !X || !y || !out_ok || d < 1 || n < 1) return bad(who, "bad arguments");
   if (scalar_bad) { set_error(scalar_bad); return GPRC_ERR_ARG; }
   GPRC_TRY(use_device(ctx));
   KernelSpec ks;
@@ -513,7 +513,7 @@ int predict_entry(gprc_model* m, int type, const char* not_type, const char* bad
   GPRC_TRY(a.set(out1, ns));
   GPRC_TRY(b.set(out2, cnt2));
   GPRC_TRY(work(xs.dev, a.dev, b.dev));
-  return finish_sync(s, a, &b);
+  return finish_sync(s, a, b);
 }
 
 // diag((L L^T)^-1) of a factored model, kinv_i = sum_k (L^-1)_ki^2 for i < n (kinv: n_pad doubles; entries past n may be written): the
@@ -656,7 +656,7 @@ int gprc_gpr_logp_grad(gprc_ctx* ctx, int kernel, const double* params, int n_pa
 int gprc_gpr_loo(gprc_model* m, double* mean_out, double* var_out, double* logdens_out, double* loo_out) {
   if (!m || m->type != MODEL_GPR) { set_error("loo: not a GPR model"); return GPRC_ERR_ARG; }
   if (!mean_out && !var_out && !logdens_out && !loo_out) { set_error("loo: all four outputs are null"); return GPRC_ERR_ARG; }
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("loo: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(ctx_gone("loo", *m));
   gprc_ctx* ctx = m->ctx;
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
@@ -673,10 +673,7 @@ int gprc_gpr_loo(gprc_model* m, double* mean_out, double* var_out, double* logde
   GPRC_TRY(launch_loo_point(s, m->alpha, m->y, kinv.p, nullptr, 0, n, n_pad, om.dev, ov.dev, ell_dev, nullptr, nullptr, nullptr));
   std::vector<double> hl(loo_out ? (size_t)n : 0);
   if (loo_out) GPRC_HIP(hipMemcpyAsync(hl.data(), ell_dev, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  if (mean_out) GPRC_TRY(om.finish(s));
-  if (var_out) GPRC_TRY(ov.finish(s));
-  if (logdens_out) GPRC_TRY(ol.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
+  GPRC_TRY(finish_sync(s, om, ov, ol));
   if (loo_out) *loo_out = sum_in_order(hl.data(), n);
   return 0;
 }
@@ -782,7 +779,7 @@ int gprc_gpr_predict_grad(gprc_model* m, const double* X_star, int64_t ns, doubl
   if (ns < 1 || !X_star) { set_error("predict_grad: bad arguments (n_star >= 1, non-null X_star)"); return GPRC_ERR_ARG; }
   if (!mean_out && !var_out && !dmean_out && !dvar_out) { set_error("predict_grad: all four outputs are null"); return GPRC_ERR_ARG; }
   GPRC_TRY(check_grad_kernel("predict_grad", m->ks.id));
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("predict_grad: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(ctx_gone("predict_grad", *m));
   gprc_ctx* ctx = m->ctx;
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
@@ -808,12 +805,7 @@ int gprc_gpr_predict_grad(gprc_model* m, const double* X_star, int64_t ns, doubl
     GPRC_TRY(predict_chunk(m, xs.dev + s0 * d, mcur, vt, ldv, part, tmp, nullptr, false, mean_out ? om.dev + s0 : nullptr,
                            var_out ? ov.dev + s0 : nullptr, pmean.p, pvar.p, dmean_out ? odm.dev + s0 * d : nullptr, dvar_out ? odv.dev + s0 * d : nullptr));
   }
-  if (mean_out) GPRC_TRY(om.finish(s));
-  if (var_out) GPRC_TRY(ov.finish(s));
-  if (dmean_out) GPRC_TRY(odm.finish(s));
-  if (dvar_out) GPRC_TRY(odv.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  return finish_sync(s, om, ov, odm, odv);
 }
 
 int gprc_gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const double* y_new) {
@@ -824,7 +816,7 @@ int gprc_gpr_extend(gprc_model* m, const double* X_new, int64_t mnew, const doub
     return GPRC_ERR_ARG;
   }
   if (mnew < 1 || !X_new || !y_new) { set_error("extend: bad arguments (m >= 1 observations, non-null X_new and y_new)"); return GPRC_ERR_ARG; }
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("extend: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(ctx_gone("extend", *m));
   GPRC_TRY(use_device(m->ctx));
   int info = 0;
   GPRC_TRY(gpr_extend(m, X_new, mnew, y_new, &info));
@@ -872,16 +864,7 @@ static int get_scalar(const gprc_model* m, int type, const char* not_type, doubl
 int gprc_gpr_get_alpha(gprc_model* m, double* alpha_out) { return get_vector(m, MODEL_GPR, "not a GPR model", &gprc_model::alpha, alpha_out); }
 int gprc_gpr_get_logp(gprc_model* m, double* logp_out) { return get_scalar(m, MODEL_GPR, "not a GPR model", &gprc_model::logp, logp_out); }
 int gprc_gpr_get_noise(gprc_model* m, double* noise_out) { return get_scalar(m, MODEL_GPR, "not a GPR model", &gprc_model::noise, noise_out); }
-int gprc_model_free(gprc_model* m) {
-  if (!m) return 0;
-  if (m->ctx && !ctx_alive(m->ctx, m->ctx_id)) {   // the context went first: its stream is gone (and was synchronised), its pool too
-    m->ctx = nullptr;                   // -> the buffers go straight back to the driver
-    (void)hipDeviceSynchronize();
-  }
-  if (m->ctx && m->ctx->stream) (void)hipStreamSynchronize(m->ctx->stream);
-  free_model(m);
-  return 0;
-}
+int gprc_model_free(gprc_model* m) { return free_bound(m, free_model); }   // ctx == nullptr: the buffers go straight back to the driver
 
 // ---- GPC ----------------------------------------------------------------------------------------
 int gprc_gpc_fit(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d,

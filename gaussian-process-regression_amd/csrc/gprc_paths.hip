@@ -14,7 +14,6 @@
 // eval_grad: the same two products differentiated with respect to the test point (gen_gemm_grad; the values, when asked for, by eval's
 // own two launches); rows x S x d x stripes doubles per chunk.  gprc_dev_feature_gemm_grad / gprc_dev_kernel_gemm_grad: each alone.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <memory>
 #include <new>
@@ -24,37 +23,17 @@
 
 using namespace gprc;
 
-struct gprc_paths {
-  gprc_ctx* ctx = nullptr;
-  uint64_t ctx_id = 0;
+struct gprc_paths : Bound {
   KernelSpec ks{};
   int64_t n = 0, d = 0, D = 0, S = 0;
-  double* X = nullptr;       // d x n: the training points at creation
-  double* Nu = nullptr;      // d x D, cycles
-  double* phase = nullptr;   // D, turns
-  double* W = nullptr;       // D x S
-  double* U = nullptr;       // n x S
+  DevMem X;       // d x n: the training points at creation
+  DevMem Nu;      // d x D, cycles
+  DevMem phase;   // D, turns
+  DevMem W;       // D x S
+  DevMem U;       // n x S
 };
 
 namespace gprc {
-
-namespace {
-
-// the device buffers of a paths object and their sizes in doubles
-std::array<std::pair<double**, int64_t>, 5> paths_parts(gprc_paths* p) {
-  return {{{&p->X, p->d * p->n}, {&p->Nu, p->d * p->D}, {&p->phase, p->D}, {&p->W, p->D * p->S}, {&p->U, p->n * p->S}}};
-}
-
-void free_paths(gprc_paths* p) {
-  if (!p) return;
-  if (p->ctx) (void)hipSetDevice(p->ctx->device);
-  for (const auto& pr : paths_parts(p))
-    if (*pr.first) pool_release(p->ctx, *pr.first, sizeof(double) * (size_t)pr.second);
-  delete p;
-}
-struct PathsFree { void operator()(gprc_paths* p) const { free_paths(p); } };
-
-}  // namespace
 
 // One generated-operand product over all rows, in chunks: a chunk's partials are rows x S x stripes doubles, sized by the context's chunk
 // budget (at most 1 GiB).  Results do not depend on the chunking, bit for bit (kernels_paths.hip).
@@ -94,9 +73,8 @@ int gen_gemm_grad(gprc_ctx* ctx, const KernelSpec* ks, const double* Bp, const d
 }
 
 int paths_usable(const char* who, const gprc_paths* p) {
-  if (!p) { set_error(std::string(who) + ": null paths object"); return GPRC_ERR_ARG; }
-  if (!p->ctx || !ctx_alive(p->ctx, p->ctx_id)) { set_error(std::string(who) + ": the context of the paths has been destroyed"); return GPRC_ERR_ARG; }
-  return 0;
+  if (!p) return bad(who, "null paths object");
+  return ctx_gone(who, *p, "the context of the paths has been destroyed");
 }
 
 }  // namespace
@@ -122,7 +100,7 @@ int gprc_gpr_paths_create(gprc_model* m, const double* Nu, const double* phase, 
     set_error("paths_create: defined for sqrexp, gammaexp, rationalquadratic and sqrexp_ard, matern32, matern52, matern32_ard and matern52_ard");
     return GPRC_ERR_ARG;
   }
-  if (!m->ctx || !ctx_alive(m->ctx, m->ctx_id)) { set_error("paths_create: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(ctx_gone("paths_create", *m));
   gprc_ctx* ctx = m->ctx;
   GPRC_TRY(use_device(ctx));
   hipStream_t s = ctx->stream;
@@ -132,23 +110,23 @@ int gprc_gpr_paths_create(gprc_model* m, const double* Nu, const double* phase, 
   GPRC_TRY(ph.set(s, phase, D));
   GPRC_TRY(w.set(s, W, D * S));
   GPRC_TRY(e.set(s, E, n * S));
-  std::unique_ptr<gprc_paths, PathsFree> p(new (std::nothrow) gprc_paths());
+  std::unique_ptr<gprc_paths, BoundDelete> p(new (std::nothrow) gprc_paths());
   if (!p) { set_error("out of host memory"); return GPRC_ERR_NOMEM; }
   p->ctx = ctx; p->ctx_id = ctx->id; p->ks = m->ks; p->n = n; p->d = d; p->D = D; p->S = S;
-  for (const auto& pr : paths_parts(p.get())) GPRC_TRY(pool_alloc(ctx, sizeof(double) * (size_t)pr.second, (void**)pr.first));
-  GPRC_HIP(hipMemcpyAsync(p->X, m->X, sizeof(double) * d * n, hipMemcpyDeviceToDevice, s));
-  GPRC_HIP(hipMemcpyAsync(p->Nu, nu.dev, sizeof(double) * d * D, hipMemcpyDeviceToDevice, s));
-  GPRC_HIP(hipMemcpyAsync(p->phase, ph.dev, sizeof(double) * D, hipMemcpyDeviceToDevice, s));
-  GPRC_HIP(hipMemcpyAsync(p->W, w.dev, sizeof(double) * D * S, hipMemcpyDeviceToDevice, s));
+  GPRC_TRY(p->X.copy_from(s, m->X, d * n));
+  GPRC_TRY(p->Nu.copy_from(s, nu.dev, d * D));
+  GPRC_TRY(p->phase.copy_from(s, ph.dev, D));
+  GPRC_TRY(p->W.copy_from(s, w.dev, D * S));
+  GPRC_TRY(p->U.alloc(n * S));
   if (!iterative) GPRC_TRY(ensure_reversed_factor(m));
   // the prior term at the training points, sqrt(2 / D) Phi(X) W, into U's buffer
-  GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu, p->phase, D, p->X, n, d, p->W, D, S, std::sqrt(2.0 / (double)D), false, p->U, n));
+  GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu.p, p->phase.p, D, p->X.p, n, d, p->W.p, D, S, std::sqrt(2.0 / (double)D), false, p->U.p, n));
   if (iterative) {   // U = K_y^-1 (y - prior - sqrt(noise) E) in blocks of right-hand sides (gprc_iter.hip)
     DevMem rhs;
     GPRC_TRY(rhs.alloc(n * S));
-    GPRC_HIP(hipMemcpyAsync(rhs.p, p->U, sizeof(double) * n * S, hipMemcpyDeviceToDevice, s));
+    GPRC_HIP(hipMemcpyAsync(rhs.p, p->U.p, sizeof(double) * n * S, hipMemcpyDeviceToDevice, s));
     GPRC_TRY(launch_paths_rhs(s, m->y, rhs.p, n, e.dev, n, std::sqrt(m->noise), n, S));
-    GPRC_TRY(igpr_solve_dev(m, rhs.p, n, S, p->U, n, nullptr, nullptr, nullptr));
+    GPRC_TRY(igpr_solve_dev(m, rhs.p, n, S, p->U.p, n, nullptr, nullptr, nullptr));
     GPRC_HIP(hipStreamSynchronize(s));
     *paths_out = p.release();
     return 0;
@@ -160,11 +138,11 @@ int gprc_gpr_paths_create(gprc_model* m, const double* Nu, const double* phase, 
   const double sqn = std::sqrt(m->noise);
   for (int64_t s0 = 0; s0 < S; s0 += rows) {
     const int64_t scur = std::min(rows, S - s0), m_pad = pad_up(scur, NBI);
-    GPRC_TRY(launch_paths_residual(s, m->y, p->U, n, e.dev, n, sqn, s0, scur, n, m_pad, n_pad, vt, ldv));
+    GPRC_TRY(launch_paths_residual(s, m->y, p->U.p, n, e.dev, n, sqn, s0, scur, n, m_pad, n_pad, vt, ldv));
     GPRC_TRY(solve_rows(ctx, m->packed, m->winv, n_pad, vt, ldv, m_pad));            // R L^-T
     GPRC_TRY(launch_reverse_cols(s, vt, ldv, m_pad, n_pad));
     GPRC_TRY(solve_rows(ctx, m->packed_rev, m->winv_rev, n_pad, vt, ldv, m_pad));    // (R L^-T L^-1) J
-    GPRC_TRY(launch_paths_weights(s, vt, ldv, n_pad, s0, scur, n, p->U, n));
+    GPRC_TRY(launch_paths_weights(s, vt, ldv, n_pad, s0, scur, n, p->U.p, n));
   }
   GPRC_HIP(hipStreamSynchronize(s));   // the staged inputs go out of scope
   *paths_out = p.release();
@@ -182,8 +160,8 @@ int gprc_gpr_paths_eval(gprc_paths* p, const double* X_star, int64_t ns, double*
   Out o;
   GPRC_TRY(xs.set(s, X_star, p->d * ns));
   GPRC_TRY(o.set(out, ld_out, ns, p->S));
-  GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu, p->phase, p->D, xs.dev, ns, p->d, p->W, p->D, p->S, std::sqrt(2.0 / (double)p->D), false, o.dev, o.ld));
-  GPRC_TRY(gen_gemm(ctx, &p->ks, p->X, nullptr, p->n, xs.dev, ns, p->d, p->U, p->n, p->S, 1.0, true, o.dev, o.ld));
+  GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu.p, p->phase.p, p->D, xs.dev, ns, p->d, p->W.p, p->D, p->S, std::sqrt(2.0 / (double)p->D), false, o.dev, o.ld));
+  GPRC_TRY(gen_gemm(ctx, &p->ks, p->X.p, nullptr, p->n, xs.dev, ns, p->d, p->U.p, p->n, p->S, 1.0, true, o.dev, o.ld));
   return finish_sync(s, o);
 }
 
@@ -203,19 +181,19 @@ int gprc_gpr_paths_eval_grad(gprc_paths* p, const double* X_star, int64_t ns, do
   GPRC_TRY(g.set(dout, ld_dout, ns, p->S * p->d));
   if (out) {   // the launches of gprc_gpr_paths_eval with its arguments: its bits
     GPRC_TRY(o.set(out, ld_out, ns, p->S));
-    GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu, p->phase, p->D, xs.dev, ns, p->d, p->W, p->D, p->S, scale, false, o.dev, o.ld));
-    GPRC_TRY(gen_gemm(ctx, &p->ks, p->X, nullptr, p->n, xs.dev, ns, p->d, p->U, p->n, p->S, 1.0, true, o.dev, o.ld));
+    GPRC_TRY(gen_gemm(ctx, nullptr, p->Nu.p, p->phase.p, p->D, xs.dev, ns, p->d, p->W.p, p->D, p->S, scale, false, o.dev, o.ld));
+    GPRC_TRY(gen_gemm(ctx, &p->ks, p->X.p, nullptr, p->n, xs.dev, ns, p->d, p->U.p, p->n, p->S, 1.0, true, o.dev, o.ld));
   }
-  GPRC_TRY(gen_gemm_grad(ctx, nullptr, p->Nu, p->phase, p->D, xs.dev, ns, p->d, p->W, p->D, p->S, scale, false, g.dev, g.ld));
-  GPRC_TRY(gen_gemm_grad(ctx, &p->ks, p->X, nullptr, p->n, xs.dev, ns, p->d, p->U, p->n, p->S, 1.0, true, g.dev, g.ld));
-  return out ? finish_sync(s, g, &o) : finish_sync(s, g);
+  GPRC_TRY(gen_gemm_grad(ctx, nullptr, p->Nu.p, p->phase.p, p->D, xs.dev, ns, p->d, p->W.p, p->D, p->S, scale, false, g.dev, g.ld));
+  GPRC_TRY(gen_gemm_grad(ctx, &p->ks, p->X.p, nullptr, p->n, xs.dev, ns, p->d, p->U.p, p->n, p->S, 1.0, true, g.dev, g.ld));
+  return finish_sync(s, g, o);
 }
 
 int gprc_gpr_paths_get_weights(gprc_paths* p, double* U_out) {
   GPRC_TRY(paths_usable("paths_get_weights", p));
   if (!U_out) { set_error("paths_get_weights: null output"); return GPRC_ERR_ARG; }
   GPRC_TRY(use_device(p->ctx));
-  GPRC_HIP(hipMemcpyAsync(U_out, p->U, sizeof(double) * p->n * p->S, hipMemcpyDefault, p->ctx->stream));
+  GPRC_HIP(hipMemcpyAsync(U_out, p->U.p, sizeof(double) * p->n * p->S, hipMemcpyDefault, p->ctx->stream));
   GPRC_HIP(hipStreamSynchronize(p->ctx->stream));
   return 0;
 }
@@ -229,16 +207,7 @@ int gprc_gpr_paths_dims(const gprc_paths* p, int64_t* n_out, int64_t* d_out, int
   return 0;
 }
 
-int gprc_gpr_paths_free(gprc_paths* p) {
-  if (!p) return 0;
-  if (p->ctx && !ctx_alive(p->ctx, p->ctx_id)) {   // the context went first: the buffers go straight back to the driver (as gprc_model_free)
-    p->ctx = nullptr;
-    (void)hipDeviceSynchronize();
-  }
-  if (p->ctx && p->ctx->stream) (void)hipStreamSynchronize(p->ctx->stream);
-  free_paths(p);
-  return 0;
-}
+int gprc_gpr_paths_free(gprc_paths* p) { return free_bound(p, delete_bound<gprc_paths>); }
 
 int gprc_dev_feature_gemm(gprc_ctx* ctx, const double* Nu, const double* phase, int64_t D, const double* A, int64_t rows, int64_t d, const double* W,
                           int64_t ldw, int64_t S, double scale, double* out, int64_t ld) {

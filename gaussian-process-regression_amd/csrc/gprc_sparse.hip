@@ -35,10 +35,10 @@ struct SgprArgs {
 };
 
 int sgpr_check(const char* who, gprc_ctx* ctx, const SgprArgs& a, bool out_ok) {
-  if (!ctx || !a.X || !a.y || !a.Z || !out_ok || a.d < 1) { set_error(std::string(who) + ": bad arguments (null pointer or d < 1)"); return GPRC_ERR_ARG; }
-  if (a.n < 1 || a.m < 1) { set_error(std::string(who) + ": n >= 1 training points and m >= 1 inducing points"); return GPRC_ERR_ARG; }
-  if (!(a.noise > 0.0) || !std::isfinite(a.noise)) { set_error(std::string(who) + ": noise must be finite and > 0"); return GPRC_ERR_ARG; }
-  if (!(a.jitter >= 0.0) || !std::isfinite(a.jitter)) { set_error(std::string(who) + ": jitter must be finite and >= 0"); return GPRC_ERR_ARG; }
+  if (!ctx || !a.X || !a.y || !a.Z || !out_ok || a.d < 1) return bad(who, "bad arguments (null pointer or d < 1)");
+  if (a.n < 1 || a.m < 1) return bad(who, "n >= 1 training points and m >= 1 inducing points");
+  if (!(a.noise > 0.0) || !std::isfinite(a.noise)) return bad(who, "noise must be finite and > 0");
+  if (!(a.jitter >= 0.0) || !std::isfinite(a.jitter)) return bad(who, "jitter must be finite and >= 0");
   return 0;
 }
 
@@ -376,7 +376,7 @@ int gprc_sgpr_get_elbo(gprc_model* model, double* elbo_out, double* trace_out) {
 
 int gprc_sgpr_get_c(gprc_model* model, double* c_out) {
   if (!model || model->type != MODEL_SGPR || !c_out) { set_error("sgpr_get_c: not a sparse GPR model (or a null output)"); return GPRC_ERR_ARG; }
-  if (!model->ctx || !ctx_alive(model->ctx, model->ctx_id)) { set_error("sgpr_get_c: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(ctx_gone("sgpr_get_c", *model));
   GPRC_TRY(use_device(model->ctx));
   GPRC_HIP(hipMemcpyAsync(c_out, model->alpha, sizeof(double) * model->n, hipMemcpyDefault, model->ctx->stream));
   GPRC_HIP(hipStreamSynchronize(model->ctx->stream));
@@ -386,7 +386,7 @@ int gprc_sgpr_get_c(gprc_model* model, double* c_out) {
 int gprc_sgpr_predict(gprc_model* mo, const double* X_star, int64_t ns, double* mean_out, double* var_out) {
   if (!mo || mo->type != MODEL_SGPR) { set_error("sgpr_predict: not a sparse GPR model"); return GPRC_ERR_ARG; }
   if (ns < 0 || (ns > 0 && !X_star) || (!mean_out && !var_out)) { set_error("sgpr_predict: bad arguments (non-null X_star, at least one output)"); return GPRC_ERR_ARG; }
-  if (!mo->ctx || !ctx_alive(mo->ctx, mo->ctx_id)) { set_error("sgpr_predict: the model's context has been destroyed"); return GPRC_ERR_ARG; }
+  GPRC_TRY(ctx_gone("sgpr_predict", *mo));
   if (ns == 0) return 0;
   gprc_ctx* ctx = mo->ctx;
   GPRC_TRY(use_device(ctx));
@@ -407,10 +407,7 @@ int gprc_sgpr_predict(gprc_model* mo, const double* X_star, int64_t ns, double* 
     const int64_t mcur = std::min<int64_t>(rows, ns - s0);
     GPRC_TRY(sgpr_predict_chunk(mo, xs.dev + s0 * mo->d, mcur, vt, ldv, part, kss, red.p, mean_out ? om.dev + s0 : nullptr, var_out ? ov.dev + s0 : nullptr));
   }
-  if (mean_out) GPRC_TRY(om.finish(s));
-  if (var_out) GPRC_TRY(ov.finish(s));
-  GPRC_HIP(hipStreamSynchronize(s));
-  return 0;
+  return finish_sync(s, om, ov);
 }
 
 }  // extern "C"

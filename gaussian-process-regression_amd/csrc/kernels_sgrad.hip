@@ -288,19 +288,8 @@ int launch_cross_grad_sum(hipStream_t s, const KernelSpec& ks, const double* pz,
   if (cols <= 0) return 0;
   GPRC_TRY(check_grad_kernel("cross_grad", ks.id));
   // the factor that does not depend on (i, j) (ARD: its constant times 1 / l_c per coordinate, from the spec)
-  const double il2 = 1.0 / (ks.p[0] * ks.p[0]);
-  double iso = il2;
-  switch (ks.id) {
-    case GPRC_GAMMAEXP: iso = ks.p[1]; break;
-    case GPRC_SQREXP_ARD: iso = 1.0; break;
-    case GPRC_MATERN32: iso = 3.0 * il2; break;
-    case GPRC_MATERN52: iso = 5.0 / 3.0 * il2; break;
-    case GPRC_MATERN32_ARD: iso = 3.0; break;
-    case GPRC_MATERN52_ARD: iso = 5.0 / 3.0; break;
-    default: break;
-  }
   hipLaunchKernelGGL(cross_grad_sum_kernel, dim3((unsigned)((cols * d + 255) / 256)), dim3(256), 0, s, pz, cross_grad_stripes(rows_pad), d, cols_pad, cols,
-                     f * iso, is_ard(ks.id) ? 1 : 0, make_deriv_spec(ks), dZ);
+                     f * deriv_tail_factor(ks), is_ard(ks.id) ? 1 : 0, make_deriv_spec(ks), dZ);
   GPRC_LAUNCH_CHECK();
   return 0;
 }
