@@ -70,6 +70,11 @@ PROTOTYPES = {
     "gprc_gpr_batch_get_alpha": (C.c_int, [_vp, _vp]),
     "gprc_batch_model_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_batch_model_free": (C.c_int, [_vp]),
+    "gprc_gpc_batch_fit": (C.c_int, [_vp, C.c_int, _i64, _vp, C.c_int, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.c_double, C.c_int, C.POINTER(_vp), _vp, _vp,
+                                     _vp]),
+    "gprc_gpc_batch_predict_latent": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64]),
+    "gprc_gpc_batch_predict_class": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64]),
+    "gprc_gpc_batch_get_f_hat": (C.c_int, [_vp, _vp]),
     "gprc_dev_knn": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64]),
     "gprc_lgpr_create": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, C.c_double, _i64, C.POINTER(_vp)]),
     "gprc_lgpr_set_params": (C.c_int, [_vp, _dp, C.c_int, C.c_double]),
@@ -77,6 +82,9 @@ PROTOTYPES = {
     "gprc_lgpr_neighbours": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64]),
     "gprc_lgpr_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gprc_lgpr_free": (C.c_int, [_vp]),
+    "gprc_lgpc_create": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _i64, _vp, _i64, C.c_double, C.c_int, C.POINTER(_vp)]),
+    "gprc_lgpc_set_params": (C.c_int, [_vp, _dp, C.c_int]),
+    "gprc_lgpc_predict": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gprc_dev_knn_before": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64]),
     "gprc_lgpr_vecchia_prepare": (C.c_int, [_vp, _i64]),
     "gprc_lgpr_vecchia_logp_grad": (C.c_int, [_vp, _dp, C.c_int, C.c_double, C.POINTER(C.c_double), _vp, _vp, C.POINTER(_i64)]),

@@ -205,7 +205,9 @@ __device__ __forceinline__ void potf2_phase_c_block(double* S, const double* Wd,
 // [3 + 2 s] / [4 + 2 s] after the two barriers of step s, [19] exit (stores issued).  Measurement only.
 #define POTF2_STAMP(k) do { if (ptr && threadIdx.x == 0) ptr[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
 // preloaded: S already holds the block (gemm_tile_128<.., LDSOUT>), the loads from A are skipped.
-template <int NW>
+// STORE = false (kernels_batch_gpc.hip, which factors again and again and reads the image): L and the inverse stay in the LDS image and
+// nothing goes to A or winv, which may be null with `preloaded`; the default is every other caller's code, instruction for instruction.
+template <int NW, bool STORE = true>
 __device__ __attribute__((noinline)) void potf2_blocked_body(double* sm, double* A, int64_t lda, double* winv, int* info, int col0,
                                                              unsigned long long* ptr = nullptr, bool preloaded = false) {
   static_assert(NW >= 8, "phase B needs one wave per task: 7 tasks per step");
@@ -273,7 +275,7 @@ __device__ __attribute__((noinline)) void potf2_blocked_body(double* sm, double*
     __syncthreads();
     POTF2_STAMP(4 + 2 * s);
   }
-  {
+  if constexpr (STORE) {
     const int i = t & 127, ty = t >> 7;
     const double wd = Wdiag[i];
     constexpr int BATCH = 8;

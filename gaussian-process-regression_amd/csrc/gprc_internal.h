@@ -12,9 +12,10 @@
 //   gprc_paths.hip  posterior sample paths by pathwise conditioning (the gprc_paths object, create, eval and eval_grad) and their entry points
 //   gprc_iter.hip   the iterative exact GPR (pivoted-Cholesky preconditioner, batched conjugate gradients, fit / solve / predict, and
 //                   the stochastic log evidence with its gradient)
-//   gprc_batch.hip  small GPs in batches: the batched evidence and gradient, the fitted batch (gprc_batch_model) and its predict
+//   gprc_batch.hip  small GPs in batches: the batched evidence and gradient, the fitted batch (gprc_batch_model) and its predict; the
+//                   classifier batch (the Laplace mode search of kernels_batch_gpc.hip) on the same object and the same predict launch
 //   gprc_local.hip  the local GPR: device nearest-neighbour search (one front for both searches), then one batched small model per test
-//                   point (on gprc_batch's entry points); the Vecchia likelihood on the same object
+//                   point (on gprc_batch's entry points); the Vecchia likelihood on the same object; the local classifier likewise
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
 // Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
@@ -288,6 +289,35 @@ int launch_batch_predict(hipStream_t s, int kernel, const BatchPredictArgs& a, i
 // The same launch with the gradients with respect to the test points (the same kernel body behind a template flag: mean and var keep
 // launch_batch_predict's bits):  dmean = -t_c sum_k alpha_k h_k (x*_c - x_kc),  dvar = 2 t_c sum_k u_k h_k (x*_c - x_kc),  u = W^T (W k*).
 int launch_batch_predict_grad(hipStream_t s, int kernel, const BatchPredictArgs& a, int64_t models, int split);
+
+// ---- launchers (kernels_batch_gpc.hip: small Laplace classifiers in batches) -----------------------
+// One classifier of n_b <= GPRC_BATCH_MAX_N points per workgroup: K, the whole Newton loop of the mode search and the final factorisation
+// in one launch of `models` <= GPRC_BATCH_LAUNCH workgroups; workgroup g handles model b0 + g.  Per model b (all DEVICE memory):
+//   prm, X, y            as BatchArgs' (the record's noise slot is not read; y in {-1, +1})
+//   logq + b, iters + b (iters may be null), info + b (zeroed by the caller): the Laplace evidence, the iterations, and 0, the first
+//                        non-positive pivot (1-based), GPRC_BATCH_GPC_MAXITER or GPRC_BATCH_GPC_NONFINITE; a flagged model's logq is NaN
+//   alpha + b 128        g = (y + 1) / 2 - pi at the mode;   fhat + b 128: the mode (both zero from n_b on, NaN when flagged)
+//   w + b 128^2          L^-1 diag(sw) of B = I + sw K sw = L L^T in BatchArgs::w's layout: launch_batch_predict on (alpha, w) is the
+//                        latent prediction of gprc_gpc_predict_latent
+// slab: batch_gpc_scratch_doubles(models) doubles, K of workgroup g at slab + g 128^2.  Kernels: those of with_gradient_kernel.
+constexpr int GPRC_BATCH_GPC_MAX_ITER = 1000;   // the loop is bounded on the device: the host refuses more
+struct BatchGpcArgs {
+  const double* X;
+  const double* y;
+  const double* prm;
+  double* slab;
+  double* logq;
+  int* iters;
+  double* alpha;
+  double* fhat;
+  double* w;
+  int* info;
+  int64_t x_stride, y_stride, d, b0;
+  int prm_stride, np_store, n_params, max_iter;
+  double epsilon;
+};
+size_t batch_gpc_scratch_doubles(int64_t models);
+int launch_batch_gpc_fit(hipStream_t s, int kernel, const BatchGpcArgs& a, int64_t models);
 
 // ---- launchers (kernels_batch_loo.hip: leave-one-out from a fitted batch) --------------------------
 // One workgroup per model, model b0 + g: p_i = sum_{k >= i} W[k + 128 i]^2, mean_i = y_i - alpha_i / p_i, var_i = 1 / p_i,

@@ -7,6 +7,8 @@
 // (the conditioning sets, searched once and kept as n x m_cond indices), gprc_lgpr_vecchia_logp_grad (launches of kernels_vecchia.hip over
 // chunks of GPRC_VECCHIA_CHUNK points, the groups' rows added in order in long double, 1/2 and cross_grad_finish once) and
 // gprc_lgpr_vecchia_neighbours.
+// The local classifier ("Batched and local GPC"): gprc_lgpc_* on the same object with a kind tag -- the same search
+// and gather, then gprc_gpc_batch_fit, the latent prediction and the class probability, one Laplace classifier per test point.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -19,7 +21,11 @@ using namespace gprc;
 
 constexpr int64_t LGPR_CHUNK = 2048;   // test points per batched fit: 2048 x 128 KiB = 256 MiB of L^-1 at a time
 
+enum LocalKind { LOCAL_GPR = 0, LOCAL_GPC = 1 };
 struct gprc_local_model : Bound {
+  int kind = LOCAL_GPR;
+  double epsilon = 0.0;   // LOCAL_GPC: the mode search's stop threshold and its cap
+  int max_iter = 0;
   int kernel = 0;
   std::vector<double> params;
   double noise = 0.0;
@@ -105,6 +111,48 @@ int store_params(const char* who, gprc_local_model* m, const double* params, int
   return 0;
 }
 
+// a regression call on a classifier, or the other way round
+int local_kind(const char* who, const gprc_local_model* m, int kind) {
+  if (m->kind == kind) return 0;
+  return bad(who, kind == LOCAL_GPC ? "the model is a local regression (gprc_lgpr_create): use the gprc_lgpr_* calls"
+                                    : "the model is a local classifier (gprc_lgpc_create): use the gprc_lgpc_* calls");
+}
+
+// what gprc_lgpr_create and gprc_lgpc_create share: the checks, the object with the training set on the device
+int local_create(const char* who, int kind, gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                 const double* y, double noise, int64_t m, double epsilon, int max_iter, gprc_local_model** model_out) {
+  if (model_out) *model_out = nullptr;
+  if (!ctx) return bad(who, "null context");
+  GPRC_TRY(check_grad_kernel(who, kernel));
+  if (!model_out) return bad(who, "null output pointer (model_out)");
+  if (!X || !y) return bad(who, "null input pointer (X, y)");
+  if (d < 1 || n < 1) return bad(who, "d < 1 or n < 1");
+  if (n >= (int64_t(1) << 31)) return bad(who, "n >= 2^31: the neighbour indices are 32-bit");
+  if (m < 1) return bad(who, "m < 1");
+  if (kind == LOCAL_GPC) {
+    if (!(epsilon > 0.0)) return bad(who, "epsilon must be > 0");
+    if (max_iter > GPRC_BATCH_GPC_MAX_ITER) return bad(who, "max_iter > 1000");
+  }
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  std::unique_ptr<gprc_local_model, BoundDelete> mod(new gprc_local_model);
+  mod->ctx = ctx;
+  mod->ctx_id = ctx->id;
+  mod->kind = kind;
+  mod->epsilon = epsilon;
+  mod->max_iter = max_iter;
+  mod->kernel = kernel;
+  mod->n = n;
+  mod->d = d;
+  mod->m = std::min<int64_t>(std::min<int64_t>(m, n), GPRC_BATCH_MAX_N);
+  GPRC_TRY(store_params(who, mod.get(), params, n_params, noise));
+  GPRC_TRY(mod->X.copy_from(s, X, d * n));
+  GPRC_TRY(mod->y.copy_from(s, y, n));
+  GPRC_HIP(hipStreamSynchronize(s));
+  *model_out = mod.release();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -131,35 +179,13 @@ int gprc_dev_knn(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, const dou
 
 int gprc_lgpr_create(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n, const double* y, double noise,
                      int64_t m, gprc_local_model** model_out) {
-  const char* who = "lgpr_create";
-  if (model_out) *model_out = nullptr;
-  if (!ctx) return bad(who, "null context");
-  GPRC_TRY(check_grad_kernel(who, kernel));
-  if (!model_out) return bad(who, "null output pointer (model_out)");
-  if (!X || !y) return bad(who, "null input pointer (X, y)");
-  if (d < 1 || n < 1) return bad(who, "d < 1 or n < 1");
-  if (n >= (int64_t(1) << 31)) return bad(who, "n >= 2^31: the neighbour indices are 32-bit");
-  if (m < 1) return bad(who, "m < 1");
-  GPRC_TRY(use_device(ctx));
-  hipStream_t s = ctx->stream;
-  std::unique_ptr<gprc_local_model, BoundDelete> mod(new gprc_local_model);
-  mod->ctx = ctx;
-  mod->ctx_id = ctx->id;
-  mod->kernel = kernel;
-  mod->n = n;
-  mod->d = d;
-  mod->m = std::min<int64_t>(std::min<int64_t>(m, n), GPRC_BATCH_MAX_N);
-  GPRC_TRY(store_params(who, mod.get(), params, n_params, noise));
-  GPRC_TRY(mod->X.copy_from(s, X, d * n));
-  GPRC_TRY(mod->y.copy_from(s, y, n));
-  GPRC_HIP(hipStreamSynchronize(s));
-  *model_out = mod.release();
-  return 0;
+  return local_create("lgpr_create", LOCAL_GPR, ctx, kernel, params, n_params, X, d, n, y, noise, m, 0.0, 0, model_out);
 }
 
 int gprc_lgpr_set_params(gprc_local_model* m, const double* params, int n_params, double noise) {
   const char* who = "lgpr_set_params";
   GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPR));
   GPRC_TRY(use_device(m->ctx));
   return store_params(who, m, params, n_params, noise);
 }
@@ -181,6 +207,7 @@ int gprc_lgpr_neighbours(gprc_local_model* m, const double* X_star, int64_t n_st
 int gprc_lgpr_predict(gprc_local_model* m, const double* X_star, int64_t n_star, double* mean_out, double* var_out, int* info_out) {
   const char* who = "lgpr_predict";
   GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPR));
   if (n_star < 0) return bad(who, "n_star < 0");
   if (n_star == 0) return 0;
   if (!X_star) return bad(who, "null input pointer (X_star)");
@@ -246,6 +273,7 @@ int gprc_dev_knn_before(gprc_ctx* ctx, const double* X, int64_t d, int64_t n, in
 int gprc_lgpr_vecchia_prepare(gprc_local_model* m, int64_t m_cond) {
   const char* who = "lgpr_vecchia_prepare";
   GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPR));
   if (m_cond < 1 || m_cond > GPRC_BATCH_MAX_N - 1) return bad(who, "m_cond = " + std::to_string(m_cond) + " is outside 1 .. 127");
   gprc_ctx* ctx = m->ctx;
   GPRC_TRY(use_device(ctx));
@@ -265,6 +293,7 @@ int gprc_lgpr_vecchia_prepare(gprc_local_model* m, int64_t m_cond) {
 int gprc_lgpr_vecchia_neighbours(gprc_local_model* m, int* idx_out, int64_t ld_out) {
   const char* who = "lgpr_vecchia_neighbours";
   GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPR));
   if (m->m_cond < 0) return bad(who, "no gprc_lgpr_vecchia_prepare yet");
   if (ld_out < m->m_cond) return bad(who, "ld_out < m_cond");
   if (m->m_cond == 0) return 0;
@@ -280,6 +309,7 @@ int gprc_lgpr_vecchia_logp_grad(gprc_local_model* m, const double* params, int n
                                 int64_t* flagged_out) {
   const char* who = "lgpr_vecchia_logp_grad";
   GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPR));
   if (!params) return bad(who, "null input pointer (params)");
   if (!logp_out) return bad(who, "null output pointer (logp_out)");
   if (!(noise >= 0.0) || !std::isfinite(noise)) return bad(who, "noise must be finite and >= 0");
@@ -337,6 +367,72 @@ int gprc_lgpr_vecchia_logp_grad(gprc_local_model* m, const double* params, int n
   if (flagged_out) *flagged_out = (int64_t)flagged;
   if (want_grad) half_theta_grad(ks, acc.data(), dnoise, !any, n_params, grad_out);
   return 0;
+}
+
+int gprc_lgpc_create(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n, const double* y, int64_t m,
+                     double epsilon, int max_iter, gprc_local_model** model_out) {
+  return local_create("lgpc_create", LOCAL_GPC, ctx, kernel, params, n_params, X, d, n, y, 0.0, m, epsilon, max_iter, model_out);
+}
+
+int gprc_lgpc_set_params(gprc_local_model* m, const double* params, int n_params) {
+  const char* who = "lgpc_set_params";
+  GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPC));
+  GPRC_TRY(use_device(m->ctx));
+  return store_params(who, m, params, n_params, 0.0);
+}
+
+int gprc_lgpc_predict(gprc_local_model* m, const double* X_star, int64_t n_star, double* fs_bar_out, double* Vfs_out, double* prob_out, int* iters_out,
+                      int* info_out) {
+  const char* who = "lgpc_predict";
+  GPRC_TRY(alive(who, m));
+  GPRC_TRY(local_kind(who, m, LOCAL_GPC));
+  if (n_star < 0) return bad(who, "n_star < 0");
+  if (n_star == 0) return 0;
+  if (!X_star) return bad(who, "null input pointer (X_star)");
+  if (!fs_bar_out && !Vfs_out && !prob_out) return bad(who, "null output pointers (fs_bar_out, Vfs_out, prob_out: not all three may be NULL)");
+  if ((iters_out && is_device_ptr(iters_out)) || (info_out && is_device_ptr(info_out))) return bad(who, "iters_out and info_out must be host memory");
+  gprc_ctx* ctx = m->ctx;
+  GPRC_TRY(use_device(ctx));
+  hipStream_t s = ctx->stream;
+  const int64_t d = m->d, k = m->m;
+  const int n_params = (int)m->params.size();
+  In xs;
+  GPRC_TRY(xs.set(s, X_star, d * n_star));
+  Out fs, vf, prob;
+  GPRC_TRY(fs.set_keeping(fs_bar_out, n_star, false, s));
+  GPRC_TRY(vf.set_keeping(Vfs_out, n_star, false, s));
+  GPRC_TRY(prob.set_keeping(prob_out, n_star, false, s));
+  const int64_t chunk = std::min<int64_t>(n_star, LGPR_CHUNK);
+  std::vector<double> thetas((size_t)(chunk * n_params)), logq((size_t)chunk);
+  for (int64_t b = 0; b < chunk; ++b) std::copy(m->params.begin(), m->params.end(), thetas.begin() + b * n_params);
+  std::vector<int> iters((size_t)chunk), info((size_t)chunk);
+  DevMem idx, Xg, yg, fs_tmp, vf_tmp;   // the class probability needs both latent values, asked for or not
+  GPRC_TRY(idx.alloc((chunk * k + 1) / 2));
+  GPRC_TRY(Xg.alloc(chunk * d * k));
+  GPRC_TRY(yg.alloc(chunk * k));
+  if (prob_out && !fs_bar_out) GPRC_TRY(fs_tmp.alloc(chunk));
+  if (prob_out && !Vfs_out) GPRC_TRY(vf_tmp.alloc(chunk));
+  int* idx_dev = reinterpret_cast<int*>(idx.p);
+  for (int64_t j0 = 0; j0 < n_star; j0 += chunk) {
+    const int64_t B = std::min<int64_t>(chunk, n_star - j0);
+    const double* xs_c = xs.dev + j0 * d;
+    GPRC_TRY(knn_run(ctx, m->X.p, d, m->n, {xs_c, 0, B}, m->scale.p, k, idx_dev, nullptr, k));
+    GPRC_TRY(launch_knn_gather(s, idx_dev, k, m->X.p, m->y.p, d, B, k, Xg.p, yg.p));
+    gprc_batch_model* fitted = nullptr;
+    GPRC_TRY(gprc_gpc_batch_fit(ctx, m->kernel, B, thetas.data(), n_params, n_params, Xg.p, d, k, d * k, yg.p, k, nullptr, m->epsilon, m->max_iter, &fitted,
+                                logq.data(), iters.data(), info.data()));
+    // one test point per model, straight into the outputs; a flagged model's point is NaN, and so is its probability
+    double* fsp = fs_bar_out ? fs.dev + j0 : fs_tmp.p;
+    double* vfp = Vfs_out ? vf.dev + j0 : vf_tmp.p;
+    int rc = gprc_gpc_batch_predict_latent(fitted, xs_c, 1, d, nullptr, fsp, vfp, 1);
+    if (rc == 0 && prob_out) rc = launch_gpc_class_prob(s, fsp, vfp, prob.dev + j0, B);
+    gprc_batch_model_free(fitted);
+    GPRC_TRY(rc);
+    if (iters_out) std::copy(iters.begin(), iters.begin() + B, iters_out + j0);
+    if (info_out) std::copy(info.begin(), info.begin() + B, info_out + j0);
+  }
+  return finish_sync(s, fs, vf, prob);
 }
 
 int gprc_lgpr_dims(const gprc_local_model* m, int64_t* n_out, int64_t* d_out, int64_t* m_out) {

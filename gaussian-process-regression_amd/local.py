@@ -17,6 +17,8 @@ nearest-neighbour GP; DESIGN.md section 7, "Vecchia likelihood"): with the order
 LocalGPR.vecchia_prepare searches the conditioning sets once (gprc_dev_knn_before) and freezes them, LocalGPR.vecchia_logp_grad is the
 sum and its exact gradient in one native call (gprc_lgpr_vecchia_logp_grad), fit.optimize_local the optimiser over it.  The order
 matters: vecchia_order gives a random permutation to apply to (X, y) first.
+LocalGPC is the classifier on the same search (gprc_lgpc_*; DESIGN.md section 7, "Batched and local GPC"): every test point gets the
+Laplace GP classifier of its own m nearest training points, fitted in batches on the device.
 Out of scope here: max-min ordering, grouped conditioning sets, Vecchia prediction, gradients at x*.
 """
 from __future__ import annotations
@@ -28,7 +30,7 @@ import numpy as np
 from . import _native as nat
 from .covfunc import as_points, as_test_points, require_tagged
 
-__all__ = ["LocalGPR", "knn", "knn_before", "vecchia_order", "MAX_NEIGHBOURS", "MAX_CONDITIONING", "BATCHED_KERNELS"]
+__all__ = ["LocalGPR", "LocalGPC", "knn", "knn_before", "vecchia_order", "MAX_NEIGHBOURS", "MAX_CONDITIONING", "BATCHED_KERNELS"]
 
 MAX_NEIGHBOURS = 128   # a local model is one batched small model (include/gprc_native.h GPRC_BATCH_MAX_N)
 MAX_CONDITIONING = 127   # a conditional is the model of the conditioning set and the point itself
@@ -223,3 +225,87 @@ class LocalGPR(nat.Handle):
     noise = property(lambda self: self._noise)
     m = property(lambda self: self._m, doc="neighbours per test point, min(m, n)")
     info = property(lambda self: self._info, doc="per test point of the last predict: 0, or the minor of its local model that is not positive definite")
+
+
+class LocalGPC(nat.Handle):
+    """LocalGPC(X, y, k, m=64, epsilon=1e-10, max_iter=0): X d x n, y in {-1, +1} of length n, k a cov_func() of a kernel with a batched
+    small-model path, m the neighbours a test point's classifier is fitted on (1 .. 128; clamped to n); epsilon and max_iter: the mode
+    search's stop threshold and cap (0 selects 100, at most 1000).  The object holds X and y on the device until .close(); nothing is
+    fitted before a predict."""
+    _free = "gprc_lgpr_free"
+
+    def __init__(self, X, y, k, m=64, epsilon=1e-10, max_iter=0, ctx=None):
+        m = _check_m(m, "LocalGPC")
+        Xm = np.asfortranarray(as_points(X))
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+        if y.ndim != 1 or y.size != Xm.shape[1]:
+            raise ValueError("length(y) == ncol(X) is not TRUE")
+        if Xm.shape[1] < 1:
+            raise ValueError("ncol(X) >= 1 is not TRUE")
+        if not np.all(np.abs(y) == 1.0):
+            raise ValueError("LocalGPC: the labels must be -1 or +1")
+        k = self._checked_kernel(k, Xm.shape[0])
+        d, n = Xm.shape
+        self._X, self._y, self._k, self._m = Xm, y, k, min(m, n)
+        self._info = self._iters = None
+        self._model = C.c_void_p()
+        self._ctx = ctx or nat.default_context()
+        _, pp, npar = nat.params_array(k.native_params(d))
+        nat.check(nat.lib().gprc_lgpc_create(self._ctx.handle, k.gprc_kernel[0], pp, npar, Xm.ctypes.data, d, n, y.ctypes.data, m, float(epsilon),
+                                             int(max_iter), C.byref(self._model)))
+
+    @staticmethod
+    def _checked_kernel(k, d):
+        k = require_tagged(k, "LocalGPC")
+        if k.gprc_kernel[0] not in BATCHED_KERNELS:
+            raise ValueError("LocalGPC: the kernel has no batched small-model path (sqrexp, gammaexp, rationalquadratic, sqrexp_ard and the "
+                             "Matern kernels have)")
+        k.native_params(d)
+        return k
+
+    def _points(self, X_star):
+        return np.asfortranarray(as_test_points(X_star, self._X.shape[0]))
+
+    def _predict(self, X_star, latent, prob):
+        handle = self.handle
+        Xs = self._points(X_star)
+        ns = Xs.shape[1]
+        fs, vf = (np.empty(ns), np.empty(ns)) if latent else (None, None)
+        pr = np.empty(ns) if prob else None
+        iters, info = np.zeros(ns, dtype=np.intc), np.zeros(ns, dtype=np.intc)
+        nat.check(nat.lib().gprc_lgpc_predict(handle, Xs.ctypes.data, ns, nat.ptr(fs), nat.ptr(vf), nat.ptr(pr), iters.ctypes.data, info.ctypes.data))
+        self._iters, self._info = iters, info
+        return fs, vf, pr
+
+    def predict_latent(self, X_star):
+        """(fs_bar[n*], Vfs[n*]): the latent mean and variance of every test point's own classifier; NaN where .info != 0"""
+        return self._predict(X_star, True, False)[:2]
+
+    def predict_class(self, X_star):
+        """P(y* = +1) of every test point, `GPC.predict_class`'s integral on its own classifier; NaN where .info != 0"""
+        return self._predict(X_star, False, True)[2]
+
+    def neighbours(self, X_star):
+        """(idx[n*, m], dist2[n*, m]) of the test points in the model's metric, the order the local models take their points in"""
+        handle = self.handle
+        Xs = self._points(X_star)
+        ns, m = Xs.shape[1], self._m
+        idx, dist = np.empty((ns, m), dtype=np.intc), np.empty((ns, m))
+        nat.check(nat.lib().gprc_lgpr_neighbours(handle, Xs.ctypes.data, ns, idx.ctypes.data, dist.ctypes.data, m))
+        return idx, dist
+
+    def set_params(self, k):
+        """another kernel object of the same kernel family and size; X and y stay on the device"""
+        k = self._checked_kernel(k, self._X.shape[0])
+        if k.gprc_kernel[0] != self._k.gprc_kernel[0]:
+            raise ValueError("LocalGPC.set_params: the kernel cannot change, only its parameters")
+        _, pp, npar = nat.params_array(k.native_params(self._X.shape[0]))
+        nat.check(nat.lib().gprc_lgpc_set_params(self.handle, pp, npar))
+        self._k = k
+
+    X = property(lambda self: self._X)
+    y = property(lambda self: self._y)
+    k = property(lambda self: self._k)
+    m = property(lambda self: self._m, doc="neighbours per test point, min(m, n)")
+    info = property(lambda self: self._info, doc="per test point of the last predict: gprc_gpc_batch_fit's info of its local classifier")
+    iters = property(lambda self: self._iters, doc="per test point of the last predict: the Newton iterations of its local classifier")

@@ -248,6 +248,48 @@ GPRC_API int gprc_gpr_batch_loo(gprc_batch_model* model, double* mean_out, doubl
 GPRC_API int gprc_gpr_batch_get_alpha(gprc_batch_model* model, double* alpha_out);
 GPRC_API int gprc_batch_model_dims(const gprc_batch_model* model, int64_t* B_out, int64_t* d_out, int64_t* n_max_out);
 GPRC_API int gprc_batch_model_free(gprc_batch_model* model);
+/* Laplace GP classifiers in batches ("Batched and local GPC"): gprc_gpc_fit (flags = 0) for B small models in one
+ * call, one model of at most GPRC_BATCH_MAX_N points per workgroup -- K, every Newton iteration of the mode search from f = 0, the stop
+ * rule |objective - last| < epsilon and the final factorisation of B = I + sqrt(W) K sqrt(W) without leaving the CU or asking the host.
+ *   params, X, y, n_each, the strides   exactly gprc_gpr_batch_fit's (there is no noise); y in {-1, +1}, not checked on the device
+ *   epsilon    > 0, the absolute stop threshold;   max_iter <= 0 selects 100, at most 1000
+ *   logq_out   HOST, B: objective - sum log L_ii at the mode, the Laplace log evidence (gprc_gpc_logq_grad's value)
+ *   iters_out  HOST, B, may be NULL: the Newton iterations taken
+ *   info_out   HOST, B: 0 converged; k > 0 the first non-positive pivot of B, 1-based (B has eigenvalues >= 1: only non-finite input gives
+ *              one); GPRC_BATCH_GPC_MAXITER the cap was reached; GPRC_BATCH_GPC_NONFINITE the objective was not finite
+ * A flagged model (info != 0) stops at once, is not retried and does not fail the call: GPRC_OK, and its logq, f_hat and every
+ * prediction are NaN; the other models are unaffected.  A model's outputs are the same bits alone (B = 1) and anywhere in any batch --
+ * however long the other models iterate --, with shared and with strided data, from host and from device pointers, with and without
+ * iters_out, on every call.  Against gprc_gpc_fit they agree to rounding, and the iteration counts to one step where a decrement lies
+ * within rounding of epsilon.  The object is a gprc_batch_model of the classifier kind: gprc_batch_model_dims and gprc_batch_model_free
+ * serve it; gprc_gpr_batch_predict, _predict_grad, _loo and _get_alpha return GPRC_ERR_ARG for it, as the gprc_gpc_batch_* calls do for a
+ * regression batch.  B = 0 returns GPRC_OK and *model_out = NULL.
+ * MEMORY: 128^2 doubles (128 KiB) per model for L^-1 diag(sqrt(W)), held until gprc_batch_model_free, plus 2 * 128 + d * n_max (or
+ * x_stride) + n_max (or y_stride) + n_params + 6 doubles per model; during the fit another 128^2 doubles (K) per model of a launch, at
+ * most 32 MiB, from the context's pool.
+ * GPRC_ERR_ARG: gprc_gpr_batch_fit's cases (a null context, params, X, y, model_out, logq_out or info_out, a kernel outside the eight,
+ * n_max > GPRC_BATCH_MAX_N, n_max < 1, d < 1, n_params < 1, ld_params < n_params, a stride that is neither 0 nor at least one model's
+ * extent, an n_each outside 1 .. n_max), epsilon not > 0, max_iter > 1000.
+ *
+ * gprc_gpc_batch_predict_latent: fs_bar = k*^T g and Vfs = k(x*, x*) - |L^-1 (sqrt(W) o k*)|^2 (R/GPCclass.R:112-115, as
+ * gprc_gpc_predict_latent) of every model at its own test points: gprc_gpr_batch_predict's launch, arguments, layout, bit rules and
+ * argument errors, on the stored g and L^-1 diag(sqrt(W)); either output may be NULL, not both.
+ * gprc_gpc_batch_predict_class: P(y* = +1) of every model at its test points, gprc_gpc_predict_class's integral (the reference's use of
+ * the variance as dnorm's sd included) over the latent prediction; prob_out host or device, model b's values at [b * ld_out + j],
+ * entries behind ns_each[b] are left as they were; MEMORY: 2 * B * ld_out doubles from the context's pool.  GPRC_ERR_ARG: the latent
+ * call's cases, a null prob_out.
+ * gprc_gpc_batch_get_f_hat: f_hat_out HOST, B x n_max: the modes, zero behind n_b, NaN for a flagged model. */
+#define GPRC_BATCH_GPC_MAXITER (-1)
+#define GPRC_BATCH_GPC_NONFINITE (-2)
+GPRC_API int gprc_gpc_batch_fit(gprc_ctx* ctx, int kernel, int64_t B, const double* params, int n_params, int64_t ld_params, const double* X,
+                                int64_t d, int64_t n_max, int64_t x_stride, const double* y, int64_t y_stride, const int64_t* n_each,
+                                double epsilon, int max_iter, gprc_batch_model** model_out, double* logq_out, int* iters_out,
+                                int* info_out);
+GPRC_API int gprc_gpc_batch_predict_latent(gprc_batch_model* model, const double* X_star, int64_t ns_max, int64_t xs_stride,
+                                           const int64_t* ns_each, double* fs_bar_out, double* Vfs_out, int64_t ld_out);
+GPRC_API int gprc_gpc_batch_predict_class(gprc_batch_model* model, const double* X_star, int64_t ns_max, int64_t xs_stride,
+                                          const int64_t* ns_each, double* prob_out, int64_t ld_out);
+GPRC_API int gprc_gpc_batch_get_f_hat(gprc_batch_model* model, double* f_hat_out);
 /* Exact k-nearest-neighbours by brute force in float64 ("Local GPR"): for every test point j the m training points
  * with the smallest key (dist2, index), lexicographic -- the lower index first among equal distances -- in ascending key order,
  *   dist2(j, i) = sum_c ((x*_jc - x_ic) * s_c)^2,   c ascending, one fused multiply-add per term;  s_c = 1 without a scale.
@@ -290,6 +332,28 @@ GPRC_API int gprc_lgpr_neighbours(gprc_local_model* model, const double* X_star,
                                   int64_t ld_out);
 GPRC_API int gprc_lgpr_dims(const gprc_local_model* model, int64_t* n_out, int64_t* d_out, int64_t* m_out);
 GPRC_API int gprc_lgpr_free(gprc_local_model* model);
+/* The local classifier ("Batched and local GPC"): every test point is classified by the Laplace GPC of its own m
+ * nearest training points.  gprc_lgpc_create is gprc_lgpr_create without the noise and with the mode search's epsilon (> 0) and max_iter
+ * (<= 0 selects 100, at most 1000); y in {-1, +1}; the object is a gprc_local_model of the classifier kind: gprc_lgpr_neighbours,
+ * gprc_lgpr_dims and gprc_lgpr_free serve it; gprc_lgpr_predict, gprc_lgpr_set_params and the three gprc_lgpr_vecchia_* calls return
+ * GPRC_ERR_ARG for it, as the gprc_lgpc_* calls do for a regression object.  gprc_lgpc_set_params swaps the parameters without another
+ * upload.  gprc_lgpc_predict: per chunk of at most 2048 test points the neighbour search in the model's metric, the gather,
+ * gprc_gpc_batch_fit on one model per point (its points in neighbour order), the latent prediction and the class probability.
+ *   X_star                           host or device, d x n_star
+ *   fs_bar_out, Vfs_out, prob_out    host or device, n_star values each: gprc_gpc_batch_predict_latent's and _class's; each may be NULL,
+ *                                    not all three; the others keep their bits
+ *   iters_out, info_out              HOST, n_star ints, may be NULL: gprc_gpc_batch_fit's of point j's local model; a flagged point's
+ *                                    outputs are NaN, the call does not fail and the other points are unaffected
+ * A test point's bits depend on the model, the parameters and its own coordinates only: not on n_star, the chunk it falls into or its
+ * place.  MEMORY: d * n + n doubles held by the object; during a predict 128 KiB + (d + 2) m + 2 * 128 doubles per point of a chunk, at most
+ * 256 MiB + the slabs and 32 MiB of K, from the context's pool.
+ * GPRC_ERR_ARG: gprc_lgpr_create's and gprc_lgpr_predict's cases, epsilon not > 0, max_iter > 1000, all three outputs NULL, iters_out or
+ * info_out in device memory, an object of the other kind. */
+GPRC_API int gprc_lgpc_create(gprc_ctx* ctx, int kernel, const double* params, int n_params, const double* X, int64_t d, int64_t n,
+                              const double* y, int64_t m, double epsilon, int max_iter, gprc_local_model** model_out);
+GPRC_API int gprc_lgpc_set_params(gprc_local_model* model, const double* params, int n_params);
+GPRC_API int gprc_lgpc_predict(gprc_local_model* model, const double* X_star, int64_t n_star, double* fs_bar_out, double* Vfs_out,
+                               double* prob_out, int* iters_out, int* info_out);
 /* The predecessor-constrained search (the conditioning sets of the Vecchia likelihood below): for every query i in [first, first + count),
  * a column of X itself, the m smallest keys (dist2, j) among the columns j < i of X.  Distance formula, key, tie rule, NaN rule and the
  * layout of idx_out / dist_out (query i at row i - first) are exactly gprc_dev_knn's; ranks that no candidate fills (i < m) report -1
