@@ -47,6 +47,14 @@ constexpr int PB = 128;
 constexpr int BLD = 144;
 constexpr int PB_SMEM_DOUBLES = PB * BLD + 512 + PB;  // S, 2 x Wd, Wdiag
 constexpr size_t PB_SMEM_BYTES = PB_SMEM_DOUBLES * sizeof(double);
+// Where potf2_blocked_body leaves things in sm, for the kernels that go on working in its image (small_model.h):
+// the two 16 x 16 buffers (512 doubles, free between the body's calls), the diagonal of the inverse, and W[k][i] of the factored image
+// S -- the inverse sits transposed above the diagonal, its diagonal in the side array
+__device__ __forceinline__ double* pb_work(double* sm) { return sm + PB * BLD; }
+__device__ __forceinline__ double* pb_wdiag(double* sm) { return sm + PB * BLD + 512; }
+__device__ __forceinline__ double pb_w(const double* S, const double* Wdiag, int k, int i) {
+  return k > i ? S[i + k * BLD] : (k == i ? Wdiag[i] : 0.0);
+}
 
 // sqrt(d) and 1/sqrt(d) from v_rsq_f64 + two Newton steps (+ one correction of the root)
 __device__ __forceinline__ void sqrt_rsqrt(double d, double& root, double& rinv) {
@@ -213,8 +221,8 @@ __device__ __attribute__((noinline)) void potf2_blocked_body(double* sm, double*
   static_assert(NW >= 8, "phase B needs one wave per task: 7 tasks per step");
   constexpr int TYS = NW / 2;          // column groups of the 128-row load / store loops (NW * 64 threads / 128 rows)
   double* S = sm;                      // PB x BLD
-  double* Wd2 = sm + PB * BLD;         // 2 x (16 x 16): the 16x16 inverse of step s lives in buffer s & 1
-  double* Wdiag = Wd2 + 512;           // PB
+  double* Wd2 = pb_work(sm);           // 2 x (16 x 16): the 16x16 inverse of step s lives in buffer s & 1
+  double* Wdiag = pb_wdiag(sm);        // PB
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int q = lane >> 4, r = lane & 15;

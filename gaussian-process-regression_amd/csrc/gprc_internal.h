@@ -17,7 +17,8 @@
 //   gprc_local.hip  the local GPR: device nearest-neighbour search (one front for both searches), then one batched small model per test
 //                   point (on gprc_batch's entry points); the Vecchia likelihood on the same object; the local classifier likewise
 //   gprc_mgpu.hip   the multi-GPU layer, on the public ABI only
-// Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip) and
+// Device cores shared between kernel files are headers: chol_tile.h (the Cholesky side: kernels_gemm.hip, kernels_chol.hip),
+// small_model.h (built on the other two: what the kernels that run one model of at most 128 points per workgroup share) and
 // pair_tile.h (the covariance side: the 128 x 64 pairwise tile of kernels_fill.hip, kernels_grad.hip, kernels_pgrad.hip and
 // kernels_sgrad.hip, the kernel-id dispatcher and the set of kernels with an exact gradient; kernels_paths.hip takes the tile
 // extents, the staging, the dispatcher and, for its gradient product, pair_weight from it and has its own lane layout, the MFMA
@@ -85,6 +86,14 @@ int ensure_dynamic_lds(size_t bytes) {
   GPRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   if (known) set[dev].store(true, std::memory_order_release);
   return 0;
+}
+// one launch of a kernel that needs the raised limit: the limit, the launch, the launch's error (which names `who`, the caller's kernel)
+template <auto Kernel, class... Args>
+int launch_with_lds(const char* who, dim3 grid, dim3 block, size_t bytes, hipStream_t s, const Args&... args) {
+  GPRC_TRY(ensure_dynamic_lds<Kernel>(bytes));
+  hipLaunchKernelGGL(Kernel, grid, block, bytes, s, args...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, who, __FILE__, __LINE__);
 }
 
 // ---- in-library event profiler (bench.py's live roofline numbers) ---------------------------------

@@ -39,8 +39,9 @@
 //                      ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7))  (ARD: the same per coordinate)
 // No atomics except the factor body's one compare-and-swap on the model's info word; no register spills (the 8 bytes of scratch a lane that
 // the compiler reports are the frame of the call into the factor body, which is not inlined: profiles/batch_isa.txt).
-#include "chol_tile.h"
-#include "pair_tile.h"
+// The squared distance, the spec load, the image's entry rule, the two products with W and the 128-entry sums are small_model.h's, shared
+// with the other kernels that run one small model per workgroup; what a pair adds to the theta sums is pair_tile.h's theta_terms.
+#include "small_model.h"
 
 namespace gprc {
 
@@ -48,33 +49,11 @@ namespace {
 
 constexpr int BT_WAVES = 8;
 constexpr int BT_MAXBLK = 5;                              // 36 blocks of the lower triangle over eight waves: at most five a wave
-constexpr int BT_SPEC_DOUBLES = (sizeof(KernelSpec) + 7) / 8;
-constexpr int BT_EXTRA = 3 * PB + BT_WAVES * PT_D + MAX_PARAMS + BT_SPEC_DOUBLES;   // y, z, alpha; red; gacc; the spec
+constexpr int BT_EXTRA = 3 * PB + BT_WAVES * PT_D + MAX_PARAMS + SPEC_DOUBLES;   // y, z, alpha; red; gacc; the spec
 constexpr size_t BT_SMEM_BYTES = PB_SMEM_BYTES + sizeof(double) * BT_EXTRA;
 static_assert(BT_SMEM_BYTES <= 163840, "the batch kernel's LDS must fit a workgroup's 160 KiB");
-constexpr double LOG_2PI = 1.8378770664093453;
 
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-// s_ij of points i, j < n_b of the model at X (point-major, d coordinates each); SCALED: the coordinates times p[r] = 1 / l_r first
-template <bool SCALED>
-__device__ __forceinline__ double bt_sqdist(const double* X, int i, int j, int64_t d, const double* p) {
-  const double* xi = X + (int64_t)i * d;
-  const double* xj = X + (int64_t)j * d;
-  double s = 0.0;
-  for (int64_t r = 0; r < d; ++r) {
-    double df;
-    if constexpr (SCALED) df = bt_scaled_diff(xi[r], xj[r], p[r]);
-    else df = xi[r] - xj[r];
-    s = fma(df, df, s);
-  }
-  return s;
-}
-
-// W[k][i] of the factored image: the inverse sits transposed above the diagonal, its diagonal in the side array
-__device__ __forceinline__ double bt_w(const double* S, const double* Wdiag, int k, int i) {
-  return k > i ? S[i + k * BLD] : (k == i ? Wdiag[i] : 0.0);
-}
 
 __device__ __forceinline__ double bt_sum8(const double* r, int stride) {
   return sum4_pairs(r[0], r[stride], r[2 * stride], r[3 * stride]) + sum4_pairs(r[4 * stride], r[5 * stride], r[6 * stride], r[7 * stride]);
@@ -85,7 +64,7 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr bool ARD = is_ard(KID);
   double* S = sm;
-  const double* Wdiag = sm + PB * BLD + 512;
+  const double* Wdiag = pb_wdiag(sm);
   double* yv = sm + PB_SMEM_DOUBLES;
   double* zv = yv + PB;                 // z = W y, later the diagonal of M
   double* av = zv + PB;                 // alpha
@@ -104,24 +83,14 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
   const int64_t d = a.d;
 
   // ---- load
-  if (t == 0) { ks.id = KID; ks.n_params = a.n_params; }
-  for (int k = t; k < a.np_store; k += 512) ks.p[k] = prm[k];
+  load_spec<KID>(ks, prm, a.np_store, a.n_params, t, 512);
   if (t < PB) yv[t] = t < nb ? y[t] : 0.0;
   __syncthreads();
 
   // ---- fill: row i = t & 127, columns (t >> 7) + 4 c
   for (int e = t; e < PB * PB; e += 512) {
     const int i = e & (PB - 1), j = e >> 7;
-    double v = 0.0;
-    if (i >= j) {
-      if (i < nb) {
-        v = kernel_value<KID>(bt_sqdist<ARD>(X, i, j, d, ks.p), ks);
-        if (i == j) v += noise;
-      } else {
-        v = i == j ? 1.0 : 0.0;
-      }
-    }
-    S[i + j * BLD] = v;
+    S[i + j * BLD] = image_entry(i, j, nb, noise, [=, &ks] { return kernel_value<KID>(sqdist<ARD>(X + (int64_t)i * d, X + (int64_t)j * d, d, ks.p), ks); });
   }
   __syncthreads();
 
@@ -132,38 +101,17 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
   __syncthreads();
 
   // ---- solve
-  {
-    const int k = t >> 2, q = t & 3;
-    double acc = 0.0;
-    if (k < nb)
-      for (int i = q; i < k; i += 4) acc = fma(S[i + k * BLD], yv[i], acc);
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    if (q == 0) zv[k] = k < nb ? fma(Wdiag[k], yv[k], acc) : 0.0;
-  }
+  winv_forward(S, Wdiag, yv, nb, t, [zv](int k, double z) { zv[k] = z; });
   __syncthreads();
-  {
-    const int i = t >> 2, q = t & 3;
-    double acc = 0.0;
-    if (i < nb)
-      for (int k = i + 1 + q; k < nb; k += 4) acc = fma(S[i + k * BLD], zv[k], acc);
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    if (q == 0) {
-      const double al = i < nb ? fma(Wdiag[i], zv[i], acc) : 0.0;
-      av[i] = al;
-      a.alpha[b * PB + i] = al;
-    }
-  }
+  winv_transposed(S, Wdiag, zv, nb, t, [av, al_out = a.alpha + b * PB](int i, double al) {
+    av[i] = al;
+    al_out[i] = al;
+  });
   __syncthreads();
   {
     double ya = 0.0, lg = 0.0;
     if (t < nb) { ya = yv[t] * av[t]; lg = log(S[t + t * BLD]); }
-    if (wave < 2) {
-      ya = wave_sum(ya);
-      lg = wave_sum(lg);
-      if (lane == 0) { red[wave] = ya; red[2 + wave] = lg; }
-    }
+    sum128(ya, lg, red, wave, lane);
     __syncthreads();
     if (t == 0) out[0] = -0.5 * (red[0] + red[1]) - (red[2] + red[3]) - 0.5 * (double)nb * LOG_2PI;
   }
@@ -190,30 +138,12 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) m[g] = av[i0 + lr + 4 * g] * av[j0 + lc];
       for (int k0 = i0; k0 < kend; k0 += 4)
-        m = __builtin_amdgcn_mfma_f64_16x16x4f64(bt_w(S, Wdiag, k0 + lr, i0 + lc), bt_w(S, Wdiag, k0 + lr, j0 + lc), m, 0, 0, 1);
+        m = __builtin_amdgcn_mfma_f64_16x16x4f64(pb_w(S, Wdiag, k0 + lr, i0 + lc), pb_w(S, Wdiag, k0 + lr, j0 + lc), m, 0, 0, 1);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int i = i0 + lr + 4 * g, j = j0 + lc;
         if (i == j && i < nb) zv[i] = m[g];
-        if (i < nb && i > j) {
-          const double gij = 2.0 * m[g];
-          const double s = bt_sqdist<ARD>(X, i, j, d, ks.p);
-          if constexpr (KID == GPRC_GAMMAEXP) {
-            if (s > 0.0) {
-              const PairW pw = cross_weight<KID>(s, ks);
-              a0 = fma(gij, pw.hs, a0);
-              a1 = fma(gij, pw.h2, a1);
-            }
-          } else {
-            const PairW pw = cross_weight<KID>(s, ks);
-            if constexpr (ARD) {
-              wh[kb][g] = gij * pw.h;
-            } else {
-              a0 = fma(gij, pw.hs, a0);
-              if constexpr (KID == GPRC_RATQUAD) a1 = fma(gij, pw.h2, a1);
-            }
-          }
-        }
+        if (i < nb && i > j) theta_terms<KID>(2.0 * m[g], sqdist<ARD>(X + (int64_t)i * d, X + (int64_t)j * d, d, ks.p), ks, a0, a1, wh[kb][g]);
       }
     }
   }
@@ -260,10 +190,7 @@ __global__ __launch_bounds__(512) void batch_logp_grad_kernel(BatchArgs a) {
   // ---- d / d noise: the diagonal of M (the barriers above stand between its writes and these reads)
   {
     double dm = t < nb ? zv[t] : 0.0;
-    if (wave < 2) {
-      dm = wave_sum(dm);
-      if (lane == 0) red[wave] = dm;
-    }
+    sum128(dm, red, wave, lane);
     __syncthreads();
     if (t == 0) out[1 + np] = red[0] + red[1];
   }
@@ -281,17 +208,10 @@ int launch_batch_logp_grad(hipStream_t s, int kernel, const BatchArgs& a, int64_
     return GPRC_ERR_ARG;
   }
   int rc = 0;
-  hipError_t e = hipSuccess;
   with_gradient_kernel(kernel, [&](auto kid) {
-    constexpr int KID = decltype(kid)::value;
-    rc = ensure_dynamic_lds<batch_logp_grad_kernel<KID>>(BT_SMEM_BYTES);
-    if (rc != 0) return;
-    hipLaunchKernelGGL((batch_logp_grad_kernel<KID>), dim3((unsigned)models), dim3(512), BT_SMEM_BYTES, s, a);
-    e = hipGetLastError();
+    rc = launch_with_lds<batch_logp_grad_kernel<decltype(kid)::value>>("batch_logp_grad_kernel", dim3((unsigned)models), dim3(512), BT_SMEM_BYTES, s, a);
   });
-  GPRC_TRY(rc);
-  GPRC_HIP(e);
-  return 0;
+  return rc;
 }
 
 }  // namespace gprc

@@ -7,12 +7,12 @@
 //            noise, n_b) into a KernelSpec in LDS; y, zero from n_b on; f = 0;
 //   fill     K, WITHOUT a noise term, whole and symmetric into the workgroup's 128^2 slab in device memory (L2-resident; the LDS cannot
 //            hold K beside the image of B): kernel_value<KID> of the squared distance of the pair (larger index first), ARD coordinates
-//            scaled by bt_scaled_diff as kernels_batch.hip scales them; rows and columns >= n_b are zero;
+//            scaled by bt_scaled_diff (small_model.h's sqdist, the one every small model takes); rows and columns >= n_b are zero;
 //   loop     it = 1, 2, ...:  pi = sigmoid(f), W = pi (1 - pi), sw = sqrt(W), b = W f + (y + 1) / 2 - pi  (zero from n_b on);
 //            the image S = I + (sw_i sw_j) K_ij (lower triangle, zero above, the identity from n_b on); potf2_blocked_body<8, false>
 //            (preloaded; nothing is stored: L stays in the lower triangle of the image, W_B = L^-1 transposed above it, its diagonal in
 //            the side array); t = K b; u = sw o t; z = W_B u; v = W_B^T z (the two triangular solves as products with the explicit
-//            inverse, as kernels_batch.hip forms z and alpha); a = b - sw o v; f = K a;
+//            inverse: small_model.h's winv_forward and winv_transposed); a = b - sw o v; f = K a;
 //            objective = -1/2 a.f - sum log(1 + exp(-y_i f_i)).  Thread 0 forms the objective and the verdict -- converged (it > 1 and
 //            |objective - last| < epsilon), a non-positive pivot (the model's info word, read back past L1), a non-finite objective,
 //            the cap (it = max_iter), or go on -- and writes both to LDS; after the barrier every thread reads the same bits and the
@@ -40,34 +40,18 @@
 //   a.f, sum log(1 + exp(-y f)), sum log L_ii    entry t to thread t < 128; each of the two waves by wave_sum; wave 0 + wave 1
 // No atomics on memory except the factor body's one compare-and-swap on the model's info word (and the load that reads it back); no
 // register spills: the scratch the compiler reports is the frame of the call into the factor body (profiles/batch_gpc_isa.txt).
-#include "chol_tile.h"
-#include "pair_tile.h"
+#include "small_model.h"
 
 namespace gprc {
 
 namespace {
 
-constexpr int GC_SPEC_DOUBLES = (sizeof(KernelSpec) + 7) / 8;
 constexpr int GC_CTL = 8;                                    // objective, verdict, 2 x 2 wave partials
-constexpr int GC_EXTRA = 7 * PB + GC_CTL + GC_SPEC_DOUBLES;  // y, f, sw, b, u, z, a; control; the spec
+constexpr int GC_EXTRA = 7 * PB + GC_CTL + SPEC_DOUBLES;  // y, f, sw, b, u, z, a; control; the spec
 constexpr size_t GC_SMEM_BYTES = PB_SMEM_BYTES + sizeof(double) * GC_EXTRA;
 static_assert(GC_SMEM_BYTES <= 163840, "the batched classifier's LDS must fit a workgroup's 160 KiB");
 static_assert(4 * PB <= 512, "the partial sums of a product with K live in the factor body's two 16 x 16 buffers");
 constexpr int GC_CONTINUE = -1000;                           // the verdict that keeps the loop going: no info code
-
-template <bool SCALED>
-__device__ __forceinline__ double gc_sqdist(const double* X, int i, int j, int64_t d, const double* p) {
-  const double* xi = X + (int64_t)i * d;
-  const double* xj = X + (int64_t)j * d;
-  double s = 0.0;
-  for (int64_t r = 0; r < d; ++r) {
-    double df;
-    if constexpr (SCALED) df = bt_scaled_diff(xi[r], xj[r], p[r]);
-    else df = xi[r] - xj[r];
-    s = fma(df, df, s);
-  }
-  return s;
-}
 
 __device__ __forceinline__ double gc_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }   // R/GPCclass.R:63
 
@@ -101,8 +85,8 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr bool ARD = is_ard(KID);
   double* S = sm;
-  double* part = sm + PB * BLD;                 // 4 x PB: the body's Wd buffers between its calls
-  const double* Wdiag = sm + PB * BLD + 512;
+  double* part = pb_work(sm);                   // 4 x PB: the body's Wd buffers between its calls
+  const double* Wdiag = pb_wdiag(sm);
   double* yv = sm + PB_SMEM_DOUBLES;
   double* fv = yv + PB;
   double* swv = fv + PB;
@@ -125,8 +109,7 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
   const double qnan = __builtin_nan("");
 
   // ---- load
-  if (t == 0) { ks.id = KID; ks.n_params = a.n_params; }
-  for (int k = t; k < a.np_store; k += 512) ks.p[k] = prm[k];
+  load_spec<KID>(ks, prm, a.np_store, a.n_params, t, 512);
   if (t < PB) { yv[t] = t < nb ? y[t] : 0.0; fv[t] = 0.0; }
   __syncthreads();
 
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
   for (int e = t; e < PB * PB; e += 512) {
     const int i = e & (PB - 1), j = e >> 7;
     double v = 0.0;
-    if (i < nb && j < nb) v = kernel_value<KID>(gc_sqdist<ARD>(X, i > j ? i : j, i > j ? j : i, d, ks.p), ks);
+    if (i < nb && j < nb) v = kernel_value<KID>(sqdist<ARD>(X + (int64_t)(i > j ? i : j) * d, X + (int64_t)(i > j ? j : i) * d, d, ks.p), ks);
     K[e] = v;
   }
   __syncthreads();
@@ -163,25 +146,10 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
     __syncthreads();
     if (t < PB) uv[t] = swv[t] * sum4_pairs(part[t], part[PB + t], part[2 * PB + t], part[3 * PB + t]);
     __syncthreads();
-    {                                                       // z = W_B u  (:82)
-      const int k = t >> 2, q = t & 3;
-      double acc = 0.0;
-      if (k < nb)
-        for (int i = q; i < k; i += 4) acc = fma(S[i + k * BLD], uv[i], acc);
-      acc += __shfl_xor(acc, 1, 64);
-      acc += __shfl_xor(acc, 2, 64);
-      if (q == 0) zv[k] = k < nb ? fma(Wdiag[k], uv[k], acc) : 0.0;
-    }
+    // z = W_B u  (:82);  v = W_B^T z  (:83),  a = b - sw o v  (:84)
+    winv_forward(S, Wdiag, uv, nb, t, [zv](int k, double z) { zv[k] = z; });
     __syncthreads();
-    {                                                       // v = W_B^T z  (:83),  a = b - sw o v  (:84)
-      const int i = t >> 2, q = t & 3;
-      double acc = 0.0;
-      if (i < nb)
-        for (int k = i + 1 + q; k < nb; k += 4) acc = fma(S[i + k * BLD], zv[k], acc);
-      acc += __shfl_xor(acc, 1, 64);
-      acc += __shfl_xor(acc, 2, 64);
-      if (q == 0) av[i] = i < nb ? bv[i] - swv[i] * fma(Wdiag[i], zv[i], acc) : 0.0;
-    }
+    winv_transposed(S, Wdiag, zv, nb, t, [=](int i, double v) { av[i] = i < nb ? bv[i] - swv[i] * v : 0.0; });
     __syncthreads();
     gc_kv_partials(K, av, nb, part, t);                     // f = K a  (:85)
     __syncthreads();
@@ -192,11 +160,7 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
         fv[t] = f;
         if (t < nb) { af = av[t] * f; ll = log(1.0 + exp(-yv[t] * f)); }
       }
-      if (wave < 2) {
-        af = wave_sum(af);
-        ll = wave_sum(ll);
-        if (lane == 0) { ctl[2 + wave] = af; ctl[4 + wave] = ll; }
-      }
+      sum128<2>(af, ll, ctl, wave, lane);
     }
     __syncthreads();
     if (t == 0) {                                           // :86-90, and what ends a model early
@@ -235,10 +199,7 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
   __syncthreads();
   {
     double lg = t < nb ? log(S[t + t * BLD]) : 0.0;
-    if (wave < 2) {
-      lg = wave_sum(lg);
-      if (lane == 0) ctl[2 + wave] = lg;
-    }
+    sum128<2>(lg, ctl, wave, lane);
   }
   __syncthreads();
   if (t == 0) {
@@ -264,7 +225,7 @@ __global__ __launch_bounds__(512) void batch_gpc_fit_kernel(BatchGpcArgs a) {
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) {
         const int c = ty + 4 * (c0 + u);
-        wv[u] = (k > c ? S[c + k * BLD] : (k == c ? wd : 0.0)) * swv[c];
+        wv[u] = (k > c ? S[c + k * BLD] : (k == c ? wd : 0.0)) * swv[c];   // (pb_w, W[k][k] read once)
       }
 #pragma unroll
       for (int u = 0; u < BATCH; ++u) Wt[k + (ty + 4 * (c0 + u)) * PB] = wv[u];
@@ -285,17 +246,10 @@ int launch_batch_gpc_fit(hipStream_t s, int kernel, const BatchGpcArgs& a, int64
     return GPRC_ERR_ARG;
   }
   int rc = 0;
-  hipError_t e = hipSuccess;
   with_gradient_kernel(kernel, [&](auto kid) {
-    constexpr int KID = decltype(kid)::value;
-    rc = ensure_dynamic_lds<batch_gpc_fit_kernel<KID>>(GC_SMEM_BYTES);
-    if (rc != 0) return;
-    hipLaunchKernelGGL((batch_gpc_fit_kernel<KID>), dim3((unsigned)models), dim3(512), GC_SMEM_BYTES, s, a);
-    e = hipGetLastError();
+    rc = launch_with_lds<batch_gpc_fit_kernel<decltype(kid)::value>>("batch_gpc_fit_kernel", dim3((unsigned)models), dim3(512), GC_SMEM_BYTES, s, a);
   });
-  GPRC_TRY(rc);
-  GPRC_HIP(e);
-  return 0;
+  return rc;
 }
 
 }  // namespace gprc

@@ -52,8 +52,7 @@
 //                      bt_scaled_diff, an exact 0 at a training point); the four lr groups as the mean's; then one multiplication by
 //                      -t_c or 2 t_c, t_c = deriv_tail_factor (ARD: times the record's 1 / l_c)
 // A gammaexp pair at distance 0 has h = 0 (pair_weight).  The gradient bits of a test point depend on its model and coordinates alone.
-#include "chol_tile.h"
-#include "pair_tile.h"
+#include "small_model.h"
 
 namespace gprc {
 
@@ -61,8 +60,7 @@ namespace {
 
 constexpr int BP_WAVES = BATCH_PREDICT_WAVES;
 constexpr int BP_THREADS = 64 * BP_WAVES;
-constexpr int BP_SPEC_DOUBLES = (sizeof(KernelSpec) + 7) / 8;
-constexpr size_t BP_SMEM_BYTES = sizeof(double) * (PB * BLD + PB + BP_SPEC_DOUBLES);
+constexpr size_t BP_SMEM_BYTES = sizeof(double) * (PB * BLD + PB + SPEC_DOUBLES);
 static_assert(BP_SMEM_BYTES <= 163840, "the batched predict kernel's LDS must fit a workgroup's 160 KiB");
 static_assert(BATCH_PREDICT_TILE == 16 && PB == 128 && BLD % 2 == 0, "the lane layout is the 16 x 16 x 4 MFMA's");
 
@@ -118,8 +116,7 @@ __global__ __launch_bounds__(BP_THREADS) void batch_predict_kernel(BatchPredictA
   const bool need_w = var || dvar;      // the image of W and the product V = W K*
 
   // ---- load: the spec, alpha, and (variance) rows and columns < kend of W, two rows a thread and load
-  if (t == 0) { ks.id = KID; ks.n_params = a.n_params; }
-  for (int k = t; k < a.np_store; k += BP_THREADS) ks.p[k] = prm[k];
+  load_spec<KID>(ks, prm, a.np_store, a.n_params, t, BP_THREADS);
   if (t < PB) av[t] = a.alpha[b * PB + t];
   if (need_w) {
     const double* W = a.W + b * (PB * PB);
@@ -358,17 +355,10 @@ int launch_batch_predict_any(const char* who, hipStream_t s, int kernel, const B
     return GPRC_ERR_ARG;
   }
   int rc = 0;
-  hipError_t e = hipSuccess;
   with_gradient_kernel(kernel, [&](auto kid) {
-    constexpr int KID = decltype(kid)::value;
-    rc = ensure_dynamic_lds<batch_predict_kernel<KID, GRAD>>(BP_SMEM_BYTES);
-    if (rc != 0) return;
-    hipLaunchKernelGGL((batch_predict_kernel<KID, GRAD>), dim3((unsigned)split, (unsigned)models), dim3(BP_THREADS), BP_SMEM_BYTES, s, a);
-    e = hipGetLastError();
+    rc = launch_with_lds<batch_predict_kernel<decltype(kid)::value, GRAD>>(who, dim3((unsigned)split, (unsigned)models), dim3(BP_THREADS), BP_SMEM_BYTES, s, a);
   });
-  GPRC_TRY(rc);
-  GPRC_HIP(e);
-  return 0;
+  return rc;
 }
 
 }  // namespace

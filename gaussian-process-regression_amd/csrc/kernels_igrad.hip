@@ -10,7 +10,7 @@
 // one double per lane, (index lane & 15, r = lane >> 4), straight from A and B; rows >= n and r >= R are exact zeros), and the
 // accumulator's layout -- col = lane & 15, row = (lane >> 4) + 4 reg -- decides which four pairs of a sub-tile a lane owns: it forms
 // their squared distances from the points in LDS (PT_D coordinates at a time, as everywhere else) and the theta integrands of
-// cross_weight (pair_tile.h) in place, so the weight makes no trip through LDS or HBM.  The ARD kernels' per-coordinate sums take
+// cross_weight (pair_tile.h; theta_terms adds them up) in place, so the weight makes no trip through LDS or HBM.  The ARD kernels' per-coordinate sums take
 // kernels_grad.hip's second coordinate pass, d <= 256.  What the device leaves is the sum WITHOUT the factors that do not depend on
 // (i, j): cross_grad_finish (kernels_sgrad.hip) applies them.  gammaexp's weight is 0 at s = 0.
 //
@@ -114,24 +114,8 @@ __global__ __launch_bounds__(256) void lowrank_grad_kernel(IgradArgs a) {
 #pragma unroll
     for (int sub = 0; sub < IG_SUB; ++sub)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const double gij = w[sub][g];
-        if constexpr (KID == GPRC_GAMMAEXP) {   // its weight and both integrands are 0 at s = 0: such a pair adds nothing
-          if (s[sub][g] > 0.0) {
-            const PairW pw = cross_weight<KID>(s[sub][g], a.ks);
-            a0 = fma(gij, pw.hs, a0);
-            a1 = fma(gij, pw.h2, a1);
-          }
-        } else {
-          const PairW pw = cross_weight<KID>(s[sub][g], a.ks);
-          if constexpr (ARD) {
-            s[sub][g] = gij * pw.h;
-          } else {
-            a0 = fma(gij, pw.hs, a0);
-            if constexpr (KID == GPRC_RATQUAD) a1 = fma(gij, pw.h2, a1);
-          }
-        }
-      }
+      for (int g = 0; g < 4; ++g)
+        theta_terms<KID>(w[sub][g], s[sub][g], a.ks, a0, a1, s[sub][g]);   // (ARD: weight x h takes the distance's place)
 
     if constexpr (ARD) {
       for (int64_t r0 = 0; r0 < a.d; r0 += PT_D) {

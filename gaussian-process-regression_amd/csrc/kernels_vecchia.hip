@@ -6,7 +6,7 @@
 //            [N(i) in neighbour order, then i LAST], p + 1 <= 128 of them, p = min(m, i); their indices and targets go to LDS, the
 //            coordinates are read through the indices wherever they are needed (L1 / L2) -- no gathered n m d copy exists;
 //   fill     K_y = K + noise I into an LDS image of 16 nblk rows and columns, nblk = ceil((p + 1) / 16) -- the model's own block count, not
-//            the launch's: kernel_value<KID> of the squared distance (kernels_batch.hip's chain: coordinates ascending, one fma chain, the
+//            the launch's: kernel_value<KID> of the squared distance (small_model.h's sqdist: coordinates ascending, one fma chain, the
 //            ARD kernels scale by 1 / l_c first); rows and columns >= p + 1 are the identity, everything above the diagonal is zero;
 //   factor   blocked right-looking Cholesky in place with chol_tile.h's pieces and NO inverse blocks: per 16-column step wave 0's diag16
 //            (the 16 x 16 diagonal block; its inverse W_ss stays transposed above that block's diagonal), the panel X_I = A_I W_ss^T and the
@@ -16,9 +16,9 @@
 //            the diagonal block against its stored inverse W_ss;
 //   cond     -log L_pp - 1/2 z_p^2 - 1/2 log 2 pi;
 //   gradient (when asked for) a' = a - z_p w (a'_p = 0), G = a a^T - a' a'^T - w w^T -- the difference of the full model's and the
-//            sub-model's alpha alpha^T - K_y^-1 -- contracted over the pairs r > s against cross_weight<KID> exactly as kernels_batch.hip
-//            contracts its M: pairs count twice, gammaexp skips s = 0, the ARD kernels park 2 G_rs h_rs in the image (L is no longer
-//            needed) and take a second pass over the coordinates; and sum_r G_rr for d / d noise.
+//            sub-model's alpha alpha^T - K_y^-1 -- contracted over the pairs r > s against cross_weight<KID> by pair_tile.h's theta_terms,
+//            which also contracts kernels_batch.hip's M: pairs count twice, gammaexp skips s = 0, the ARD kernels park 2 G_rs h_rs in the
+//            image (L is no longer needed) and take a second pass over the coordinates; and sum_r G_rr for d / d noise.
 // What a point leaves: cond_i, then the n_params sums WITHOUT the factors that do not depend on the pair, then sum_r G_rr, at
 // out + (i - i0) (n_params + 2); its info word (0, or the first non-positive pivot, 1-based).  A flagged point's values are all NaN.
 // vecchia_reduce_kernel then adds groups of 256 consecutive points BY GLOBAL INDEX (launches start at multiples of 256) into one row per
@@ -37,8 +37,7 @@
 //   sum G_rr           entry r to thread r < 128; each of the two waves by wave_sum; wave 0 + wave 1
 //   groups of 256      point i to thread i mod 256; wave_sum; (w0 + w1) + (w2 + w3)
 // No atomics except the one compare-and-swap on the workgroup's LDS flag; no scratch (profiles/vecchia_isa.txt).
-#include "chol_tile.h"
-#include "pair_tile.h"
+#include "small_model.h"
 
 namespace gprc {
 
@@ -46,28 +45,12 @@ namespace {
 
 constexpr int VC_THREADS = 256;
 constexpr int VC_WAVES = VC_THREADS / 64;
-constexpr double VC_LOG_2PI = 1.8378770664093453;
 
 constexpr int vc_n(int nbmax) { return 16 * nbmax; }
 constexpr int vc_ld(int nbmax) { return 16 * nbmax + 16; }   // + 16: consecutive k-slices of an MFMA operand move by 32 banks, as BLD does
 // S, Wd, wdiag, six vectors (y, z, a, w, two right-hand sides), the waves' partials, the indices (ints), three words
 constexpr int vc_lds_doubles(int nbmax) { return vc_n(nbmax) * vc_ld(nbmax) + 256 + 7 * vc_n(nbmax) + VC_WAVES * PT_D + vc_n(nbmax) / 2 + 2; }
 static_assert(sizeof(double) * vc_lds_doubles(8) <= 163840, "the widest image must fit a workgroup's 160 KiB");
-
-// s_ij of the points gi, gj of X (point-major, d coordinates each); SCALED: the coordinates times p[c] = 1 / l_c first
-template <bool SCALED>
-__device__ __forceinline__ double vc_sqdist(const double* X, int gi, int gj, int64_t d, const double* p) {
-  const double* xi = X + (int64_t)gi * d;
-  const double* xj = X + (int64_t)gj * d;
-  double s = 0.0;
-  for (int64_t c = 0; c < d; ++c) {
-    double df;
-    if constexpr (SCALED) df = bt_scaled_diff(xi[c], xj[c], p[c]);
-    else df = xi[c] - xj[c];
-    s = fma(df, df, s);
-  }
-  return s;
-}
 
 __device__ __forceinline__ double vc_sum16(double v) {   // the 16 lanes of a row, every lane gets the sum
   v += __shfl_xor(v, 8, 64);
@@ -122,16 +105,10 @@ __global__ __launch_bounds__(VC_THREADS) void vecchia_kernel(const VecchiaArgs a
   // ---- fill
   for (int e = t; e < Nm * Nm; e += VC_THREADS) {
     const int c = e / Nm, r = e - c * Nm;
-    double v = 0.0;
-    if (r >= c) {
-      if (r < np1) {
-        v = kernel_value<KID>(vc_sqdist<ARD>(a.X, pts[r], pts[c], d, ks.p), ks);
-        if (r == c) v += a.noise;
-      } else {
-        v = r == c ? 1.0 : 0.0;
-      }
-    }
-    S[r + c * LD] = v;
+    S[r + c * LD] = image_entry(r, c, np1, a.noise, [=, &a, &ks] {
+      const int gr = pts[r], gc = pts[c];
+      return kernel_value<KID>(sqdist<ARD>(a.X + (int64_t)gr * d, a.X + (int64_t)gc * d, d, ks.p), ks);
+    });
   }
   __syncthreads();
 
@@ -207,7 +184,7 @@ __global__ __launch_bounds__(VC_THREADS) void vecchia_kernel(const VecchiaArgs a
   const double zp = zv[p];
   double* out = a.out + (i - a.i0) * a.out_stride;
   if (t == 0) {
-    out[0] = flagged ? qnan : -log(S[p + p * LD]) - 0.5 * (zp * zp) - 0.5 * VC_LOG_2PI;
+    out[0] = flagged ? qnan : -log(S[p + p * LD]) - 0.5 * (zp * zp) - 0.5 * LOG_2PI;
     a.info[i - a.i0] = words[2];
   }
   if (!a.want_grad) return;
@@ -223,22 +200,9 @@ __global__ __launch_bounds__(VC_THREADS) void vecchia_kernel(const VecchiaArgs a
       g = fma(-tv[r], tv[s], g);
       g = fma(-wv[r], wv[s], g);
       const double gij = 2.0 * g;
-      const double sq = vc_sqdist<ARD>(a.X, pts[r], pts[s], d, ks.p);
-      if constexpr (KID == GPRC_GAMMAEXP) {
-        if (sq > 0.0) {
-          const PairW pw = cross_weight<KID>(sq, ks);
-          a0 = fma(gij, pw.hs, a0);
-          a1 = fma(gij, pw.h2, a1);
-        }
-      } else {
-        const PairW pw = cross_weight<KID>(sq, ks);
-        if constexpr (ARD) {
-          S[r + s * LD] = gij * pw.h;   // over L, which nobody reads again
-        } else {
-          a0 = fma(gij, pw.hs, a0);
-          if constexpr (KID == GPRC_RATQUAD) a1 = fma(gij, pw.h2, a1);
-        }
-      }
+      const int gr = pts[r], gs = pts[s];
+      const double sq = sqdist<ARD>(a.X + (int64_t)gr * d, a.X + (int64_t)gs * d, d, ks.p);
+      theta_terms<KID>(gij, sq, ks, a0, a1, S[r + s * LD]);   // (ARD parks its value over L, which nobody reads again)
     }
   }
   const int np = a.n_params;
@@ -295,10 +259,7 @@ __global__ __launch_bounds__(VC_THREADS) void vecchia_kernel(const VecchiaArgs a
       g = fma(-tv[t], tv[t], g);
       g = fma(-wv[t], wv[t], g);
     }
-    if (wave < 2) {
-      g = wave_sum(g);
-      if (lane == 0) red[wave] = g;
-    }
+    sum128(g, red, wave, lane);
     __syncthreads();
     if (t == 0) out[1 + np] = flagged ? qnan : red[0] + red[1];
   }
@@ -328,11 +289,7 @@ __global__ __launch_bounds__(256) void vecchia_reduce_kernel(const VecchiaReduce
 
 template <int KID, int NBMAX>
 int launch_one(hipStream_t s, const VecchiaArgs& a, int64_t count) {
-  constexpr size_t bytes = sizeof(double) * vc_lds_doubles(NBMAX);
-  GPRC_TRY((ensure_dynamic_lds<vecchia_kernel<KID, NBMAX>>(bytes)));
-  hipLaunchKernelGGL((vecchia_kernel<KID, NBMAX>), dim3((unsigned)count), dim3(VC_THREADS), bytes, s, a);
-  GPRC_LAUNCH_CHECK();
-  return 0;
+  return launch_with_lds<vecchia_kernel<KID, NBMAX>>("vecchia_kernel", dim3((unsigned)count), dim3(VC_THREADS), sizeof(double) * vc_lds_doubles(NBMAX), s, a);
 }
 
 }  // namespace

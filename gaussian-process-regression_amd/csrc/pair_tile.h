@@ -8,7 +8,9 @@
 // the column broadcasts); the squared distance of a lane's 32 pairs accumulates in s0[16] / s1[16]; a per-kernel epilogue follows.
 // What is here: the tile shape, the staging loop, the distance loop of the contraction kernels, the wave and four-wave sums, R's `^`,
 // the weight h of a pair in dk / dx* (pair_weight) with the factor it leaves to the tail (deriv_tail_factor), the weight and theta
-// integrands of a pair in dk / dtheta for a general weight matrix (cross_weight),
+// integrands of a pair in dk / dtheta for a general weight matrix (cross_weight) and what such a pair adds to the theta sums (theta_terms:
+// kernels_igrad.hip and the small-model kernels of small_model.h; kernels_sgrad.hip's `pair` lambda feeds its dz sums from the same
+// weight inside the same branch and stays its own),
 // and for the host the derived constants of the contraction kernels, the set of kernels with an exact gradient and the dispatcher
 // from a run-time kernel id to a template instantiation.
 //
@@ -107,8 +109,8 @@ __device__ __forceinline__ double r_pow(double x, double y) {
 }
 
 // a p - b p as the contraction kernels form it from their staged coordinates: two rounded products, then the difference.  Contracted
-// into fma(a, p, -(b p)) the difference of two equal points would be the rounding error of the product, not 0.  (The batched kernels,
-// kernels_batch.hip and kernels_batch_predict.hip, scale their ARD coordinates with it: a test point equal to a training point is s = 0.)
+// into fma(a, p, -(b p)) the difference of two equal points would be the rounding error of the product, not 0.  (The small-model kernels,
+// small_model.h's sqdist and kernels_batch_predict.hip, scale their ARD coordinates with it: a test point equal to a training point is s = 0.)
 __device__ __forceinline__ double bt_scaled_diff(double a, double b, double p) {
 #pragma clang fp contract(off)
   const double ap = a * p, bp = b * p;
@@ -220,6 +222,28 @@ __device__ __forceinline__ PairW cross_weight(double s, const KernelSpec& ks) {
   } else {                                                            // rationalquadratic: p[1] = alpha, p[2] = 1 / (2 alpha l^2)
     const double x = s * ks.p[2], q = 1.0 + x, lq = log1p(x), h = exp(-ks.p[1] * lq) / q;
     return {h, h * s, h * (x - q * lq)};
+  }
+}
+
+// what one pair of squared distance s and weight gij adds to the theta sums: gammaexp skips s = 0 (its weight and both integrands are 0
+// there) and takes hs and h2; the ARD kernels park gij h in `keep` for their second pass over the coordinates; ratquad takes hs and h2;
+// everyone else hs.  kernels_batch.hip, kernels_vecchia.hip and kernels_igrad.hip: the three differ in where `keep` lives.
+template <int KID>
+__device__ __forceinline__ void theta_terms(double gij, double s, const KernelSpec& ks, double& a0, double& a1, double& keep) {
+  if constexpr (KID == GPRC_GAMMAEXP) {
+    if (s > 0.0) {
+      const PairW pw = cross_weight<KID>(s, ks);
+      a0 = fma(gij, pw.hs, a0);
+      a1 = fma(gij, pw.h2, a1);
+    }
+  } else {
+    const PairW pw = cross_weight<KID>(s, ks);
+    if constexpr (is_ard(KID)) {
+      keep = gij * pw.h;
+    } else {
+      a0 = fma(gij, pw.hs, a0);
+      if constexpr (KID == GPRC_RATQUAD) a1 = fma(gij, pw.h2, a1);
+    }
   }
 }
 
